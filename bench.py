@@ -53,6 +53,37 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(path, result, ranked, dist, rank, world):
+    """--dump-outputs: the answer of one timed step as the caller received it from Pipeline.wait, queries in batch order (ranks
+    concatenated in rank order): count.npy (the operator's return value per query, float64) and, for the ranked operators,
+    tlen.npy (results per query, float64) and topk.npy (each query's scores, descending, float32). The caller's top-k rows are
+    padded with -inf past tlen; the dump writes 0 there, so every value is finite and tlen still says where a row ends. and / or
+    return no top-k (ds2i_hip.h), so they write count.npy alone. Above DUMP_CAP_BYTES a fixed, seeded sample of the queries is
+    written and rows.npy holds their positions in the batch."""
+    import numpy as np
+    from ds2i_amd import sharding as sh
+    count, topk, tlen = (sh.gather_concat(dist, rank, world, a) for a in result)
+    if rank != 0:
+        return
+    arrays = {"count": count.astype(np.float64)}
+    if ranked:
+        arrays["tlen"] = tlen.astype(np.float64)
+        arrays["topk"] = np.where(np.arange(topk.shape[1])[None, :] < tlen[:, None], topk, 0).astype(np.float32)
+    n = len(count)
+    row_bytes = 8 + (8 + 4 * topk.shape[1] if ranked else 0) + 8  # + 8: the row's entry in rows.npy
+    if n * row_bytes > DUMP_CAP_BYTES:
+        rows = np.sort(np.random.default_rng(0xD0E5).choice(n, DUMP_CAP_BYTES // row_bytes, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+    log("--dump-outputs: %s of the last timed step (%d of %d queries) in %s" % (", ".join(sorted(arrays)), len(arrays["count"]), n, path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -71,7 +102,12 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N>1: weak = every rank its own 4096-query batches; strong = one stream of batches cut into N slices")
     ap.add_argument("--traffic-json", default=None, help="rocprofv3 --pmc derived HBM bytes per launch (profiles/*.json)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the answer of the last timed step (what Pipeline.wait returned) as DIR/<name>.npy, for comparing two "
+                         "builds output for output; pass --workload too so that the collection does not hang on the host's build rate")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -210,6 +246,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = sh.max_over_ranks(dist, elapsed)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, results[-1], args.op in ("ranked_and", "wand", "maxscore", "ranked_or"), dist, rank, world)
     count, topk, tlen = results[0]
     # spread of the step time: intervals between consecutive batch completions in the pipelined region (the first `depth`
     # completions include the ramp-up of the pipeline and are left out when there are enough steps)

@@ -424,11 +424,6 @@ extern "C" {
 
 const char* ds2i_hip_last_error(void) { return ds2i_get_error(); }
 
-// The kernel classes of a batch run on one stream each, uploads and merges on two more; with the HIP default of 4
-// hardware queues several of them end up sharing one (the null stream owns a queue) and serialise. Ask for more
-// before the runtime initialises; an explicit setting of the user wins.
-__attribute__((constructor)) static void ds2i_hip_more_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
-
 // The knobs (knobs.hpp) are read from the environment by every ds2i_hip_index_open -- the one place the library reads it -- and hold
 // for that index and for every batch planned until the next upload; ds2i_hip_set_option sets one without the environment.
 namespace {

@@ -3,7 +3,7 @@
 Mirrors reference test/test_block_codecs.cpp:9-46 (sizes {1,16,127,128} x magnitudes 1..24 x
 {sum unknown, sum given}: decode(encode(v)) == v and the decoder consumes exactly the encoded bytes),
 and pins vbyte / interpolative / QMX / posting-list layout to the reference's own bytes
-(tests/golden/appendix_c.json; oracle/_ref for QMX).
+(tests/golden/appendix_c.json; tests/golden/qmx_reference_codec.npz and, where built, oracle/_ref for QMX).
 """
 import json
 import os
@@ -68,21 +68,35 @@ def test_golden_appendix_c(built_lib):
     assert d.encode_posting_list(pl["codec"], pl["docs"], pl["freqs"]).hex() == pl["hex"]
 
 
+def _ref_codec_gold():
+    """tests/golden/qmx_reference_codec.npz (make_qmx_codec_golden.py): byte streams of the reference's own QMX encoder."""
+    g = np.load(os.path.join(os.path.dirname(GOLD), "qmx_reference_codec.npz"))
+    split = lambda enc, off: [bytes(enc[off[i]:off[i + 1]]) for i in range(len(off) - 1)]
+    return g["values"], split(g["enc"], g["enc_off"]), dict(zip(g["appendix_names"].tolist(), split(g["appendix_enc"], g["appendix_off"])))
+
+
+def _ref_qmx_encode(R, v):
+    buf = np.zeros(8192, dtype=np.uint8)
+    ln = R.ref_qmx_encode(buf.ctypes.data, v.ctypes.data)
+    return bytes(buf[:ln])
+
+
 def test_golden_appendix_c_qmx_rows_live(built_lib):
-    """The QMX rows of appendix_c.json regenerated from the reference's own encoder (oracle/_ref): the only rows of that
-    fixture whose provenance is reproducible here (the others are survey-session values, see its _provenance)."""
+    """The QMX rows of appendix_c.json against the reference's own encoder: the only rows of that fixture whose provenance
+    is reproducible (the others are survey-session values, see its _provenance). The encoder's bytes are stored in
+    qmx_reference_codec.npz; where oracle/_ref was built the live encoder must write them too."""
     R = o.ref_qmx()
-    if R is None:
-        pytest.skip("oracle/_ref/libqmx_ref.so not built (needs /root/reference at build time)")
+    _, _, stored = _ref_codec_gold()
     g = json.load(open(GOLD))
     n = 0
     for case in g["blocks"]:
         if case["codec"] != "block_qmx" or len(case["values"]) != 128:
             continue
         v = np.ascontiguousarray(case["values"], dtype=np.uint32)
-        buf = np.zeros(8192, dtype=np.uint8)
-        ln = R.ref_qmx_encode(buf.ctypes.data, v.ctypes.data)
-        live = (d.encode_vbyte(ln) + bytes(buf[:ln])).hex()
+        ref = stored[case["name"]]
+        if R is not None:
+            assert _ref_qmx_encode(R, v) == ref, case["name"]
+        live = (d.encode_vbyte(len(ref)) + ref).hex()
         if "hex" in case:
             assert live == case["hex"], case["name"]
         if "len" in case:
@@ -90,37 +104,31 @@ def test_golden_appendix_c_qmx_rows_live(built_lib):
         if "prefix" in case:
             assert live.startswith(case["prefix"]) and live.endswith(case["suffix"]), case["name"]
         n += 1
-    assert n >= 3
+    assert n >= 3 and n == len(stored)
 
 
 def test_qmx_against_reference_codec(built_lib):
-    """oracle/_ref = the reference's qmx_codec.hpp compiled as-is: encoder bytes and decoder output must agree."""
+    """The reference's qmx_codec.hpp: encoder bytes and decoder output must agree with the product encoder and the oracle
+    decoder over 600 seeded blocks of 0..32 bits. The reference encoder's bytes are stored in qmx_reference_codec.npz;
+    where oracle/_ref was built (the header compiled as-is) its live encoder and decoder are checked as well."""
     R = o.ref_qmx()
-    if R is None:
-        pytest.skip("oracle/_ref/libqmx_ref.so not built (needs /root/reference at build time)")
-    rng = np.random.default_rng(7)
-    for it in range(600):
-        mag = int(rng.integers(0, 33))
-        kind = it % 4
-        if kind == 0:
-            v = rng.integers(0, 1 << mag, size=128, dtype=np.uint64)
-        elif kind == 1:
-            v = np.where(rng.random(128) < 0.9, rng.integers(0, 4, 128), rng.integers(0, 1 << mag, 128))
-        elif kind == 2:
-            v = np.repeat(rng.integers(0, 1 << mag, 32), 4) >> rng.integers(0, 8, 128)
-        else:
-            v = np.where(rng.random(128) < 0.7, 1, rng.integers(0, 1 << (mag // 2), 128))
+    values, encs, _ = _ref_codec_gold()
+    assert len(values) == len(encs) == 600
+    for v, ref in zip(values, encs):
         v = np.ascontiguousarray(v, dtype=np.uint32)
-        buf = np.zeros(8192, dtype=np.uint8)
-        ln = R.ref_qmx_encode(buf.ctypes.data, v.ctypes.data)
         mine = d.encode_block("block_qmx", v)
         val, vl = o.decode_vbyte(mine)
-        assert val == ln and mine[vl:] == bytes(buf[:ln])
-        ref_out = np.zeros(640, dtype=np.uint32)
+        assert val == len(ref) and mine[vl:] == ref
+        buf = np.zeros(8192, dtype=np.uint8)
+        buf[:len(ref)] = np.frombuffer(ref, dtype=np.uint8)
         my_out = np.zeros(640, dtype=np.uint32)
-        R.ref_qmx_decode(ref_out.ctypes.data, buf.ctypes.data, ln)
-        o.lib().oracle_qmx_decode_stream(my_out.ctypes.data, buf.ctypes.data, ln)
-        assert np.array_equal(ref_out[:128], v) and np.array_equal(my_out[:128], v)
+        o.lib().oracle_qmx_decode_stream(my_out.ctypes.data, buf.ctypes.data, len(ref))
+        assert np.array_equal(my_out[:128], v)
+        if R is not None:
+            assert _ref_qmx_encode(R, v) == ref
+            ref_out = np.zeros(640, dtype=np.uint32)
+            R.ref_qmx_decode(ref_out.ctypes.data, buf.ctypes.data, len(ref))
+            assert np.array_equal(ref_out[:128], v)
 
 
 def test_qmx_golden_blocks_from_the_reference_encoder(built_lib):

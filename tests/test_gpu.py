@@ -1126,6 +1126,41 @@ def test_bench_contract(built_lib):
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0
 
 
+def test_bench_dump_outputs(built_lib, tmp_path):
+    """--dump-outputs DIR: the answer of the LAST timed step as the caller received it (count / topk / tlen, float64 / float32 /
+    float64; finite: 0 where the caller's top-k row holds -inf padding) -- the oracle's answer to that step's batch; two runs with
+    the same arguments write the same arrays; --steps is the number of timed steps and ms_per_step the time of one."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    steps, warmup, nq = 3, 1, 512
+    runs = []
+    for i in range(2):
+        dump = tmp_path / ("run%d" % i)
+        j = _run_bench(["--workload", "c2", "--steps", str(steps), "--warmup", str(warmup), "--batch", str(nq), "--no-oracle",
+                        "--dump-outputs", str(dump)])
+        assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0
+        assert sorted(os.listdir(dump)) == ["count.npy", "tlen.npy", "topk.npy"]
+        runs.append({n: np.load(dump / (n + ".npy")) for n in ("count", "topk", "tlen")})
+    a, b = runs
+    assert a["count"].dtype == np.float64 and a["topk"].dtype == np.float32 and a["tlen"].dtype == np.float64
+    assert a["count"].shape == (nq,) and a["topk"].shape == (nq, 10) and a["tlen"].shape == (nq,)
+    for n in a:
+        assert np.array_equal(a[n], b[n]), n
+    W = bench.WORKLOADS["c2"]
+    p = d.SynthParams(seed=W["seed"], num_docs=W["num_docs"], num_terms=W["num_terms"], zipf_exp=W["zipf_exp"],
+                      top_df_frac=W["top_df_frac"], min_len=W["min_len"], clustered_every=W["clustered_every"])
+    img, wand, _ = d.synth_build(p, "block_optpfor")
+    last = d.synth_queries(0x51E21 + 7919 * (warmup + steps - 1), p.num_terms, nq)  # bench.py's seed of its last timed batch
+    oc, otopk, otlen, _, _ = o.Index("block_optpfor", img, wand).query_batch("ranked_and", last, k=10)
+    assert np.array_equal(a["count"], oc) and np.array_equal(a["tlen"], otlen) and (otlen > 0).any()
+    assert np.isfinite(a["topk"]).all()
+    f = np.isfinite(otopk)
+    assert np.array_equal(f, np.arange(10)[None, :] < otlen[:, None].astype(np.int64))
+    np.testing.assert_allclose(a["topk"][f], otopk[f], rtol=1e-5)
+    assert not a["topk"][~f].any()
+
+
 def _run_bench(extra, nproc=1, env_extra=None, timeout=900):
     import json
     import os
