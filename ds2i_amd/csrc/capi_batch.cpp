@@ -179,6 +179,10 @@ struct ds2i_hip_batch {
     std::vector<uint32_t> keep_terms, keep_offs;
     int keep_want_matches = 0;
     bool no_list_streams = false;
+    // ... and at k > 64 without the k-wide stream kernels (k_ranked_stream / k_union_stream with TopKBig): a profiled run launches the class
+    // kernels for stream groups, and those hold DS2I_HIP_MAX_K scores -- the queries go to k_daat_long, which counts its decodes
+    bool no_bigk_streams = false;
+    bool profiled_run = false; // the last launch counted block decodes: its stream groups ran the class kernels (class_groups reports that)
     bool union_stream = false;
     bool union_rstream = false;   // ... and some class of it runs k_union_stream (union_stream.hip): unit records + the floor words
     // or_freq on a block_optpfor index with the side tables: the union's size by the `or` kernels, the freqs -- which do not
@@ -283,10 +287,10 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
     const bool bigk = ranked && k > DS2I_HIP_MAX_K;
     // ... except ranked_and on block_optpfor with every table: k_ranked_stream is compiled with 4 / 16 scores per lane too, and those
     // instantiations also take the one-term queries -- every query of 1 .. DS2I_STREAM_NT_MAX terms stays on the pruned stream path
-    const bool bigk_stream = bigk && base_op == DS2I_OP_RANKED_AND && !(op & DS2I_OP_REFERENCE_ORDER) && idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots &&
+    const bool bigk_stream = bigk && !b->no_bigk_streams && base_op == DS2I_OP_RANKED_AND && !(op & DS2I_OP_REFERENCE_ORDER) && idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots &&
                              idx->d_tails && idx->d_skip && idx->d_bmw && idx->d_rmw && !kn.no_ranked_stream && kn.stream_nt_max >= 4;
     // ... and wand / maxscore / ranked_or there (k_union_stream with the same heaps; their one-term queries are answered by the ranked_and seed pass)
-    bool bigk_union = bigk && (base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR) && !(op & DS2I_OP_REFERENCE_ORDER) &&
+    bool bigk_union = bigk && !b->no_bigk_streams && (base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR) && !(op & DS2I_OP_REFERENCE_ORDER) &&
                             idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && idx->d_tails && idx->d_skip && idx->d_bmw && idx->d_rmw && !kn.no_union_rstream &&
                             !kn.no_ranked_stream && kn.stream_nt_max >= 4;
     auto goes_long = [&](size_t nterms) {
@@ -926,6 +930,7 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
             b->seed->idx = idx;
         }
         b->seed->pool_batches = b->pool_batches;
+        b->seed->no_bigk_streams = b->no_bigk_streams;
         int rc = plan_batch(b->seed, DS2I_OP_RANKED_AND, k, sterms.data(), soffs.data(), nq, 0);
         if (rc) return rc;
     }
@@ -997,6 +1002,15 @@ int upload_batch(ds2i_hip_batch* b) {
 int launch_batch(ds2i_hip_batch* b) {
     ds2i_hip_index* idx = b->idx;
     if (!b->uploaded) return ds2i_set_error(DS2I_EINVAL, "batch has not been prepared");
+    // a counting run launches the class kernel (ds2i_launch_batch) for a stream group, and the class kernels keep DS2I_HIP_MAX_K scores:
+    // at a larger k the rows would come back half written. enable_block_profile plans such batches without the k-wide streams
+    // (no_bigk_streams); anything else that reaches here is refused before a kernel is enqueued
+    const bool counting = b->instrument && b->profile_on;
+    if (counting && b->k > DS2I_HIP_MAX_K)
+        for (int c = 0; c < NCLS; ++c)
+            for (const auto& sl : b->sub[c])
+                if (b->ncls[c] && sl.stream)
+                    return ds2i_set_error(DS2I_EINVAL, "block profile at k > DS2I_HIP_MAX_K: a stream launch group would run a class kernel that keeps DS2I_HIP_MAX_K scores");
     if (b->use_seed) { // block-synchronous ranked_and first: its k-th score seeds the pruning floor of every unit
         b->seed->instrument = b->instrument;
         b->seed->profile_on = b->profile_on;
@@ -1005,6 +1019,7 @@ int launch_batch(ds2i_hip_batch* b) {
         int rc = launch_batch(b->seed);
         if (rc) return rc;
     }
+    b->profiled_run = counting;
     // per-unit partials, shared floors, result block and counters start from zero. The clears go to the upload
     // stream: they depend on nothing but the slot being free, so the class kernels of this batch can start while the
     // previous batch is still being merged
@@ -1424,10 +1439,12 @@ int ds2i_hip_batch_enable_block_profile(ds2i_hip_batch* b) {
     const size_t bytes = 8 * (size_t)(idx->total_blocks ? idx->total_blocks : 1);
     HIP_OK(b->d_prof.reserve(bytes));
     HIP_OK(hipMemset(b->d_prof.p, 0, bytes));
-    if ((!b->sterms.empty() || b->freq_stream) && !b->keep_offs.empty()) {
+    if ((!b->sterms.empty() || b->freq_stream || b->k > DS2I_HIP_MAX_K) && !b->keep_offs.empty()) {
         // queries answered by list streams have no work units and their kernels count nothing: plan the batch again without them, so
-        // that every block decode of the batch shows in the profile (the input of the block_mixed optimiser)
+        // that every block decode of the batch shows in the profile (the input of the block_mixed optimiser). At k > 64 the stream
+        // groups cannot fall back to the class kernels (launch_batch): those queries go to k_daat_long, the seed pass with them
         b->no_list_streams = true;
+        b->no_bigk_streams = true;
         HIP_OK(hipDeviceSynchronize());
         int rc = plan_batch(b, b->op, b->k, b->keep_terms.empty() ? nullptr : b->keep_terms.data(), b->keep_offs.data(), b->nq, b->keep_want_matches);
         if (!rc) rc = upload_batch(b);
@@ -1481,7 +1498,7 @@ int ds2i_hip_batch_class_groups(ds2i_hip_batch* b, int cls, ds2i_hip_group_stats
         out[g].kernel_ms = g < b->grp_ms[cls].size() ? b->grp_ms[cls][g] : 0.0;
         out[g].lists = sl.lists;
         out[g].units = sl.end - sl.begin;
-        out[g].pipelined_stream = sl.stream ? 1 : 0;
+        out[g].pipelined_stream = (sl.stream && !b->profiled_run) ? 1 : 0;
         uint32_t nq = 0, last = 0xFFFFFFFFu; // distinct queries of the group (its units are grouped by query only loosely: count by marking)
         std::vector<char> seen(b->nq ? b->nq : 1, 0);
         for (uint32_t i = sl.begin; i < sl.end; ++i) {

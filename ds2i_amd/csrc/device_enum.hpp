@@ -406,7 +406,10 @@ struct CtxT {
         }
         wave_sync();
         ++s_docs_blocks;
-        if (STATS && block_profile && lane == 0) atomicAdd(block_profile + 2ull * (m(s, M_PBASE) + b), 1u);
+        if (STATS && block_profile && lane == 0) {
+            atomicAdd(block_profile + 2ull * (m(s, M_PBASE) + b), 1u);
+            if (freqs_too) atomicAdd(block_profile + 2ull * (m(s, M_PBASE) + b) + 1, 1u); // (freqs decoded together with the docs: s_freqs_blocks counted them above)
+        }
         s_bytes += 4 + consumed; // endpoint + docs part
         PT_END(*this, PH_DOCS);
     }

@@ -19,6 +19,24 @@ class Collection:
         self.num_docs = int(p.num_docs)
         self.lists = [d.synth_list(p, t) for t in range(p.num_terms)]
         self.sizes = d.synth_doc_sizes(p)
+        self._norm_lens()
+
+    @classmethod
+    def from_lists(cls, num_docs, lists, sizes):
+        """A collection of explicit posting lists [(docs, freqs)] and per-document sizes (no synthetic parameters: p is None)."""
+        self = cls.__new__(cls)
+        self.p = None
+        self.num_docs = int(num_docs)
+        self.lists = [(np.asarray(dd, dtype=np.uint32), np.asarray(ff, dtype=np.uint32)) for dd, ff in lists]
+        self.sizes = np.asarray(sizes, dtype=np.uint32)
+        assert len(self.sizes) == self.num_docs
+        for dd, ff in self.lists:
+            assert len(dd) == len(ff) and len(dd) > 0 and np.all(np.diff(dd.astype(np.int64)) > 0) and int(dd[-1]) < self.num_docs
+            assert np.all(ff > 0)
+        self._norm_lens()
+        return self
+
+    def _norm_lens(self):
         lens = self.sizes.astype(np.float32)
         avg = np.float32(lens.astype(np.float64).sum() / float(self.num_docs))
         self.norm_lens = (lens / avg).astype(np.float32)
@@ -145,3 +163,86 @@ def mixed_block_type_counts(image, oracle_mod, max_blocks=20000):
             visited += 1
     assert visited > 0
     return counts
+
+
+def topk64(coll, terms, k, conjunctive):
+    """float64 top-k BM25 of the AND (conjunctive) / OR result set of `terms`, from the raw lists and document sizes alone --
+    nothing of oracle/ and none of the float32 helpers above: k1 = 1.2, b = 0.5, idf floored at 1e-6, a repeated term
+    weighted by its query frequency, norm_len = size / average size. Returns (scores descending, float64[min(k, n)], n = the
+    size of the result set)."""
+    k1, b = 1.2, 0.5
+    qtf = {}
+    for t in terms:
+        qtf[int(t)] = qtf.get(int(t), 0) + 1
+    if not qtf:
+        return np.zeros(0), 0
+    n_docs = coll.num_docs
+    sizes = coll.sizes.astype(np.float64)
+    norm = sizes / (sizes.sum() / n_docs)
+    score = np.zeros(n_docs)
+    hits = np.zeros(n_docs, dtype=np.int64)
+    for t, f in qtf.items():
+        docs, freqs = coll.lists[t]
+        docs = docs.astype(np.int64)
+        df = float(len(docs))
+        # (the one step where float32 and float64 part by more than 1e-5: a list of about half the documents has a ratio near 1,
+        # whose float32 rounding alone moves the idf by up to 1e-5 relative -- the ratio is rounded as the scoring rounds it)
+        idf = max(1e-6, np.log(float(np.float32((n_docs - df + 0.5) / (df + 0.5)))))
+        tf = freqs.astype(np.float64)
+        score[docs] += f * idf * (1.0 + k1) * tf / (tf + k1 * (1.0 - b + b * norm[docs]))
+        hits[docs] += 1
+    member = hits == len(qtf) if conjunctive else hits > 0
+    s = np.sort(score[member])[::-1]
+    return s[:k], len(s)
+
+
+# ---------------------------------------------------------------- a crafted collection whose result-set sizes are known exactly
+BOUNDARY_SIZES = (1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025, 3000)
+
+
+def boundary_collection(num_docs=5000, seed=0xB0DA):
+    """Term 0 holds every document (freq 1); term 1 + i the first BOUNDARY_SIZES[i] documents of one fixed order that starts
+    with doc 0 and doc num_docs - 1, so these lists are nested: an AND of several is the shortest, an OR the longest, and every
+    size of BOUNDARY_SIZES (block edges 127 / 128 / 129 / 256 among them) is the result size of some query. Two strided lists
+    have random freqs. The last term is a group of 300 documents of equal size, all with freq 3: its one-term query, and its
+    AND with term 0, tie across every k-th place. (No list holds close to half the documents: an idf near 0 is
+    ill-conditioned in float32.)"""
+    rng = np.random.default_rng(seed)
+    n = num_docs
+    order = np.concatenate([[0, n - 1], 1 + rng.permutation(n - 2)]).astype(np.int64)
+    tie = np.sort(rng.choice(n, 300, replace=False))
+    sizes = rng.integers(20, 400, n).astype(np.uint32)
+    sizes[tie] = 150
+    lists = [(np.arange(n), np.ones(n, dtype=np.uint32))]
+    for m in BOUNDARY_SIZES:
+        lists.append((np.sort(order[:m]), rng.integers(1, 12, m).astype(np.uint32)))
+    for stride in (3, 7):
+        docs = np.arange(stride // 2, n, stride)
+        lists.append((docs, rng.integers(1, 30, len(docs)).astype(np.uint32)))
+    lists.append((tie, np.full(len(tie), 3, dtype=np.uint32)))
+    return Collection.from_lists(n, lists, sizes)
+
+
+def boundary_queries(coll):
+    """Empty, every term alone, duplicated terms, [all, list of size m] (AND = m, OR = num_docs), neighbouring nested lists (AND =
+    the smaller size, OR = the larger: every size is an OR size too), every length 2 .. 16 and two queries of more than 16 terms."""
+    T = len(coll.lists)
+    pre = list(range(1, 1 + len(BOUNDARY_SIZES)))
+    tie = T - 1
+    nested = [0] + pre[::-1] + [T - 3]                   # (16 lists: all, 3000, 1025, ..., 1, the stride-3 list)
+    qs = [[]] + [[t] for t in range(T)] + [[5, 5], [tie, tie], [0, 0, pre[4]]]
+    qs += [[0, t] for t in pre] + [[0, tie], [tie, pre[-1]], [tie, pre[-2], pre[-2]]]
+    qs += [[pre[i], pre[i + 1]] for i in range(len(pre) - 1)] + [[pre[0], pre[-1]], [pre[-1], pre[3]]]
+    qs += [nested[:L] for L in range(2, 17)]              # AND = the (L-1)-th largest size, OR = num_docs
+    qs += [pre[i:i + L] for L in (3, 5, 9, 14) for i in (0, len(pre) - L)]
+    qs += [list(range(T)), list(range(T)) + [tie, 2]]     # > 16 terms
+    return qs
+
+
+def edge_queries(num_terms):
+    """the edge shapes for a synthetic collection: empty, one term, duplicates, every length 2 .. 16, one beyond 16 terms"""
+    T = num_terms
+    qs = [[], [5], [T - 1], [5, 5], [7, 3, 7, 3], [0, 0, 1]]
+    qs += [[(11 * j + L) % T for j in range(L)] for L in range(2, 17)]
+    qs.append(list(range(0, 40, 2)))
+    return qs

@@ -1001,22 +1001,45 @@ def test_block_profile_and_hybrid_optimiser(coll, queries, images):
     fixed-policy index's at the same size."""
     codec = "block_mixed"
     gidx = d.Index(codec, images[0][codec], images[1])
+    oidx = o.Index(codec, images[0][codec], images[1])
+
+    def answers_equal_oracle(batch, op, k):  # (the profiled runs take other kernels than the default ones: their answers, too)
+        _, topk, tlen, _ = batch.fetch()
+        _, otopk, otlen, _, _ = oidx.query_batch(op, queries, k=k)
+        assert np.array_equal(tlen, otlen), (op, k)
+        f = np.isfinite(otopk)
+        assert np.array_equal(np.isfinite(topk), f), (op, k)
+        np.testing.assert_allclose(topk[f], otopk[f], rtol=RTOL, err_msg=str((op, k)))
+
     b = d.Batch(gidx, "ranked_and", queries, k=10)
     b.enable_block_profile()
     st = b.run()
+    answers_equal_oracle(b, "ranked_and", 10)
     prof = b.block_profile()
     nb_all = sum((len(dd) + 127) // 128 for dd, _ in coll.lists)
     assert prof.shape == (nb_all, 2)
     assert int(prof[:, 0].sum()) == st.docs_blocks_decoded and int(prof[:, 1].sum()) == st.freqs_blocks_decoded
     st2 = b.run()  # accumulates (a second run may decode a few blocks more or fewer: the parts of a split query race for their shared floor)
+    answers_equal_oracle(b, "ranked_and", 10)
     assert int(b.block_profile()[:, 0].sum()) == st.docs_blocks_decoded + st2.docs_blocks_decoded
     b.close()
     # wand profile includes its ranked_and seed pass
     bw = d.Batch(gidx, "wand", queries, k=10)
     bw.enable_block_profile()
     bw.run()
+    answers_equal_oracle(bw, "wand", 10)
     assert int(bw.block_profile().sum()) > 0
     bw.close()
+    # k > 64: the profile re-plans the batch onto the kernels that count (k_daat_long), whose heaps hold k scores
+    for op in ("ranked_and", "wand"):
+        bk = d.Batch(gidx, op, queries, k=200)
+        bk.run()
+        bk.enable_block_profile()
+        stk = bk.run()
+        answers_equal_oracle(bk, op, 200)
+        pk = bk.block_profile()
+        assert (int(pk[:, 0].sum()), int(pk[:, 1].sum())) == (stk.docs_blocks_decoded, stk.freqs_blocks_decoded), op
+        bk.close()
 
     hb = d.HybridBuilder(coll.num_docs)
     base = 0
