@@ -375,7 +375,7 @@ def synth_doc_sizes(p):
 
 
 def set_option(name, value):
-    """a DS2I_* tuning knob without the environment (ds2i_hip_set_option): before the first batch is planned"""
+    """a DS2I_* tuning knob without the environment (ds2i_hip_set_option): read by the uploads after it (each index keeps its own)"""
     _check(lib().ds2i_hip_set_option(name.encode(), None if value is None else str(value).encode()))
 
 

@@ -171,7 +171,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
     auto without_tables = [&](const char* why, uint64_t want) -> int {
         x->list_rmw_off64.clear();
         x->list_rmw_shift.clear();
-        if (ds2i_knobs().rmw_require) {
+        if (x->knobs.rmw_require) {
             char msg[256];
             std::snprintf(msg, sizeof msg, "doc-id-range tables (%.2f GB) cannot be built: %s (DS2I_RMW_REQUIRE is set)", want / 1e9, why);
             return ds2i_set_error(DS2I_ENOMEM, msg);
@@ -189,7 +189,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
         x->list_rmw_shift[t] = sh;
         x->list_rmw_off64[t] = (uint32_t)cursor;
         cursor += ds2i_dev::RmwLevels((uint32_t)x->num_docs, sh).bytes() / 64; // level 1 + its two coarser levels
-        if (ds2i_dev::RmwLevels::has_bitmap(x->list_n[t], (uint32_t)x->num_docs) && !ds2i_knobs().no_bitmaps)
+        if (ds2i_dev::RmwLevels::has_bitmap(x->list_n[t], (uint32_t)x->num_docs) && !x->knobs.no_bitmaps)
             cursor += ds2i_dev::RmwLevels::bitmap_bytes((uint32_t)x->num_docs) / 64; // dense list: + its exact bitmap
         if (cursor >= (1ull << 32)) return without_tables("more than 256 GB of tables", cursor * 64);
     }
@@ -233,7 +233,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
     a.rmw = x->d_rmw;
     a.rmh = x->d_rmh;
     a.rmw_level = 0;
-    a.bitmaps = ds2i_knobs().no_bitmaps ? 0u : 1u;
+    a.bitmaps = x->knobs.no_bitmaps ? 0u : 1u;
     x->has_bitmaps = a.bitmaps != 0;
     HIP_OK(ds2i_launch_block_max_weights(&a, grid, x->stream[0]));
     for (uint32_t lvl = 1; lvl <= 2; ++lvl) { // level lvl + 1 = maxima of 64 entries of level lvl, 4096 entries per item
@@ -259,7 +259,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
 // Bytes of the doc-id-range tables (levels + dense lists' bitmaps) at G entries per posting; the hints are a buffer of the same size.
 static uint64_t range_table_bytes_at(const ds2i_hip_index* x, double G) {
     uint64_t cursor = 0;
-    const bool bitmaps = !ds2i_knobs().no_bitmaps;
+    const bool bitmaps = !x->knobs.no_bitmaps;
     for (uint64_t t = 0; t < x->size; ++t) {
         uint32_t sh = 0;
         while (sh < 31 && (double)(x->num_docs >> (sh + 1)) >= G * (double)x->list_n[t]) ++sh;
@@ -277,8 +277,7 @@ static uint64_t range_table_bytes_at(const ds2i_hip_index* x, double G) {
 // A knob set explicitly (DS2I_RMW_G, DS2I_NO_RMH, DS2I_NO_XSLOTS) is not overridden. Reported by ds2i_hip_index_get_info.
 // DS2I_TABLE_BUDGET in bytes ("<bytes>" or "<factor>x" of the CALLER's image -- for a transcoded upload the image handed to
 // ds2i_hip_index_open, not its re-encoded form), 0 = none
-static uint64_t table_budget_bytes(size_t image_bytes) {
-    const Ds2iKnobs kn = ds2i_knobs();
+static uint64_t table_budget_bytes(const Ds2iKnobs& kn, size_t image_bytes) {
     const char* eb = kn.table_budget;
     if (!*eb) return 0;
     char* end = nullptr;
@@ -287,12 +286,12 @@ static uint64_t table_budget_bytes(size_t image_bytes) {
     return (end && (*end == 'x' || *end == 'X')) ? (uint64_t)(v * (double)image_bytes) : (uint64_t)v;
 }
 static void choose_table_plan(ds2i_hip_index* x, size_t image_bytes) {
-    const Ds2iKnobs kn = ds2i_knobs();
+    const Ds2iKnobs& kn = x->knobs;
     x->plan_g = kn.rmw_g;
     if (!(x->plan_g > 0) || kn.no_rmw) x->plan_g = 0;
     x->plan_hints = !kn.no_rmh;
     x->plan_slots = !kn.no_xslots && x->kind == DS2I_BLOCK_OPTPFOR;
-    x->table_budget = table_budget_bytes(image_bytes);
+    x->table_budget = table_budget_bytes(kn, image_bytes);
     if (!x->table_budget) return;
     const bool g_pinned = kn.rmw_g_set || kn.no_rmw; // (an explicit knob pins the granularity: DS2I_NO_RMW = none)
     // resident whatever is chosen: the image and its skip table (counted in extra_bytes by now), block weights (4 B per block), norm_lens
@@ -420,20 +419,16 @@ int build_side_tables(ds2i_hip_index* x) {
 
 } // namespace
 
-extern "C" {
-
-const char* ds2i_hip_last_error(void) { return ds2i_get_error(); }
-
-// The knobs (knobs.hpp) are read from the environment by every ds2i_hip_index_open -- the one place the library reads it -- and hold
-// for that index and for every batch planned until the next upload; ds2i_hip_set_option sets one without the environment.
+// The knobs (knobs.hpp) are read from the environment by every ds2i_hip_index_open -- the one place the library reads it -- into the
+// index, and hold for that index and every batch planned on it; ds2i_hip_set_option sets one without the environment.
 namespace {
 const char* const kKnobs[] = {"DS2I_RMW_G", "DS2I_NO_RMW", "DS2I_NO_RMH", "DS2I_NO_BITMAPS", "DS2I_NO_BMW", "DS2I_NO_XSLOTS", "DS2I_RMW_REQUIRE", "DS2I_MIXED_NATIVE",
                               "DS2I_PEF_NATIVE", "DS2I_TABLE_BUDGET", "DS2I_PLAN_THREADS", "DS2I_UNIT_FACTOR", "DS2I_UNIT_CAP", "DS2I_UT_BLOCKS", "DS2I_STREAM_NT_MAX",
                               "DS2I_NO_RANKED_STREAM", "DS2I_NO_UNION_RSTREAM", "DS2I_NO_LIST_STREAMS", "DS2I_DECODE_GENERAL", "DS2I_UNIT_CLOCK"};
-Ds2iKnobs g_knobs{};
-std::mutex g_knobs_mu;
-bool g_knobs_loaded = false;
-void load_knobs_locked() {
+std::mutex g_knobs_mu; // (setenv / unsetenv against getenv on another thread)
+
+Ds2iKnobs ds2i_knobs() {
+    std::lock_guard<std::mutex> lk(g_knobs_mu);
     auto env = [](const char* n) -> const char* { return std::getenv(n); }; // (the one place the library reads its knobs)
     auto on = [&](const char* n) { return env(n) != nullptr; };
     auto num = [&](const char* n, double dflt) { const char* e = env(n); return e && std::atof(e) > 0 ? std::atof(e) : dflt; };
@@ -459,20 +454,13 @@ void load_knobs_locked() {
     v.no_list_streams = on("DS2I_NO_LIST_STREAMS");
     v.decode_general = on("DS2I_DECODE_GENERAL");
     v.unit_clock = on("DS2I_UNIT_CLOCK");
-    g_knobs = v;
-    g_knobs_loaded = true;
+    return v;
 }
-}
+} // namespace
 
-extern "C++" Ds2iKnobs ds2i_knobs() {
-    std::lock_guard<std::mutex> lk(g_knobs_mu);
-    if (!g_knobs_loaded) load_knobs_locked();
-    return g_knobs;
-}
-static void ds2i_reload_knobs() {
-    std::lock_guard<std::mutex> lk(g_knobs_mu);
-    load_knobs_locked();
-}
+extern "C" {
+
+const char* ds2i_hip_last_error(void) { return ds2i_get_error(); }
 
 int ds2i_hip_set_option(const char* name, const char* value) {
     if (!name || std::strncmp(name, "DS2I_", 5) != 0 || std::strlen(name) > 48) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_set_option: not a DS2I_* knob");
@@ -481,6 +469,7 @@ int ds2i_hip_set_option(const char* name, const char* value) {
     bool known = false;
     for (const char* k : kKnobs) known = known || std::strcmp(k, name) == 0;
     if (!known) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_set_option: unknown knob (DESIGN.md 7 lists them)");
+    std::lock_guard<std::mutex> lk(g_knobs_mu);
     if (value) setenv(name, value, 1); else unsetenv(name);
     return DS2I_OK;
 }
@@ -492,7 +481,7 @@ int ds2i_hip_device_count(void) {
 }
 
 static int index_open_impl(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, bool bare,
-                           ds2i_hip_index** out, size_t budget_base_bytes = 0);
+                           const Ds2iKnobs& kn, ds2i_hip_index** out, size_t budget_base_bytes = 0);
 
 // block_mixed, the default upload: the image is TRANSCODED to the block codec this device decodes fastest. The mixed
 // image is uploaded bare (no tables), every list decoded by the mixed-block kernels (mixed_block.hpp:198-217: OptPFor /
@@ -508,9 +497,10 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
 // (it is what the decode pass walks), every list decoded by the partitioned-sequence kernels (partitioned_sequence.hpp:198-326,
 // compact_elias_fano.hpp:184-214, compact_ranked_bitvector.hpp, positive / strict sequences), and the postings re-encoded as
 // above. DS2I_PEF_NATIVE=1 keeps the bit vectors and runs the CODEC_PEF kernels over the chunk directory.
-static int index_open_transcoded(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, ds2i_hip_index** out) {
+static int index_open_transcoded(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes,
+                                 const Ds2iKnobs& kn, ds2i_hip_index** out) {
     ds2i_hip_index* raw = nullptr;
-    int rc = index_open_impl(device, kind, index_image, index_bytes, nullptr, 0, true, &raw);
+    int rc = index_open_impl(device, kind, index_image, index_bytes, nullptr, 0, true, kn, &raw);
     if (rc) return rc;
     std::unique_ptr<ds2i_hip_index, void (*)(ds2i_hip_index*)> guard(raw, free_index);
     const uint64_t V = raw->size;
@@ -527,9 +517,9 @@ static int index_open_transcoded(int device, int kind, const void* index_image, 
     auto native = [&](const char* why) {
         std::fprintf(stderr, "ds2i_hip: %s: the %s image is uploaded as it is (native kernels)\n", why, kind == DS2I_BLOCK_MIXED ? "block_mixed" : "freq_index");
         guard.reset();
-        return index_open_impl(device, kind, index_image, index_bytes, wand_image, wand_bytes, false, out);
+        return index_open_impl(device, kind, index_image, index_bytes, wand_image, wand_bytes, false, kn, out);
     };
-    const uint64_t budget = table_budget_bytes(index_bytes);
+    const uint64_t budget = table_budget_bytes(kn, index_bytes);
     const uint64_t least = 2 * offs[V] + (4ull * ds2i_dev::XSLOT_DW + 8 + 4) * ((offs[V] + 127) / 128) + 4 * raw->num_docs;
     if (budget && least > budget) return native("DS2I_TABLE_BUDGET is below what a transcoded index needs");
     std::vector<uint32_t> docs, freqs;
@@ -581,7 +571,7 @@ static int index_open_transcoded(int device, int kind, const void* index_image, 
     if (rc) return rc;
     std::vector<uint32_t>().swap(docs);
     std::vector<uint32_t>().swap(freqs);
-    rc = index_open_impl(device, DS2I_BLOCK_OPTPFOR, ds2i_blob_data(img), ds2i_blob_size(img), wand_image, wand_bytes, false, out, index_bytes);
+    rc = index_open_impl(device, DS2I_BLOCK_OPTPFOR, ds2i_blob_data(img), ds2i_blob_size(img), wand_image, wand_bytes, false, kn, out, index_bytes);
     ds2i_blob_free(img);
     if (rc == DS2I_OK) (*out)->kind_on_disk = kind;
     return rc;
@@ -592,17 +582,16 @@ int ds2i_hip_index_open(int device, int kind, const void* index_image, size_t in
     if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
     if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
     if (device < 0 || device >= ds2i_hip_device_count()) return ds2i_set_error(DS2I_EDEVICE, "ds2i_hip_index_open: no such HIP device");
-    ds2i_reload_knobs(); // (every upload re-reads the knobs: they hold for this index and the batches planned until the next upload)
-    const bool transcode = (kind == DS2I_BLOCK_MIXED && !ds2i_knobs().mixed_native) ||
-                           (kind >= DS2I_OPT && kind <= DS2I_UNIFORM && !ds2i_knobs().pef_native);
+    const Ds2iKnobs kn = ds2i_knobs(); // (every upload reads the knobs once: the index that serves the queries carries them)
+    const bool transcode = (kind == DS2I_BLOCK_MIXED && !kn.mixed_native) || (kind >= DS2I_OPT && kind <= DS2I_UNIFORM && !kn.pef_native);
     if (transcode) {
-        return index_open_transcoded(device, kind, index_image, index_bytes, wand_image, wand_bytes, out);
+        return index_open_transcoded(device, kind, index_image, index_bytes, wand_image, wand_bytes, kn, out);
     }
-    return index_open_impl(device, kind, index_image, index_bytes, wand_image, wand_bytes, false, out);
+    return index_open_impl(device, kind, index_image, index_bytes, wand_image, wand_bytes, false, kn, out);
 }
 
 static int index_open_impl(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, bool bare,
-                           ds2i_hip_index** out, size_t budget_base_bytes) {
+                           const Ds2iKnobs& kn, ds2i_hip_index** out, size_t budget_base_bytes) {
     if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
     if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM)
         return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
@@ -611,6 +600,7 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
     std::unique_ptr<ds2i_hip_index, void (*)(ds2i_hip_index*)> x(new ds2i_hip_index, free_index);
     x->device = device;
     x->kind = kind;
+    x->knobs = kn;
     const bool freq_layout = ds2i_host::is_freq_layout(kind); // opt / ef / single / uniform: freq_index images
     ds2i_host::block_index_view view;
     ds2i_host::opt_index_view oview;
@@ -793,7 +783,7 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
     HIP_OK(hipStreamCreateWithFlags(&x->s_merge, hipStreamNonBlocking));
     if (!bare) choose_table_plan(x.get(), budget_base_bytes ? budget_base_bytes : index_bytes);
     else x->plan_g = 0, x->plan_hints = x->plan_slots = false;
-    if (!bare && x->has_wand && x->total_blocks && x->total_blocks < (1ull << 32) && !ds2i_knobs().no_bmw) {
+    if (!bare && x->has_wand && x->total_blocks && x->total_blocks < (1ull << 32) && !kn.no_bmw) {
         int rc = build_block_max_weights(x.get());
         if (rc) return rc;
     }
@@ -877,7 +867,7 @@ int ds2i_hip_decode_list(ds2i_hip_index* idx, uint32_t term, uint32_t* docs, uin
     a.tails = idx->d_tails;
     unsigned grid = (unsigned)std::min<uint64_t>(nb, uint64_t(idx->num_cus) * 16);
     // block_optpfor with side tables: through the stream kernels' decoder (DS2I_DECODE_GENERAL=1: the general decoders)
-    const bool side = idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && !ds2i_knobs().decode_general;
+    const bool side = idx->side_tables() && !idx->knobs.decode_general;
     hipError_t e = side ? ds2i_launch_decode_list_side(&a, grid, idx->stream[0]) : ds2i_launch_decode_list(&a, grid, idx->stream[0]);
     if (e == hipSuccess) e = hipStreamSynchronize(idx->stream[0]);
     if (e == hipSuccess) e = hipMemcpy(docs, d_docs, 4 * len, hipMemcpyDeviceToHost);

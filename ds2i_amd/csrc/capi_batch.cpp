@@ -51,7 +51,7 @@ hipError_t ds2i_launch_copy_seed(const uint32_t* queries, uint32_t n, uint32_t k
 uint32_t ds2i_meta_words(void); // kernels.hip: dwords of enumerator state per list slot (M_WORDS)
 }
 
-// one contiguous range of a batch's queries, planned by one thread (plan_batch)
+// one contiguous range of a batch's queries, planned by one thread (plan_queries)
 struct PlanChunk {
     uint32_t q0 = 0, q1 = 0;
     std::vector<QTerm> qterms;
@@ -143,11 +143,51 @@ void ds2i_plan_pool_run(unsigned n, const std::function<void(unsigned)>& f) {
 }
 } // namespace
 
-// k_ranked_stream is compiled for the list capacities 2 | 4 | 6 | 8; the planner hands it the queries of 2 .. DS2I_STREAM_NT_MAX lists
-// (default 8; 4 = the 5..8-term class keeps k_conjunctive<.., 8>). Round 5, interleaved on one box: 1 047-1 060 k queries/s with 8
-// against 985-992 k with 4.
-static uint32_t rs_stream_nt_max() { return ds2i_knobs().stream_nt_max; }
-static int rs_stream_classes() { return rs_stream_nt_max() > 8 ? 4 : rs_stream_nt_max() > 4 ? 3 : 2; } // classes that get unit records (BatchArgs::urec)
+// The kernel a launch group runs (ds2i_hip_batch::SubLaunch), chosen when the plan forms the group (form_groups): the class kernel of the
+// operator (ds2i_launch_batch) or one of the stream kernels declared above (_bigk: their TopKBig instantiations, k > 64)
+enum class GroupKernel : uint8_t { cls, ranked_stream, ranked_stream_bigk, ranked_stream_mixed, and_rstream, union_stream, union_stream_bigk };
+
+// Which kernel families answer a batch: decided once per plan (plan_route), before any query is planned, from the index (its tables
+// and the knobs it was uploaded with), the operator, k and the batch's flags. Two steps that depend on the queries narrow it
+// (plan_queries): a query beyond 16 terms drops bigk_union, a query that goes long drops union_stream.
+struct Route {
+    int base_op = 0;
+    bool conj = false, ranked = false, reference = false;
+    // k > 64 (one score per lane no longer suffices): every query takes the one-document-per-step kernel with a 16-scores-
+    // per-lane heap and its enumerator state in global scratch -- slower, same results (the reference has no limit on k)
+    bool bigk = false;
+    // ... except ranked_and on block_optpfor with every table: k_ranked_stream is compiled with 4 / 16 scores per lane too, and those
+    // instantiations also take the one-term queries -- every query of 1 .. DS2I_STREAM_NT_MAX terms stays on the pruned stream path
+    bool bigk_stream = false;
+    // ... and wand / maxscore / ranked_or there (k_union_stream with the same heaps; their one-term queries are answered by the ranked_and seed pass)
+    bool bigk_union = false;
+    uint32_t stream_nt_max = 16;
+    // wand / maxscore / ranked_or: the streaming form (kernels.hip, k_union_topk) needs the range tables and the block weights;
+    // queries beyond 16 terms and k > 64 keep the one-document-per-step kernel, and the whole batch keeps the windowed
+    // kernel when any query does (one operator = one kernel family per batch)
+    bool union_stream = false;
+    bool us_ok = false; // ... and its classes <= 3 may take k_union_stream (union_stream.hip): unit records + the floor words
+    // (list_stream: what a stream over ONE list needs -- its blocks through the side slots; and_stream: the other lists' bitmaps as well)
+    bool list_stream = false, and_stream = false;
+    bool and_rs_units = false; // and / and_freq units sized for k_ranked_stream<.., AND> (cut_units: and_unit_blocks)
+    // or_freq on a block_optpfor index with the side tables: the union's size by the `or` kernels, the freqs -- which do not
+    // depend on the union -- by a stream of their own after the merge (freq_stream.hip)
+    bool freq_stream = false;
+    // ranked_and / and: the classes below rs_classes may take k_ranked_stream for their queries of 2 .. rs_nt lists
+    bool rs_ok = false;
+    uint32_t rs_nt = 0, rs_classes = 0;
+    bool exact = false; // ... one launch group per list count (block_mixed native) instead of one per list capacity
+    bool seeded = false; // a ranked_and seed pass runs first (plan_seed)
+    bool goes_long(size_t nterms) const {
+        if (!bigk) return nterms > DS2I_HIP_MAX_TERMS;
+        if (bigk_stream) return !(nterms >= 1 && nterms <= stream_nt_max);
+        if (bigk_union) return nterms > DS2I_HIP_MAX_TERMS; // (an empty query: the empty virtual query's unit, as for k <= 64)
+        return true;
+    }
+    bool union_rstream() const { return union_stream && us_ok; }
+    // classes that get unit records (BatchArgs::urec): the classes of k_ranked_stream / k_and_rstream / k_union_stream
+    int urec_classes() const { return union_stream ? (us_ok ? 4 : 0) : (rs_ok && !exact) ? (int)rs_classes : 0; }
+};
 
 struct ds2i_hip_batch {
     ds2i_hip_index* idx = nullptr;
@@ -162,11 +202,12 @@ struct ds2i_hip_batch {
     bool profile_on = false;          // block access profile requested (d_prof)
     unsigned int* prof_ptr = nullptr; // where instrumented runs count block decodes (the owner's d_prof; a seed borrows it)
     // ---- host plan (vectors keep their capacity between uses of the slot)
+    Route route;
     std::vector<QTerm> qterms;
     std::vector<uint32_t> qnbs, qoff, qnb0, scratch_u32;
     std::vector<double> qcost;
     std::vector<Unit> units;
-    std::vector<uint32_t> q_unit_off, split_queries, single_queries, hist_slot, order[NCLS];
+    std::vector<uint32_t> q_unit_off, split_queries, single_queries, hist_slot, cls_units[NCLS], order[NCLS];
     std::vector<float> unit_cost;
     std::vector<PlanChunk> plan_chunks;
     std::vector<unsigned long long> match_off;
@@ -182,12 +223,7 @@ struct ds2i_hip_batch {
     // ... and at k > 64 without the k-wide stream kernels (k_ranked_stream / k_union_stream with TopKBig): a profiled run launches the class
     // kernels for stream groups, and those hold DS2I_HIP_MAX_K scores -- the queries go to k_daat_long, which counts its decodes
     bool no_bigk_streams = false;
-    bool profiled_run = false; // the last launch counted block decodes: its stream groups ran the class kernels (class_groups reports that)
-    bool union_stream = false;
-    bool union_rstream = false;   // ... and some class of it runs k_union_stream (union_stream.hip): unit records + the floor words
-    // or_freq on a block_optpfor index with the side tables: the union's size by the `or` kernels, the freqs -- which do not
-    // depend on the union -- by a stream of their own after the merge (freq_stream.hip)
-    bool freq_stream = false;
+    bool profiled_run = false; // the last launch counted block decodes: its stream groups ran the class kernels (launched_kernel)
     // and / and_freq: the queries whose lists all carry their exact bitmap are answered by list streams (freq_stream.hip,
     // k_and_stream) and get no work units; sterms = one record per list that has to be read
     std::vector<ds2i_dev::StreamTerm> sterms;
@@ -206,7 +242,7 @@ struct ds2i_hip_batch {
     DevBuf d_up, d_out, d_scr, d_matches, d_prof, d_stats, d_long, d_clk;
     // union kernels (k_disjunctive) keep their decoded blocks in dynamic LDS sized per launch: a class's units are grouped
     // by the list count of their query and every group is launched with just that many list slots
-    struct SubLaunch { uint32_t begin, end, lists; bool stream = false; /* ranked_and: k_ranked_stream<lists> (ranked_stream.hip) */ };
+    struct SubLaunch { uint32_t begin, end, lists; GroupKernel kernel; };
     std::vector<SubLaunch> sub[NCLS];
     PinBuf h_up, h_out;
     hipEvent_t ev_up = nullptr, ev_clear = nullptr, ev_done = nullptr, ev_c0[NCLS] = {}, ev_c1[NCLS] = {};
@@ -216,7 +252,6 @@ struct ds2i_hip_batch {
     bool uploaded = false, launched = false;
     float cls_ms[NCLS] = {};
     Stats cls_stats[NCLS] = {};
-    double total_ms = 0;
 };
 
 namespace {
@@ -255,86 +290,84 @@ void order_by_cost(const std::vector<float>& cost, const std::vector<uint32_t>& 
 }
 
 // ---------------------------------------------------------------- plan: host half of the query operators
-static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq, int want_matches);
-// (the plan's vectors grow with the batch: an allocation failure -- on the caller's thread or on a pool thread, see PlanPool -- is
-// an error code at the C boundary, not an exception crossing it)
-int plan_batch(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq,
-               int want_matches) {
-    try {
-        return plan_batch_impl(b, op, k, terms, query_offsets, nq, want_matches);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory planning the batch");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EINVAL, e.what());
-    }
-}
-static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq,
-                           int want_matches) {
-    ds2i_hip_index* idx = b->idx;
-    const Ds2iKnobs kn = ds2i_knobs(); // (as the last upload read them: knobs.hpp)
-    const auto plan_t0 = std::chrono::steady_clock::now();
-    if (!query_offsets || (!terms && nq && query_offsets[nq] > 0))
-        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_prepare: null argument");
+// validate + route, per-query planning, work units, launch groups, layout, seed pass -- in that order (plan_batch, at the end)
+int plan_batch(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq, int want_matches);
+
+// the operator and k checked, the batch's header set, b->route decided
+static int plan_route(ds2i_hip_batch* b, int op, uint32_t k, uint32_t nq, int want_matches) {
+    const ds2i_hip_index* idx = b->idx;
+    const Ds2iKnobs& kn = idx->knobs;
     const int base_op = op & 0xFF;
     if (base_op < DS2I_OP_AND || base_op > DS2I_OP_RANKED_OR || (op & ~(0xFF | DS2I_OP_REFERENCE_ORDER | DS2I_OP_NO_COUNTERS)))
         return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_prepare: unknown query operator");
-    const bool conj = base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ || base_op == DS2I_OP_RANKED_AND;
-    const bool ranked = base_op >= DS2I_OP_RANKED_AND;
-    if (ranked && !idx->has_wand) return ds2i_set_error(DS2I_ENOWAND, "ranked operator needs wand data");
-    if (ranked && (k == 0 || k > DS2I_HIP_MAX_K_LONG)) return ds2i_set_error(DS2I_EINVAL, "k must be in [1, DS2I_HIP_MAX_K_LONG]");
-    // k > 64 (one score per lane no longer suffices): every query takes the one-document-per-step kernel with a 16-scores-
-    // per-lane heap and its enumerator state in global scratch -- slower, same results (the reference has no limit on k)
-    const bool bigk = ranked && k > DS2I_HIP_MAX_K;
-    // ... except ranked_and on block_optpfor with every table: k_ranked_stream is compiled with 4 / 16 scores per lane too, and those
-    // instantiations also take the one-term queries -- every query of 1 .. DS2I_STREAM_NT_MAX terms stays on the pruned stream path
-    const bool bigk_stream = bigk && !b->no_bigk_streams && base_op == DS2I_OP_RANKED_AND && !(op & DS2I_OP_REFERENCE_ORDER) && idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots &&
-                             idx->d_tails && idx->d_skip && idx->d_bmw && idx->d_rmw && !kn.no_ranked_stream && kn.stream_nt_max >= 4;
-    // ... and wand / maxscore / ranked_or there (k_union_stream with the same heaps; their one-term queries are answered by the ranked_and seed pass)
-    bool bigk_union = bigk && !b->no_bigk_streams && (base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR) && !(op & DS2I_OP_REFERENCE_ORDER) &&
-                            idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && idx->d_tails && idx->d_skip && idx->d_bmw && idx->d_rmw && !kn.no_union_rstream &&
-                            !kn.no_ranked_stream && kn.stream_nt_max >= 4;
-    auto goes_long = [&](size_t nterms) {
-        if (!bigk) return nterms > DS2I_HIP_MAX_TERMS;
-        if (bigk_stream) return !(nterms >= 1 && nterms <= kn.stream_nt_max);
-        if (bigk_union) return nterms > DS2I_HIP_MAX_TERMS; // (an empty query: the empty virtual query's unit, as for k <= 64)
-        return true;
-    };
-    if (!ranked) k = 1; // and / or return counts only: k is ignored, no top-k is produced or copied
-
+    Route r;
+    r.base_op = base_op;
+    r.conj = base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ || base_op == DS2I_OP_RANKED_AND;
+    r.ranked = base_op >= DS2I_OP_RANKED_AND;
+    r.reference = (op & DS2I_OP_REFERENCE_ORDER) != 0;
+    if (r.ranked && !idx->has_wand) return ds2i_set_error(DS2I_ENOWAND, "ranked operator needs wand data");
+    if (r.ranked && (k == 0 || k > DS2I_HIP_MAX_K_LONG)) return ds2i_set_error(DS2I_EINVAL, "k must be in [1, DS2I_HIP_MAX_K_LONG]");
+    if (!r.ranked) k = 1; // and / or return counts only: k is ignored, no top-k is produced or copied
     b->op = op;
     b->k = k;
     b->nq = nq;
     b->want_matches = want_matches && (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ);
     b->uploaded = b->launched = false;
 
-    auto& qterms = b->qterms;
-    auto& qnbs = b->qnbs;
-    auto& qoff = b->qoff;
-    auto& qcost = b->qcost;
-    auto& qnb0 = b->qnb0;
+    const bool and_op = base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ;
+    const bool disj_topk = base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR;
+    const bool stream_tables = idx->side_tables() && idx->bound_tables(); // what k_ranked_stream and k_union_stream read
+    r.bigk = r.ranked && k > DS2I_HIP_MAX_K;
+    const bool bigk_ok = r.bigk && !b->no_bigk_streams && !r.reference && stream_tables && !kn.no_ranked_stream && kn.stream_nt_max >= 4;
+    r.bigk_stream = bigk_ok && base_op == DS2I_OP_RANKED_AND;
+    r.bigk_union = bigk_ok && disj_topk && !kn.no_union_rstream;
+    r.stream_nt_max = kn.stream_nt_max;
+    // ranked_or takes the seed only in its block-synchronous form: its reference-order traversal stays the unpruned
+    // exhaustive OR of queries.hpp:404-476 (the oracle the reference tests wand / maxscore against)
+    r.seeded = (!r.bigk || r.bigk_union) && (base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || (base_op == DS2I_OP_RANKED_OR && !r.reference));
+    // (any codec: k_union_topk walks the driving list by its skip table or chunk directory; k_union_stream also decodes through the side tables)
+    r.union_stream = disj_topk && !r.reference && (!r.bigk || r.bigk_union) && idx->bound_tables() && idx->d_skip_or_pef();
+    r.us_ok = !kn.no_union_rstream && stream_tables;
+    r.list_stream = and_op && !r.reference && !b->want_matches && idx->side_tables() && !kn.no_list_streams && !b->no_list_streams;
+    r.and_stream = r.list_stream && idx->d_rmw && idx->has_bitmaps;
+    r.and_rs_units = and_op && !r.reference && stream_tables && !kn.no_ranked_stream;
+    r.freq_stream = base_op == DS2I_OP_OR_FREQ && !r.reference && idx->side_tables() && !kn.no_list_streams && !b->no_list_streams;
+    // ranked_and on block_optpfor with every upload-time table: the 2- .. 8-term queries (block_mixed native: 2 .. 4) run the pipelined stream
+    // kernel compiled for exactly their list count (ranked_stream.hip), one launch group per count, back to back on the
+    // class stream; one-term queries and everything else keep the class kernel
+    // (the 5..8-term class takes the stream kernel too, up to DS2I_STREAM_NT_MAX lists -- block_optpfor only)
+    // `and` batches that do not ask for the doc-id lists take the same pipeline with AND = true -- a candidate whose hints settle
+    // its membership in every other list is counted without any of them being searched or decoded (k_conjunctive<false, ...>
+    // verifies every survivor of its filters by a probe).
+    const bool rs_and = and_op && idx->kind == DS2I_BLOCK_OPTPFOR; // (with or without the doc-id lists)
+    // k_ranked_stream is compiled for the list capacities 2 | 4 | 6 | 8; the planner hands it the queries of 2 .. DS2I_STREAM_NT_MAX lists
+    // (default 8; 4 = the 5..8-term class keeps k_conjunctive<.., 8>). Round 5, interleaved on one box: 1 047-1 060 k queries/s with 8
+    // against 985-992 k with 4.
+    r.rs_nt = idx->kind == DS2I_BLOCK_OPTPFOR ? kn.stream_nt_max : 4u;
+    r.rs_classes = r.rs_nt > 8 ? 4u : r.rs_nt > 4 ? 3u : 2u;
+    r.exact = idx->kind != DS2I_BLOCK_OPTPFOR;
+    // (block_mixed native has no side slots: k_ranked_stream_mixed parses its blocks by type byte, over the skip table)
+    r.rs_ok = (base_op == DS2I_OP_RANKED_AND || rs_and) && !r.reference && (!r.bigk || r.bigk_stream) && !kn.no_ranked_stream &&
+              (idx->side_tables() || (idx->kind == DS2I_BLOCK_MIXED && idx->d_skip)) && idx->bound_tables();
+    b->route = r;
+    return DS2I_OK;
+}
+
+// The per-query half of planning for the queries [ch.q0, ch.q1) (normalisation, BM25 query weights, list order, costs, bounds): the
+// terms into the chunk's own vectors, the per-query values into the batch's arrays at those queries (plan_queries)
+static void plan_range(ds2i_hip_batch* b, const uint32_t* terms, const uint32_t* query_offsets, PlanChunk& ch) {
+    const ds2i_hip_index* idx = b->idx;
+    const Route& r = b->route;
+    const bool conj = r.conj, ranked = r.ranked, bigk = r.bigk;
+    const uint32_t k = b->k;
+    std::vector<QTerm>& qterms = ch.qterms;
+    std::vector<uint32_t>& qnbs = ch.qnbs;
+    std::vector<uint32_t>& qnb0 = b->qnb0;
+    std::vector<uint32_t> t;
+    std::vector<std::pair<uint32_t, uint32_t>> tf; // (term, query term frequency)
     qterms.clear();
     qnbs.clear();
-    qoff.assign(nq + 1, 0);
-    qcost.assign(nq, 0.0);
-    qnb0.assign(nq, 0);
-    b->match_off.assign(nq + 1, 0);
-    b->long_terms = 0;
-    const bool split_ok = conj && !(op & DS2I_OP_REFERENCE_ORDER);
-    double total_cost[NCLS] = {};
-    // The per-query half of planning (normalisation, BM25 query weights, list order, costs, bounds) is independent from query
-    // to query: the batch is cut into contiguous ranges, one per planning thread (DS2I_PLAN_THREADS, default 4, the caller's
-    // thread takes the first range), each range fills vectors of its own, and the ranges are joined by one copy. At
-    // configs[1] scale the host's 0.9 ms of planning per 1.3 ms of kernels is what bounds the end-to-end rate, and the
-    // same holds for a batch cut over 8 GPUs; the unit list and the class orders below stay sequential.
-    typedef PlanChunk Chunk;
-    auto plan_range = [&](Chunk& ch) {
-        std::vector<QTerm>& qterms = ch.qterms;
-        std::vector<uint32_t>& qnbs = ch.qnbs;
-        std::vector<uint32_t> t;
-        std::vector<std::pair<uint32_t, uint32_t>> tf; // (term, query term frequency)
-        qterms.clear();
-        qnbs.clear();
-        for (uint32_t q = ch.q0; q < ch.q1; ++q) {
+    for (uint32_t q = ch.q0; q < ch.q1; ++q) {
         if (query_offsets[q + 1] < query_offsets[q])
             { ch.rc = DS2I_EINVAL; ch.err = "query_offsets must be non-decreasing"; return; }
         t.assign(terms + query_offsets[q], terms + query_offsets[q + 1]);
@@ -429,13 +462,28 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
                 qterms[begin].floor1 = f;
             }
         }
-        qoff[q + 1] = (uint32_t)(qterms.size() - begin); // (terms of this query: turned into offsets once the ranges are joined)
-        qcost[q] = cost;
-        ch.total_cost[goes_long(tf.size()) ? CLS_LONG : class_of(tf.size())] += cost;
+        b->qoff[q + 1] = (uint32_t)(qterms.size() - begin); // (terms of this query: turned into offsets once the ranges are joined)
+        b->qcost[q] = cost;
+        ch.total_cost[r.goes_long(tf.size()) ? CLS_LONG : class_of(tf.size())] += cost;
         if (tf.size() > DS2I_HIP_MAX_TERMS) ch.over16 = true;
-        if (goes_long(tf.size())) ch.long_terms = std::max<uint32_t>(ch.long_terms, (uint32_t)std::max<size_t>(1, tf.size()));
-        }
-    };
+        if (r.goes_long(tf.size())) ch.long_terms = std::max<uint32_t>(ch.long_terms, (uint32_t)std::max<size_t>(1, tf.size()));
+    }
+}
+
+// The per-query half of planning (normalisation, BM25 query weights, list order, costs, bounds) is independent from query
+// to query: the batch is cut into contiguous ranges, one per planning thread (DS2I_PLAN_THREADS, default 4, the caller's
+// thread takes the first range), each range fills vectors of its own, and the ranges are joined by one copy. At
+// configs[1] scale the host's 0.9 ms of planning per 1.3 ms of kernels is what bounds the end-to-end rate, and the
+// same holds for a batch cut over 8 GPUs; the unit list and the class orders below stay sequential.
+// all_cost: the cost of the whole batch (cut_units sizes its units by it)
+static int plan_queries(ds2i_hip_batch* b, const uint32_t* terms, const uint32_t* query_offsets, double& all_cost) {
+    Route& r = b->route;
+    const uint32_t nq = b->nq;
+    b->qoff.assign(nq + 1, 0);
+    b->qcost.assign(nq, 0.0);
+    b->qnb0.assign(nq, 0);
+    b->match_off.assign(nq + 1, 0);
+    b->long_terms = 0;
     // default: 4, but never more than this process's share of the CPUs it may use -- one rank per GPU under torchrun
     // (LOCAL_WORLD_SIZE) on a host whose cgroup grants 16 CPUs leaves each of 8 ranks one planning thread
     static const unsigned default_threads = [] {
@@ -451,9 +499,9 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
         const double mine = cpus / ranks - 1.0; // (one for the thread that drives the pipeline)
         return (unsigned)std::max(1.0, std::min(4.0, mine));
     }();
-    const unsigned want_threads = kn.plan_threads ? kn.plan_threads : default_threads;
+    const unsigned want_threads = b->idx->knobs.plan_threads ? b->idx->knobs.plan_threads : default_threads;
     const unsigned nchunks = nq >= 1024 ? std::max(1u, std::min(want_threads, 16u)) : 1u;
-    std::vector<Chunk>& chunks = b->plan_chunks;
+    std::vector<PlanChunk>& chunks = b->plan_chunks;
     if (chunks.size() < nchunks) chunks.resize(nchunks);
     for (unsigned c = 0; c < nchunks; ++c) {
         chunks[c].q0 = (uint32_t)((uint64_t)nq * c / nchunks);
@@ -466,50 +514,168 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
             chunks[c].over16 = false;
             for (double& v : chunks[c].total_cost) v = 0;
         }
-        ds2i_plan_pool_run(nchunks, [&](unsigned c) { plan_range(chunks[c]); });
+        ds2i_plan_pool_run(nchunks, [&](unsigned c) { plan_range(b, terms, query_offsets, chunks[c]); });
         for (unsigned c = 0; c < nchunks; ++c)
             if (chunks[c].rc) return ds2i_set_error(chunks[c].rc, chunks[c].err);
         // k > 64 through the union streams needs the whole batch on them (the kernels see virtual queries; k_daat_long does not): a
         // query beyond 16 terms sends the batch back to the one-document-per-step kernels -- planned again, once
         bool over = false;
         for (unsigned c = 0; c < nchunks; ++c) over = over || chunks[c].over16;
-        if (!(bigk_union && over)) break;
-        bigk_union = false;
+        if (!(r.bigk_union && over)) break;
+        r.bigk_union = false;
+        r.union_stream = r.seeded = false; // (at k > 64 both came with bigk_union: plan_route)
     }
-    {
-        size_t total = 0;
-        for (unsigned c = 0; c < nchunks; ++c) total += chunks[c].qterms.size();
-        qterms.resize(total);
-        qnbs.resize(total);
-        size_t at = 0;
-        for (unsigned c = 0; c < nchunks; ++c) {
-            if (!chunks[c].qterms.empty()) {
-                std::memcpy(qterms.data() + at, chunks[c].qterms.data(), chunks[c].qterms.size() * sizeof(QTerm));
-                std::memcpy(qnbs.data() + at, chunks[c].qnbs.data(), chunks[c].qnbs.size() * 4);
-            }
-            at += chunks[c].qterms.size();
-            for (int k2 = 0; k2 < NCLS; ++k2) total_cost[k2] += chunks[c].total_cost[k2];
-            b->long_terms = std::max(b->long_terms, chunks[c].long_terms);
+    size_t total = 0;
+    for (unsigned c = 0; c < nchunks; ++c) total += chunks[c].qterms.size();
+    b->qterms.resize(total);
+    b->qnbs.resize(total);
+    size_t at = 0;
+    double total_cost[NCLS] = {};
+    for (unsigned c = 0; c < nchunks; ++c) {
+        if (!chunks[c].qterms.empty()) {
+            std::memcpy(b->qterms.data() + at, chunks[c].qterms.data(), chunks[c].qterms.size() * sizeof(QTerm));
+            std::memcpy(b->qnbs.data() + at, chunks[c].qnbs.data(), chunks[c].qnbs.size() * 4);
         }
-        for (uint32_t q = 0; q < nq; ++q) qoff[q + 1] += qoff[q];
+        at += chunks[c].qterms.size();
+        for (int k2 = 0; k2 < NCLS; ++k2) total_cost[k2] += chunks[c].total_cost[k2];
+        b->long_terms = std::max(b->long_terms, chunks[c].long_terms);
     }
+    for (uint32_t q = 0; q < nq; ++q) b->qoff[q + 1] += b->qoff[q];
     for (uint32_t q = 0; q < nq; ++q) b->match_off[q + 1] += b->match_off[q];
+    if (b->long_terms) r.union_stream = false; // (a query goes long: the whole batch keeps the windowed kernel -- Route::union_stream)
+    all_cost = 0;
+    for (double c : total_cost) all_cost += c;
+    return DS2I_OK;
+}
 
-    // ---- work units: long conjunctive queries are split by block ranges of their shortest list so
-    // that one giant query does not pin a single wavefront (SURVEY.md §7 "Load imbalance")
+void add_unit(ds2i_hip_batch* b, int c, uint32_t q, uint32_t lo, uint32_t hi, uint32_t parts, double cost) {
+    b->cls_units[c].push_back((uint32_t)b->units.size());
+    b->units.push_back(Unit{q, lo, hi, parts});
+    b->unit_cost.push_back((float)cost);
+}
+
+// and / and_freq of a query whose lists all carry their exact bitmap (cut_units): the query is a sum over the postings of its shortest
+// list (and, with the freqs, over every list's own postings) of one bit test per other list -- list streams, no units (k_and_stream)
+// (and_query reads only its shortest list: that one needs no bitmap of its own)
+// One-term queries (and_query walks the list and counts it, queries.hpp:58-84): the same stream with no other list -- beside
+// the class kernels instead of in front of the two-term group on class 0's stream (424 of 4096 queries, 5 of that class's 9 ms)
+// Returns false, and adds nothing, when a list lacks its bitmap.
+bool add_list_streams(ds2i_hip_batch* b, uint32_t q, uint32_t nt) {
+    const ds2i_hip_index* idx = b->idx;
+    const int base_op = b->route.base_op;
+    const std::vector<QTerm>& qterms = b->qterms;
+    const std::vector<uint32_t>& qoff = b->qoff;
+    bool dense = true;
+    for (uint32_t i = qoff[q] + (base_op == DS2I_OP_AND ? 1u : 0u); nt > 1 && i < qoff[q + 1]; ++i)
+        dense = dense && ds2i_dev::RmwLevels::has_bitmap(qterms[i].n, (uint32_t)idx->num_docs);
+    if (!dense) return false;
+    const uint32_t lists = base_op == DS2I_OP_AND_FREQ ? nt : 1u;
+    for (uint32_t i = 0; i < lists; ++i) {
+        const QTerm& t = qterms[qoff[q] + i];
+        ds2i_dev::StreamTerm st{};
+        st.list_off = t.list_off;
+        st.tail = t.aux1;
+        st.n = t.n;
+        st.blk_base = t.blk_base;
+        st.q = q;
+        st.counts = i == 0 ? 1u : 0u;
+        st.nother = nt - 1;
+        uint32_t k2 = 0;
+        for (uint32_t j = 0; j < nt; ++j) {
+            if (j == i) continue;
+            const QTerm& o = qterms[qoff[q] + j];
+            st.bm[k2++] = 64ull * o.rmw_off64 + ds2i_dev::RmwLevels((uint32_t)idx->num_docs, o.rmw_shift).bytes();
+        }
+        b->sterms.push_back(st);
+        b->sterm_longest = std::max(b->sterm_longest, t.nblocks);
+    }
+    return true;
+}
+
+// wand / maxscore / ranked_or as streams (cut_units): the virtual queries of query q (one per driving list) and their units
+void cut_union_query(ds2i_hip_batch* b, uint32_t q, int c, uint32_t ut_blocks) {
+    const std::vector<QTerm>& qterms = b->qterms;
+    const uint32_t nt = b->qoff[q + 1] - b->qoff[q];
+    // lists by decreasing max score (device-computed list maxima x query weight); a document belongs to the first
+    // list of that order that holds it, so what list e owns scores at most S_e = the maxima from e down. A list
+    // whose S_e is below the static floor (some term's k-th best block weight) gets no units at all -- MaxScore's
+    // non-essential lists, decided at plan time; the kernel re-checks against the live threshold.
+    const size_t begin = b->qoff[q];
+    uint32_t ord[DS2I_HIP_MAX_TERMS];
+    for (uint32_t i = 0; i < nt; ++i) ord[i] = i;
+    for (uint32_t i = 1; i < nt; ++i) { // stable insertion sort, descending max score
+        const uint32_t v = ord[i];
+        uint32_t j = i;
+        while (j > 0 && qterms[begin + v].max_bmw > qterms[begin + ord[j - 1]].max_bmw) { ord[j] = ord[j - 1]; --j; }
+        ord[j] = v;
+    }
+    float suffix[DS2I_HIP_MAX_TERMS + 1];
+    suffix[nt] = 0.f;
+    for (uint32_t e = nt; e-- > 0;) suffix[e] = suffix[e + 1] + qterms[begin + ord[e]].max_bmw;
+    const float f1 = qterms[begin].floor1;
+    const size_t first_unit = b->units.size();
+    for (uint32_t e = 0; e < nt; ++e) {
+        if (e && suffix[e] * (1.0f + 1.0f / 65536.0f) < f1 * (1.0f - 1.0e-5f)) break; // this list and all after it: non-essential
+        const uint32_t vq = (uint32_t)b->voff.size() - 1;
+        QTerm drv = qterms[begin + ord[e]];
+        drv.suf_bmw = suffix[e + 1];
+        drv.floor1 = f1;
+        drv.max_weight = suffix[0]; // (k_union_stream: the query's score bound = the scale of its shared histogram)
+        b->vterms.push_back(drv);
+        for (uint32_t j = 0; j < e; ++j) { // exclusion lists
+            QTerm t = qterms[begin + ord[j]];
+            t.suf_bmw = suffix[e + 1];
+            b->vterms.push_back(t);
+        }
+        for (uint32_t j = e + 1; j < nt; ++j) { // optional lists
+            QTerm t = qterms[begin + ord[j]];
+            t.suf_bmw = suffix[j + 1];
+            b->vterms.push_back(t);
+        }
+        b->voff.push_back((uint32_t)b->vterms.size());
+        uint32_t sbits;
+        std::memcpy(&sbits, &suffix[0], 4);
+        b->vinfo.push_back(q);
+        b->vinfo.push_back(e);
+        b->vinfo.push_back(sbits);
+        const uint32_t nbe = std::max(1u, b->qnbs[begin + ord[e]]);
+        // (the 9-16-term class runs two waves per SIMD: its units are cut 4 times finer, for more of them at once)
+        const uint32_t utb_c = c == 3 ? std::max(4u, ut_blocks / 4u) : ut_blocks;
+        const uint32_t lo0 = 0;
+        const uint32_t nrest = nbe - lo0;
+        const uint32_t parts_e = (nrest + utb_c - 1) / utb_c, per = (nrest + parts_e - 1) / parts_e;
+        for (uint32_t lo = lo0; lo < nbe; lo += per) // (the driving lists of higher max score first: they raise the threshold)
+            add_unit(b, c, vq, lo, std::min(nbe, lo + per), 0, (double)(nt - e) * 1.0e7 + (double)(std::min(nbe, lo + per) - lo));
+    }
+    const uint32_t total = (uint32_t)(b->units.size() - first_unit);
+    for (size_t ui = first_unit; ui < b->units.size(); ++ui) b->units[ui].nparts = total;
+    if (total > 1) b->split_queries.push_back(q);
+}
+
+// ---- work units: long conjunctive queries are split by block ranges of their shortest list so
+// that one giant query does not pin a single wavefront (SURVEY.md §7 "Load imbalance")
+// all_cost: the batch's cost (plan_queries), scaled here to the batches in flight
+static void cut_units(ds2i_hip_batch* b, double& all_cost) {
+    const ds2i_hip_index* idx = b->idx;
+    const Route& r = b->route;
+    const uint32_t nq = b->nq;
+    const std::vector<uint32_t>& qoff = b->qoff;
+    const std::vector<uint32_t>& qnb0 = b->qnb0;
+    const std::vector<double>& qcost = b->qcost;
     b->units.clear();
     b->unit_cost.clear();
     b->q_unit_off.assign(nq + 1, 0);
     b->split_queries.clear();
     b->single_queries.clear();
-    std::vector<uint32_t> cls_ids[NCLS];
-    for (int c = 0; c < NCLS; ++c) b->nqcls[c] = 0;
-    // ranked_or takes the seed only in its block-synchronous form: its reference-order traversal stays the unpruned
-    // exhaustive OR of queries.hpp:404-476 (the oracle the reference tests wand / maxscore against)
-    const bool seeded = nq && (!bigk || bigk_union) && (base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE ||
-                                        (base_op == DS2I_OP_RANKED_OR && !(op & DS2I_OP_REFERENCE_ORDER)));
-    double all_cost = 0;
-    for (double c : total_cost) all_cost += c;
+    for (int c = 0; c < NCLS; ++c) {
+        b->cls_units[c].clear();
+        b->nqcls[c] = 0;
+    }
+    b->sterms.clear();
+    b->sterm_longest = 0;
+    b->vterms.clear();
+    b->voff.assign(1, 0);
+    b->vinfo.clear();
     // A pipeline keeps several batches in flight: a small batch shares the wave slots with its neighbours, so its units are sized as if
     // two or three of them were one batch. Sized against its own cost alone a 512-query batch was cut into 20 k units -- three and a half
     // full rounds of the wave slots, each unit paying its window fill and its heap's warm-up. Measured at GOV2 scale (queries/s with the
@@ -521,46 +687,17 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
     // With range tables a ranked conjunction is cheap per block and the parts of a split query each pay for warming up
     // their own heap: coarser units win (measured on the GOV2-scale batch, queries/s: factor 16: 355 k, 8: 344 k,
     // 4 with the many-list classes cut 4x finer: 430-457 k, 2: 251 k)
-    const bool rmw_units = ranked && conj && idx->d_rmw; // (and / and_freq verify every candidate the tables let through: their cost
-                                                         // stays with the blocks of all lists, and they are throughput-, not tail-bound: measured)
+    const bool rmw_units = r.ranked && r.conj && idx->d_rmw; // (and / and_freq verify every candidate the tables let through: their cost
+                                                             // stays with the blocks of all lists, and they are throughput-, not tail-bound: measured)
     // (a small batch -- the per-GPU share of a batch sharded over several GPUs -- is cut coarser still: at 512 queries factor 2
     // measured 391 k queries/s against 321-328 k with 4; at 4096 it is the other way round)
-    const double unit_factor = kn.unit_factor > 0 ? kn.unit_factor : rmw_units ? (nq < 1536 ? 2.0 : 4.0) : 16.0;
-    // wand / maxscore / ranked_or: the streaming form (kernels.hip, k_union_topk) needs the range tables and the block weights;
-    // queries beyond 16 terms and k > 64 keep the one-document-per-step kernel, and the whole batch keeps the windowed
-    // kernel when any query does (one operator = one kernel family per batch)
-    const bool disj_topk_op = base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR;
-    b->union_stream = disj_topk_op && !(op & DS2I_OP_REFERENCE_ORDER) && (!bigk || bigk_union) && idx->d_rmw && idx->d_bmw && idx->d_skip_or_pef() &&
-                      !b->long_terms;
-    // (list_stream: what a stream over ONE list needs -- its blocks through the side slots; and_stream: the other lists' bitmaps as well)
-    const bool list_stream = (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ) && !(op & DS2I_OP_REFERENCE_ORDER) && !b->want_matches &&
-                             idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && idx->d_tails && idx->d_skip && !kn.no_list_streams && !b->no_list_streams;
-    const bool and_stream = list_stream && idx->d_rmw && idx->has_bitmaps;
+    const double unit_factor = idx->knobs.unit_factor > 0 ? idx->knobs.unit_factor : rmw_units ? (nq < 1536 ? 2.0 : 4.0) : 16.0;
     const uint32_t and_unit_blocks = 96u; // (measured, `and`: 48: 965 k, 96: 1 068 k, 192: 1 190 k against 1 360 k of the same build, whole queries: 802 k; and_freq: 24 | 48 | 96 all 334-337 k)
-    const bool and_rs_units = (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ) && !(op & DS2I_OP_REFERENCE_ORDER) && idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && idx->d_skip &&
-                              idx->d_bmw && idx->d_rmw && !kn.no_ranked_stream;
-    b->sterms.clear();
-    b->sterm_longest = 0;
-    b->union_rstream = false;
-    b->freq_stream = base_op == DS2I_OP_OR_FREQ && !(op & DS2I_OP_REFERENCE_ORDER) && idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && idx->d_tails &&
-                     idx->d_skip && !kn.no_list_streams && !b->no_list_streams;
-    b->vterms.clear();
-    b->voff.assign(1, 0);
-    b->vinfo.clear();
-    const uint32_t ut_blocks = kn.ut_blocks; // DS2I_UT_BLOCKS, default 320: blocks of the driving list per unit (k_union_topk, round 4: 96: 335 k, 128-256: 345-352 k, 384: 335 k queries/s; k_union_stream, round 6: 64: 240 k, 160: 378 k, 320: 401 k)
-    auto add_unit = [&](int c, uint32_t q, uint32_t lo, uint32_t hi, uint32_t parts, double cost) {
-        Unit u;
-        u.q = q;
-        u.blk_begin = lo;
-        u.blk_end = hi;
-        u.nparts = parts;
-        cls_ids[c].push_back((uint32_t)b->units.size());
-        b->units.push_back(u);
-        b->unit_cost.push_back((float)cost);
-    };
+    const uint32_t ut_blocks = idx->knobs.ut_blocks; // DS2I_UT_BLOCKS, default 320: blocks of the driving list per unit (k_union_topk, round 4: 96: 335 k, 128-256: 345-352 k, 384: 335 k queries/s; k_union_stream, round 6: 64: 240 k, 160: 378 k, 320: 401 k)
+    const bool split_ok = r.conj && !r.reference;
     for (uint32_t q = 0; q < nq; ++q) {
         const uint32_t nt = qoff[q + 1] - qoff[q];
-        const int c = goes_long(nt) ? CLS_LONG : class_of(nt);
+        const int c = r.goes_long(nt) ? CLS_LONG : class_of(nt);
         // multi-list units are latency-bound chains (non-sequential probes): cut 4x finer so the tail stays parallel; the 9-16-term
         // class (one or two waves per SIMD; its few, long units were the last thing every batch waited for) 4x finer still
         const double unit_div = 4.0, unit_div_rmw = 4.0, unit_div_many = 4.0;
@@ -571,48 +708,18 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
         const double target = std::max(floor_cost, all_cost / (unit_factor * resident) / (c == 0 ? 1.0 : rmw_cost ? unit_div_rmw : unit_div) /
                                                        (c == 3 && rmw_cost ? unit_div_many : 1.0));
         ++b->nqcls[c];
-        if ((and_stream && nt >= 2 && nt <= 4) || (list_stream && nt == 1)) {
-            // every list carries its exact bitmap: the query is a sum over the postings of its shortest list (and, with the freqs,
-            // over every list's own postings) of one bit test per other list -- list streams, no units (k_and_stream)
-            // (and_query reads only its shortest list: that one needs no bitmap of its own)
-            // One-term queries (and_query walks the list and counts it, queries.hpp:58-84): the same stream with no other list -- beside
-            // the class kernels instead of in front of the two-term group on class 0's stream (424 of 4096 queries, 5 of that class's 9 ms)
-            bool dense = true;
-            for (uint32_t i = qoff[q] + (base_op == DS2I_OP_AND ? 1u : 0u); nt > 1 && i < qoff[q + 1]; ++i)
-                dense = dense && ds2i_dev::RmwLevels::has_bitmap(qterms[i].n, (uint32_t)idx->num_docs);
-            if (dense) {
-                const uint32_t lists = base_op == DS2I_OP_AND_FREQ ? nt : 1u;
-                for (uint32_t i = 0; i < lists; ++i) {
-                    const QTerm& t = qterms[qoff[q] + i];
-                    ds2i_dev::StreamTerm st{};
-                    st.list_off = t.list_off;
-                    st.tail = t.aux1;
-                    st.n = t.n;
-                    st.blk_base = t.blk_base;
-                    st.q = q;
-                    st.counts = i == 0 ? 1u : 0u;
-                    st.nother = nt - 1;
-                    uint32_t k2 = 0;
-                    for (uint32_t j = 0; j < nt; ++j) {
-                        if (j == i) continue;
-                        const QTerm& o = qterms[qoff[q] + j];
-                        st.bm[k2++] = 64ull * o.rmw_off64 + ds2i_dev::RmwLevels((uint32_t)idx->num_docs, o.rmw_shift).bytes();
-                    }
-                    b->sterms.push_back(st);
-                    b->sterm_longest = std::max(b->sterm_longest, t.nblocks);
-                }
-                b->q_unit_off[q + 1] = (uint32_t)b->units.size();
-                continue;
-            }
+        if (((r.and_stream && nt >= 2 && nt <= 4) || (r.list_stream && nt == 1)) && add_list_streams(b, q, nt)) {
+            b->q_unit_off[q + 1] = (uint32_t)b->units.size();
+            continue;
         }
-        if (seeded && nt == 1) { // one list: wand == maxscore == ranked_and, answered by the (block-synchronous) seed pass
+        if (r.seeded && nt == 1) { // one list: wand == maxscore == ranked_and, answered by the (block-synchronous) seed pass
             b->single_queries.push_back(q);
             b->q_unit_off[q + 1] = (uint32_t)b->units.size();
             continue;
         }
         if (c == CLS_LONG) { // > 16 terms: one unit, reference-order traversal over global scratch
-            add_unit(c, q, 0, conj ? std::max(1u, qnb0[q]) : (uint32_t)idx->num_docs, 1, qcost[q]);
-        } else if (conj) {
+            add_unit(b, c, q, 0, r.conj ? std::max(1u, qnb0[q]) : (uint32_t)idx->num_docs, 1, qcost[q]);
+        } else if (r.conj) {
             uint32_t parts = 1;
             if (split_ok && nt && qnb0[q] > 1) {
                 double want = std::floor(qcost[q] / target);
@@ -626,78 +733,25 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
                 // the kernel's span (DS2I_UNIT_CLOCK: 1 700 of 6 144 wave slots busy on average). The cost model above now prices
                 // such queries; DS2I_UNIT_CAP (blocks; half of it beyond 2 lists) additionally bounds every unit -- off by
                 // default: cutting EVERY query that fine cost 20 % (each part warms up its own heap). The tests use it to split everything.
-                const uint32_t cap_env = kn.unit_cap;
+                const uint32_t cap_env = idx->knobs.unit_cap;
                 if (cap_env) parts = std::max(parts, (nb0 + (c == 0 ? cap_env : std::max(8u, cap_env / 2)) - 1) / (c == 0 ? cap_env : std::max(8u, cap_env / 2)));
             }
             // `and` through the stream pipeline has no heap to warm up -- a part costs its blocks and nothing else -- and a two-list query
             // left whole was a single wave for up to 13 ms (DS2I_UNIT_CLOCK: class 0 = 487 units, median 4.9 ms, 229 waves busy on
             // average, the span of the whole batch): at most 96 blocks of the shortest list per unit
-            if (and_rs_units && split_ok && nt > 1 && nt <= rs_stream_nt_max()) parts = std::max(parts, (nb0 + and_unit_blocks - 1) / and_unit_blocks);
+            if (r.and_rs_units && split_ok && nt > 1 && nt <= r.stream_nt_max) parts = std::max(parts, (nb0 + and_unit_blocks - 1) / and_unit_blocks);
             const uint32_t per = (nb0 + parts - 1) / parts;
             parts = (nb0 + per - 1) / per;
             if (parts > 1) b->split_queries.push_back(q);
-            for (uint32_t j = 0; j < parts; ++j) add_unit(c, q, j * per, std::min(nb0, (j + 1) * per), parts, qcost[q] / parts);
-        } else if (b->union_stream && !nt) { // empty query: one unit of an empty virtual query writes the empty answer
+            for (uint32_t j = 0; j < parts; ++j) add_unit(b, c, q, j * per, std::min(nb0, (j + 1) * per), parts, qcost[q] / parts);
+        } else if (r.union_stream && !nt) { // empty query: one unit of an empty virtual query writes the empty answer
             b->voff.push_back((uint32_t)b->vterms.size());
             b->vinfo.push_back(q);
             b->vinfo.push_back(0);
             b->vinfo.push_back(0);
-            add_unit(c, (uint32_t)b->voff.size() - 2, 0, 0, 1, 0.0);
-        } else if (b->union_stream) {
-            // lists by decreasing max score (device-computed list maxima x query weight); a document belongs to the first
-            // list of that order that holds it, so what list e owns scores at most S_e = the maxima from e down. A list
-            // whose S_e is below the static floor (some term's k-th best block weight) gets no units at all -- MaxScore's
-            // non-essential lists, decided at plan time; the kernel re-checks against the live threshold.
-            const size_t begin = qoff[q];
-            uint32_t ord[DS2I_HIP_MAX_TERMS];
-            for (uint32_t i = 0; i < nt; ++i) ord[i] = i;
-            for (uint32_t i = 1; i < nt; ++i) { // stable insertion sort, descending max score
-                const uint32_t v = ord[i];
-                uint32_t j = i;
-                while (j > 0 && qterms[begin + v].max_bmw > qterms[begin + ord[j - 1]].max_bmw) { ord[j] = ord[j - 1]; --j; }
-                ord[j] = v;
-            }
-            float suffix[DS2I_HIP_MAX_TERMS + 1];
-            suffix[nt] = 0.f;
-            for (uint32_t e = nt; e-- > 0;) suffix[e] = suffix[e + 1] + qterms[begin + ord[e]].max_bmw;
-            const float f1 = qterms[begin].floor1;
-            const size_t first_unit = b->units.size();
-            for (uint32_t e = 0; e < nt; ++e) {
-                if (e && suffix[e] * (1.0f + 1.0f / 65536.0f) < f1 * (1.0f - 1.0e-5f)) break; // this list and all after it: non-essential
-                const uint32_t vq = (uint32_t)b->voff.size() - 1;
-                QTerm drv = qterms[begin + ord[e]];
-                drv.suf_bmw = suffix[e + 1];
-                drv.floor1 = f1;
-                drv.max_weight = suffix[0]; // (k_union_stream: the query's score bound = the scale of its shared histogram)
-                b->vterms.push_back(drv);
-                for (uint32_t j = 0; j < e; ++j) { // exclusion lists
-                    QTerm t = qterms[begin + ord[j]];
-                    t.suf_bmw = suffix[e + 1];
-                    b->vterms.push_back(t);
-                }
-                for (uint32_t j = e + 1; j < nt; ++j) { // optional lists
-                    QTerm t = qterms[begin + ord[j]];
-                    t.suf_bmw = suffix[j + 1];
-                    b->vterms.push_back(t);
-                }
-                b->voff.push_back((uint32_t)b->vterms.size());
-                uint32_t sbits;
-                std::memcpy(&sbits, &suffix[0], 4);
-                b->vinfo.push_back(q);
-                b->vinfo.push_back(e);
-                b->vinfo.push_back(sbits);
-                const uint32_t nbe = std::max(1u, qnbs[begin + ord[e]]);
-                // (the 9-16-term class runs two waves per SIMD: its units are cut 4 times finer, for more of them at once)
-                const uint32_t utb_c = c == 3 ? std::max(4u, ut_blocks / 4u) : ut_blocks;
-                const uint32_t lo0 = 0;
-                const uint32_t nrest = nbe - lo0;
-                const uint32_t parts_e = (nrest + utb_c - 1) / utb_c, per = (nrest + parts_e - 1) / parts_e;
-                for (uint32_t lo = lo0; lo < nbe; lo += per) // (the driving lists of higher max score first: they raise the threshold)
-                    add_unit(c, vq, lo, std::min(nbe, lo + per), 0, (double)(nt - e) * 1.0e7 + (double)(std::min(nbe, lo + per) - lo));
-            }
-            const uint32_t total = (uint32_t)(b->units.size() - first_unit);
-            for (size_t ui = first_unit; ui < b->units.size(); ++ui) b->units[ui].nparts = total;
-            if (total > 1) b->split_queries.push_back(q);
+            add_unit(b, c, (uint32_t)b->voff.size() - 2, 0, 0, 1, 0.0);
+        } else if (r.union_stream) {
+            cut_union_query(b, q, c, ut_blocks);
         } else {
             // or / ranked_or / wand / maxscore: units are equal-width doc-id ranges; every part keeps its own
             // top-k (its own pruning threshold), the merge is exact
@@ -709,7 +763,7 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
             // classes gain from finer parts
             static const double disj_scale[NCLS] = {4.0, 2.0, 4.0, 4.0, 1.0};
             // or / or_freq run as a stream (k_union): a part costs a positioning of every list plus its blocks, once each
-            const bool stream_or = !ranked && !(op & DS2I_OP_REFERENCE_ORDER);
+            const bool stream_or = !r.ranked && !r.reference;
             const double dtarget = std::max(48.0, all_cost / (unit_factor * (stream_or ? 1.0 : disj_scale[c]) * resident));
             if (nt && N > 1)
                 parts = (uint32_t)std::min<double>(std::max(1.0, std::floor(qcost[q] / dtarget)), std::min<double>(N, 1024.0));
@@ -717,15 +771,45 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
             parts = width ? (N + width - 1) / width : 1;
             if (parts > 1) b->split_queries.push_back(q);
             for (uint32_t j = 0; j < parts; ++j)
-                add_unit(c, q, j * width, (uint32_t)std::min<uint64_t>(N, (uint64_t)(j + 1) * width), parts, qcost[q] / parts);
+                add_unit(b, c, q, j * width, (uint32_t)std::min<uint64_t>(N, (uint64_t)(j + 1) * width), parts, qcost[q] / parts);
         }
         b->q_unit_off[q + 1] = (uint32_t)b->units.size();
     }
     b->nunits = (uint32_t)b->units.size();
     b->nsplit = (uint32_t)b->split_queries.size();
     b->nsingle = (uint32_t)b->single_queries.size();
+}
+
+// The units of class c stably partitioned by their list capacity (cap_of: 0 .. DS2I_HIP_MAX_TERMS + 1), largest first, and cut into
+// one launch group per capacity: capacities 2 .. DS2I_HIP_MAX_TERMS run `stream` (the stream kernel compiled for that capacity), the
+// others the class kernel with the class's list slots. Inside a group the units stay in cost order.
+template <class CapOf>
+void stream_groups(ds2i_hip_batch* b, int c, const CapOf& cap_of, uint32_t cls_lists, GroupKernel stream) {
+    uint32_t cnt[DS2I_HIP_MAX_TERMS + 2] = {}; // stable partition by capacity, largest first
+    for (uint32_t uid : b->order[c]) ++cnt[cap_of(uid)];
+    uint32_t start[DS2I_HIP_MAX_TERMS + 2], acc = 0;
+    for (int n = DS2I_HIP_MAX_TERMS + 1; n >= 0; --n) { start[n] = acc; acc += cnt[n]; }
+    std::vector<uint32_t>& tmp = b->scratch_u32;
+    tmp.resize(b->order[c].size());
+    for (uint32_t uid : b->order[c]) tmp[start[cap_of(uid)]++] = uid;
+    b->order[c].swap(tmp);
+    for (uint32_t i = 0; i < b->ncls[c];) {
+        uint32_t j = i;
+        const uint32_t l = cap_of(b->order[c][i]);
+        while (j < b->ncls[c] && cap_of(b->order[c][j]) == l) ++j;
+        const bool s = l >= 2 && l <= DS2I_HIP_MAX_TERMS;
+        b->sub[c].push_back({i, j, s ? l : cls_lists, s ? stream : GroupKernel::cls});
+        i = j;
+    }
+}
+
+// ---- launch groups: every class's units in cost order, cut into the groups its kernels are launched for
+static int form_groups(ds2i_hip_batch* b) {
+    const ds2i_hip_index* idx = b->idx;
+    const Route& r = b->route;
+    const std::vector<uint32_t>& qoff = b->qoff;
     for (int c = 0; c < NCLS; ++c) {
-        order_by_cost(b->unit_cost, cls_ids[c], b->order[c], b->scratch_u32); // costliest first
+        order_by_cost(b->unit_cost, b->cls_units[c], b->order[c], b->scratch_u32); // costliest first
         b->ncls[c] = (uint32_t)b->order[c].size();
         b->sub[c].clear();
         if (!b->ncls[c]) continue;
@@ -736,92 +820,44 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
         // 0 (off) 60.6 k, 1: 60.0 k, 2: 62.4 k, 4: 61.0 k queries/s.
         const uint32_t dyn_group = 2u;
         const uint32_t cls_lists = c == 0 ? 2u : c == 1 ? 4u : c == 2 ? 8u : 16u;
-        const bool union_kernel = !conj && !(op & DS2I_OP_REFERENCE_ORDER) && c != CLS_LONG;
+        const bool union_kernel = !r.conj && !r.reference && c != CLS_LONG;
         const int dyn_mincls = 2;
-        if (b->union_stream) {
+        if (r.union_stream) {
             // block_optpfor with every upload-time table: the virtual queries of 2 .. 8 lists run the pipelined stream kernel compiled for
             // exactly their list count (union_stream.hip), one launch group per count, back to back on the class stream -- as ranked_and
             // does (below); everything else (other codecs, 9-16 lists, the empty query's unit): k_union_topk, static LDS, one launch per class
-            const bool us_ok = !kn.no_union_rstream && c <= 3 && idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots && idx->d_tails && idx->d_skip && idx->d_bmw && idx->d_rmw;
-            b->union_rstream = b->union_rstream || us_ok;
-            if (!us_ok) {
-                b->sub[c].push_back({0u, b->ncls[c], cls_lists});
+            if (!(r.us_ok && c <= 3)) {
+                b->sub[c].push_back({0u, b->ncls[c], cls_lists, GroupKernel::cls});
                 continue;
             }
             // (list CAPACITIES 2 | 4 | 6 | 8 | 16: a launch group holds the virtual queries of cap - 1 and cap (9 .. 16) lists -- five groups
             // and five tails per batch; inside a group the units stay in cost order)
             auto cap_of = [&](uint32_t uid) { const uint32_t vq = b->units[uid].q, n = b->voff[vq + 1] - b->voff[vq]; return n < 2 ? 0u : n > DS2I_HIP_MAX_TERMS ? DS2I_HIP_MAX_TERMS + 1u : n > 8 ? (uint32_t)DS2I_HIP_MAX_TERMS : (n + 1u) & ~1u; };
-            {   // stable partition by capacity, largest first
-                uint32_t cnt[DS2I_HIP_MAX_TERMS + 2] = {};
-                for (uint32_t uid : b->order[c]) ++cnt[cap_of(uid)];
-                uint32_t start[DS2I_HIP_MAX_TERMS + 2], acc = 0;
-                for (int n = DS2I_HIP_MAX_TERMS + 1; n >= 0; --n) { start[n] = acc; acc += cnt[n]; }
-                std::vector<uint32_t>& tmp = b->scratch_u32;
-                tmp.resize(b->order[c].size());
-                for (uint32_t uid : b->order[c]) tmp[start[cap_of(uid)]++] = uid;
-                b->order[c].swap(tmp);
-            }
-            for (uint32_t i = 0; i < b->ncls[c];) {
-                uint32_t j = i;
-                const uint32_t l = cap_of(b->order[c][i]);
-                while (j < b->ncls[c] && cap_of(b->order[c][j]) == l) ++j;
-                ds2i_hip_batch::SubLaunch sl{i, j, l >= 2 && l <= DS2I_HIP_MAX_TERMS ? l : cls_lists};
-                sl.stream = l >= 2 && l <= DS2I_HIP_MAX_TERMS;
-                b->sub[c].push_back(sl);
-                i = j;
-            }
+            stream_groups(b, c, cap_of, cls_lists, r.bigk ? GroupKernel::union_stream_bigk : GroupKernel::union_stream);
             continue;
         }
-        // ranked_and on block_optpfor with every upload-time table: the 2- .. 8-term queries (block_mixed native: 2 .. 4) run the pipelined stream
-        // kernel compiled for exactly their list count (ranked_stream.hip), one launch group per count, back to back on the
-        // class stream; one-term queries and everything else keep the class kernel
-        // (the 5..8-term class takes the stream kernel too, up to DS2I_STREAM_NT_MAX lists -- block_optpfor only)
-        const bool no_rs = kn.no_ranked_stream;
-        const uint32_t rs_nt = idx->kind == DS2I_BLOCK_OPTPFOR ? rs_stream_nt_max() : 4u;
-        // `and` batches that do not ask for the doc-id lists take the same pipeline with AND = true -- a candidate whose hints settle
-        // its membership in every other list is counted without any of them being searched or decoded (k_conjunctive<false, ...>
-        // verifies every survivor of its filters by a probe).
-        const bool rs_and = (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ) && idx->kind == DS2I_BLOCK_OPTPFOR; // (with or without the doc-id lists)
-        const bool rs_ok = (base_op == DS2I_OP_RANKED_AND || rs_and) && !(op & DS2I_OP_REFERENCE_ORDER) && (!bigk || bigk_stream) && c <= (rs_nt > 8 ? 3 : rs_nt > 4 ? 2 : 1) && !no_rs &&
-                           ((idx->kind == DS2I_BLOCK_OPTPFOR && idx->d_xslots) || idx->kind == DS2I_BLOCK_MIXED) && idx->d_skip && idx->d_bmw && idx->d_rmw;
-        if (rs_ok) {
+        if (r.rs_ok && (uint32_t)c < r.rs_classes) {
             // launch groups by list CAPACITY 2 | 4 | 6 | 8 (block_optpfor: a group holds the queries of cap - 1 and cap lists, UnitRec::pad says
             // which; block_mixed native: the exact count, 2 .. 4): four groups and four tails per batch instead of seven; queries beyond
             // DS2I_STREAM_NT_MAX lists and one-term queries form the class kernel's groups. Inside a group the units stay in cost order.
-            const bool exact = idx->kind != DS2I_BLOCK_OPTPFOR;
-            auto nt_of = [&](uint32_t uid) { const uint32_t q = b->units[uid].q; return qoff[q + 1] - qoff[q]; };
             auto cap_of = [&](uint32_t uid) {
-                const uint32_t n = nt_of(uid);
-                if (n == 1 && bigk_stream) return 4u; // (k > 64: the one-term queries ride in the capacity-4 launch)
-                return n < 2 ? n : n > rs_nt ? DS2I_HIP_MAX_TERMS + 1u : exact ? n : n > 8 ? (uint32_t)DS2I_HIP_MAX_TERMS : (n + 1u) & ~1u;
+                const uint32_t q = b->units[uid].q, n = qoff[q + 1] - qoff[q];
+                if (n == 1 && r.bigk_stream) return 4u; // (k > 64: the one-term queries ride in the capacity-4 launch)
+                return n < 2 ? n : n > r.rs_nt ? DS2I_HIP_MAX_TERMS + 1u : r.exact ? n : n > 8 ? (uint32_t)DS2I_HIP_MAX_TERMS : (n + 1u) & ~1u;
             };
-            {   // stable partition by capacity, largest first
-                uint32_t cnt[DS2I_HIP_MAX_TERMS + 2] = {};
-                for (uint32_t uid : b->order[c]) ++cnt[cap_of(uid)];
-                uint32_t start[DS2I_HIP_MAX_TERMS + 2], acc = 0;
-                for (int n = DS2I_HIP_MAX_TERMS + 1; n >= 0; --n) { start[n] = acc; acc += cnt[n]; }
-                std::vector<uint32_t>& tmp = b->scratch_u32;
-                tmp.resize(b->order[c].size());
-                for (uint32_t uid : b->order[c]) tmp[start[cap_of(uid)]++] = uid;
-                b->order[c].swap(tmp);
-            }
-            for (uint32_t i = 0; i < b->ncls[c];) {
-                uint32_t j = i;
-                const uint32_t l = cap_of(b->order[c][i]);
-                while (j < b->ncls[c] && cap_of(b->order[c][j]) == l) ++j;
-                ds2i_hip_batch::SubLaunch sl{i, j, l >= 2 && l <= DS2I_HIP_MAX_TERMS ? l : cls_lists};
-                sl.stream = l >= 2 && l <= DS2I_HIP_MAX_TERMS;
-                b->sub[c].push_back(sl);
-                i = j;
-            }
+            const GroupKernel kernel = (r.base_op == DS2I_OP_AND || r.base_op == DS2I_OP_AND_FREQ) ? GroupKernel::and_rstream
+                                       : idx->kind == DS2I_BLOCK_MIXED                              ? GroupKernel::ranked_stream_mixed
+                                       : r.bigk                                                     ? GroupKernel::ranked_stream_bigk
+                                                                                                    : GroupKernel::ranked_stream;
+            stream_groups(b, c, cap_of, cls_lists, kernel);
             continue;
         }
-        if (union_kernel && !ranked) { // or / or_freq: the streaming kernel serves every list count (lists = ~0 says so)
-            b->sub[c].push_back({0u, b->ncls[c], 0xFFFFFFFFu});
+        if (union_kernel && !r.ranked) { // or / or_freq: the streaming kernel serves every list count (lists = ~0 says so)
+            b->sub[c].push_back({0u, b->ncls[c], 0xFFFFFFFFu, GroupKernel::cls});
             continue;
         }
         if (!union_kernel || c < dyn_mincls || dyn_group == 0) {
-            b->sub[c].push_back({0u, b->ncls[c], cls_lists});
+            b->sub[c].push_back({0u, b->ncls[c], cls_lists, GroupKernel::cls});
             continue;
         }
         auto lists_of = [&](uint32_t uid) {
@@ -839,26 +875,26 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
                 const uint32_t q = b->units[b->order[c][t]].q;
                 if (qoff[q + 1] - qoff[q] > l) return ds2i_set_error(DS2I_EINVAL, "internal: launch group has fewer list slots than a query of it");
             }
-            b->sub[c].push_back({i, j, l});
+            b->sub[c].push_back({i, j, l, GroupKernel::cls});
             i = j;
         }
     }
+    return DS2I_OK;
+}
 
-    if (kn.unit_clock) // (diagnostic)
-        std::fprintf(stderr, "ds2i plan: op %d nq %u units %u (per class %u %u %u %u %u) split queries %u cost %.0f, %.0f us\n", op, nq, b->nunits,
-                     b->ncls[0], b->ncls[1], b->ncls[2], b->ncls[3], b->ncls[4], b->nsplit, all_cost,
-                     1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - plan_t0).count());
-
-    // ---- layouts
+// ---- layouts: the upload block, the result block and the device scratch of the batch
+static void lay_out(ds2i_hip_batch* b) {
+    const Route& r = b->route;
+    const uint32_t nq = b->nq, k = b->k;
     size_t o = 0;
     auto place = [&](size_t bytes) { size_t at = o; o = align16(o + bytes); return at; };
-    if (b->union_stream) { // the kernels see the virtual queries; the per-query arrays (units by query, histogram slots) stay real
-        qterms.swap(b->vterms);
-        qoff.swap(b->voff);
+    if (r.union_stream) { // the kernels see the virtual queries; the per-query arrays (units by query, histogram slots) stay real
+        b->qterms.swap(b->vterms);
+        b->qoff.swap(b->voff);
     }
-    b->o_qterms = place(qterms.size() * sizeof(QTerm));
-    b->o_qoff = place(qoff.size() * 4);
-    b->o_vinfo = place(b->union_stream ? b->vinfo.size() * 4 : 0);
+    b->o_qterms = place(b->qterms.size() * sizeof(QTerm));
+    b->o_qoff = place(b->qoff.size() * 4);
+    b->o_vinfo = place(r.union_stream ? b->vinfo.size() * 4 : 0);
     b->o_units = place(b->units.size() * sizeof(Unit));
     b->o_q_unit_off = place(b->q_unit_off.size() * 4);
     b->o_split = place(b->split_queries.size() * 4);
@@ -867,8 +903,8 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
     for (uint32_t i = 0; i < b->nsplit; ++i) b->hist_slot[b->split_queries[i]] = i;
     b->o_hslot = place(b->hist_slot.size() * 4);
     for (int c = 0; c < NCLS; ++c) b->o_order[c] = place(b->order[c].size() * 4);
-    for (int c = 0; c < 4; ++c) b->o_urec[c] = place((b->union_rstream || c < rs_stream_classes()) ? b->order[c].size() * sizeof(ds2i_dev::UnitRec) : 0); // (classes of k_ranked_stream / k_union_stream)
-    b->o_qterm_q = place(b->freq_stream ? qterms.size() * 4 : 0);
+    for (int c = 0; c < 4; ++c) b->o_urec[c] = place(c < r.urec_classes() ? b->order[c].size() * sizeof(ds2i_dev::UnitRec) : 0);
+    b->o_qterm_q = place(r.freq_stream ? b->qterms.size() * 4 : 0);
     b->o_sterms = place(b->sterms.size() * sizeof(ds2i_dev::StreamTerm));
     b->o_match_off = place(b->want_matches ? b->match_off.size() * 8 : 0);
     b->up_bytes = o + 16;
@@ -885,56 +921,85 @@ static int plan_batch_impl(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t
     b->o_unit_topk_len = place(4 * nu1);
     b->o_unit_freq_sum = place(8 * nu1);
     // ranked_and / wand / maxscore / ranked_or: a 256-bucket score histogram per split query (kernels.hip, ScoreHist)
-    const bool disj_ranked = base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR;
-    const bool hist = !(op & DS2I_OP_REFERENCE_ORDER) && b->nsplit && ((base_op == DS2I_OP_RANKED_AND && idx->d_bmw) || disj_ranked);
+    const bool disj_ranked = r.base_op == DS2I_OP_WAND || r.base_op == DS2I_OP_MAXSCORE || r.base_op == DS2I_OP_RANKED_OR;
+    const bool hist = !r.reference && b->nsplit && ((r.base_op == DS2I_OP_RANKED_AND && b->idx->d_bmw) || disj_ranked);
     b->o_qfloor = place(hist ? 1024 * (size_t)b->nsplit : 16);
     b->o_qfloorw = place(hist ? 4 * (size_t)b->nsplit : 16); // k_ranked_stream: the floor the histogram implies, one word per split query
     b->scr_bytes = o;
+}
 
-    b->use_seed = seeded;
-    if (seeded) {
-        // The seed is the ranked_and top-k of a SUB-query: any k documents' partial scores bound the final k-th
-        // score from below. One- and two-term queries use all their terms (the one-term answer is final); longer
-        // queries use their two shortest lists -- the full conjunction of 5+ terms is usually too small to give k
-        // documents, while the rarest pair is cheap to intersect and carries the largest term weights.
-        const size_t seed_terms = 2;
-        // The streams (k_union_topk) start from the static floor and share a score histogram per query: measured on the
-        // GOV2-scale wand batch the sub-query pass costs 8.3 ms to save 17 % of the block decodes (209 k queries/s with it,
-        // 278 k without), so there only the one-term queries keep it -- it is what answers them.
-        const bool seed_single_only = b->union_stream;
-        auto& sterms = b->seed_terms;
-        auto& soffs = b->seed_offs;
-        sterms.clear();
-        soffs.assign(nq + 1, 0);
-        std::vector<uint32_t> dt;
-        for (uint32_t q = 0; q < nq; ++q) {
-            const uint32_t* qb = terms + query_offsets[q];
-            const uint32_t* qe = terms + query_offsets[q + 1];
-            dt.assign(qb, qe);
-            std::sort(dt.begin(), dt.end());
-            dt.erase(std::unique(dt.begin(), dt.end()), dt.end());
-            if (seed_single_only && dt.size() > 1) {
-                // no sub-query: the stream kernels find their floor themselves (static floor + shared histogram)
-            } else if (dt.size() > seed_terms && dt.size() > 2) {
-                std::stable_sort(dt.begin(), dt.end(), [&](uint32_t x, uint32_t y) { return idx->list_n[x] < idx->list_n[y]; });
-                dt.resize(std::max<size_t>(2, seed_terms));
-                for (const uint32_t* p = qb; p != qe; ++p) // keep multiplicities: the query term weight counts them
-                    if (std::find(dt.begin(), dt.end(), *p) != dt.end()) sterms.push_back(*p);
-            } else {
-                sterms.insert(sterms.end(), qb, qe);
-            }
-            soffs[q + 1] = (uint32_t)sterms.size();
+// ---- the seed pass (wand / maxscore / ranked_or): a ranked_and batch of its own over sub-queries of the same queries
+static int plan_seed(ds2i_hip_batch* b, const uint32_t* terms, const uint32_t* query_offsets) {
+    const ds2i_hip_index* idx = b->idx;
+    const uint32_t nq = b->nq;
+    // The seed is the ranked_and top-k of a SUB-query: any k documents' partial scores bound the final k-th
+    // score from below. One- and two-term queries use all their terms (the one-term answer is final); longer
+    // queries use their two shortest lists -- the full conjunction of 5+ terms is usually too small to give k
+    // documents, while the rarest pair is cheap to intersect and carries the largest term weights.
+    const size_t seed_terms = 2;
+    // The streams (k_union_topk) start from the static floor and share a score histogram per query: measured on the
+    // GOV2-scale wand batch the sub-query pass costs 8.3 ms to save 17 % of the block decodes (209 k queries/s with it,
+    // 278 k without), so there only the one-term queries keep it -- it is what answers them.
+    const bool seed_single_only = b->route.union_stream;
+    auto& sterms = b->seed_terms;
+    auto& soffs = b->seed_offs;
+    sterms.clear();
+    soffs.assign(nq + 1, 0);
+    std::vector<uint32_t> dt;
+    for (uint32_t q = 0; q < nq; ++q) {
+        const uint32_t* qb = terms + query_offsets[q];
+        const uint32_t* qe = terms + query_offsets[q + 1];
+        dt.assign(qb, qe);
+        std::sort(dt.begin(), dt.end());
+        dt.erase(std::unique(dt.begin(), dt.end()), dt.end());
+        if (seed_single_only && dt.size() > 1) {
+            // no sub-query: the stream kernels find their floor themselves (static floor + shared histogram)
+        } else if (dt.size() > seed_terms && dt.size() > 2) {
+            std::stable_sort(dt.begin(), dt.end(), [&](uint32_t x, uint32_t y) { return idx->list_n[x] < idx->list_n[y]; });
+            dt.resize(std::max<size_t>(2, seed_terms));
+            for (const uint32_t* p = qb; p != qe; ++p) // keep multiplicities: the query term weight counts them
+                if (std::find(dt.begin(), dt.end(), *p) != dt.end()) sterms.push_back(*p);
+        } else {
+            sterms.insert(sterms.end(), qb, qe);
         }
-        if (!b->seed) {
-            b->seed = new ds2i_hip_batch;
-            b->seed->idx = idx;
-        }
-        b->seed->pool_batches = b->pool_batches;
-        b->seed->no_bigk_streams = b->no_bigk_streams;
-        int rc = plan_batch(b->seed, DS2I_OP_RANKED_AND, k, sterms.data(), soffs.data(), nq, 0);
-        if (rc) return rc;
+        soffs[q + 1] = (uint32_t)sterms.size();
     }
-    return DS2I_OK;
+    if (!b->seed) {
+        b->seed = new ds2i_hip_batch;
+        b->seed->idx = b->idx;
+    }
+    b->seed->pool_batches = b->pool_batches;
+    b->seed->no_bigk_streams = b->no_bigk_streams;
+    return plan_batch(b->seed, DS2I_OP_RANKED_AND, b->k, sterms.data(), soffs.data(), nq, 0);
+}
+
+// (the plan's vectors grow with the batch: an allocation failure -- on the caller's thread or on a pool thread, see PlanPool -- is
+// an error code at the C boundary, not an exception crossing it)
+int plan_batch(ds2i_hip_batch* b, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq,
+               int want_matches) {
+    const auto plan_t0 = std::chrono::steady_clock::now();
+    if (!query_offsets || (!terms && nq && query_offsets[nq] > 0))
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_prepare: null argument");
+    try {
+        double all_cost = 0;
+        int rc = plan_route(b, op, k, nq, want_matches);
+        if (!rc) rc = plan_queries(b, terms, query_offsets, all_cost);
+        if (rc) return rc;
+        cut_units(b, all_cost);
+        rc = form_groups(b);
+        if (rc) return rc;
+        if (b->idx->knobs.unit_clock) // (diagnostic)
+            std::fprintf(stderr, "ds2i plan: op %d nq %u units %u (per class %u %u %u %u %u) split queries %u cost %.0f, %.0f us\n", op, nq, b->nunits,
+                         b->ncls[0], b->ncls[1], b->ncls[2], b->ncls[3], b->ncls[4], b->nsplit, all_cost,
+                         1e6 * std::chrono::duration<double>(std::chrono::steady_clock::now() - plan_t0).count());
+        lay_out(b);
+        b->use_seed = b->route.seeded && nq;
+        return b->use_seed ? plan_seed(b, terms, query_offsets) : DS2I_OK;
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory planning the batch");
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EINVAL, e.what());
+    }
 }
 
 // ---------------------------------------------------------------- upload: one async H2D copy of the packed plan
@@ -961,7 +1026,7 @@ int upload_batch(ds2i_hip_batch* b) {
     auto put = [&](size_t off, const void* src, size_t bytes) { if (bytes) std::memcpy(h + off, src, bytes); };
     put(b->o_qterms, b->qterms.data(), b->qterms.size() * sizeof(QTerm));
     put(b->o_qoff, b->qoff.data(), b->qoff.size() * 4);
-    if (b->union_stream) put(b->o_vinfo, b->vinfo.data(), b->vinfo.size() * 4);
+    if (b->route.union_stream) put(b->o_vinfo, b->vinfo.data(), b->vinfo.size() * 4);
     put(b->o_units, b->units.data(), b->units.size() * sizeof(Unit));
     put(b->o_q_unit_off, b->q_unit_off.data(), b->q_unit_off.size() * 4);
     put(b->o_split, b->split_queries.data(), b->split_queries.size() * 4);
@@ -969,26 +1034,21 @@ int upload_batch(ds2i_hip_batch* b) {
     put(b->o_hslot, b->hist_slot.data(), b->hist_slot.size() * 4);
     for (int c = 0; c < NCLS; ++c) put(b->o_order[c], b->order[c].data(), b->order[c].size() * 4);
     put(b->o_sterms, b->sterms.data(), b->sterms.size() * sizeof(ds2i_dev::StreamTerm));
-    if (b->freq_stream) { // or_freq: the query of every term (k_freq_stream adds a term's freqs to its query's checksum)
+    if (b->route.freq_stream) { // or_freq: the query of every term (k_freq_stream adds a term's freqs to its query's checksum)
         uint32_t* qq = (uint32_t*)(h + b->o_qterm_q);
         for (uint32_t q = 0; q < b->nq; ++q)
             for (uint32_t i = b->qoff[q]; i < b->qoff[q + 1]; ++i) qq[i] = q;
     }
-    for (int c = 0; c < 4 && b->union_rstream; ++c) { // k_union_stream: the unit, its virtual query's terms, its REAL query (results, histogram), its exclusion lists
+    // one record per ticket: what k_ranked_stream / k_union_stream read where a unit starts -- the unit, its query's terms, its query
+    // (k_union_stream: its virtual query's terms, its REAL query -- results, histogram -- and its exclusion lists)
+    const bool vq = b->route.union_stream;
+    for (int c = 0; c < b->route.urec_classes(); ++c) {
         ds2i_dev::UnitRec* r = (ds2i_dev::UnitRec*)(h + b->o_urec[c]);
         for (size_t i = 0; i < b->order[c].size(); ++i) {
             const uint32_t uid = b->order[c][i];
             const Unit& u = b->units[uid];
-            const uint32_t rq = b->vinfo[3 * (size_t)u.q];
-            r[i] = ds2i_dev::UnitRec{uid, rq, u.blk_begin, u.blk_end, u.nparts, b->qoff[u.q], b->hist_slot[rq], b->vinfo[3 * (size_t)u.q + 1] | ((b->qoff[u.q + 1] - b->qoff[u.q]) << 8)};
-        }
-    }
-    for (int c = 0; c < rs_stream_classes() && !b->union_stream; ++c) { // one record per ticket: what k_ranked_stream reads where a unit starts (conjunctive batches)
-        ds2i_dev::UnitRec* r = (ds2i_dev::UnitRec*)(h + b->o_urec[c]);
-        for (size_t i = 0; i < b->order[c].size(); ++i) {
-            const uint32_t uid = b->order[c][i];
-            const Unit& u = b->units[uid];
-            r[i] = ds2i_dev::UnitRec{uid, u.q, u.blk_begin, u.blk_end, u.nparts, b->qoff[u.q], b->hist_slot[u.q], b->qoff[u.q + 1] - b->qoff[u.q]};
+            const uint32_t rq = vq ? b->vinfo[3 * (size_t)u.q] : u.q, nt = b->qoff[u.q + 1] - b->qoff[u.q];
+            r[i] = ds2i_dev::UnitRec{uid, rq, u.blk_begin, u.blk_end, u.nparts, b->qoff[u.q], b->hist_slot[rq], vq ? b->vinfo[3 * (size_t)u.q + 1] | (nt << 8) : nt};
         }
     }
     if (b->want_matches) put(b->o_match_off, b->match_off.data(), b->match_off.size() * 8);
@@ -999,70 +1059,35 @@ int upload_batch(ds2i_hip_batch* b) {
 }
 
 // ---------------------------------------------------------------- launch: kernels + merge + one async D2H; no host sync
-int launch_batch(ds2i_hip_batch* b) {
-    ds2i_hip_index* idx = b->idx;
-    if (!b->uploaded) return ds2i_set_error(DS2I_EINVAL, "batch has not been prepared");
-    // a counting run launches the class kernel (ds2i_launch_batch) for a stream group, and the class kernels keep DS2I_HIP_MAX_K scores:
-    // at a larger k the rows would come back half written. enable_block_profile plans such batches without the k-wide streams
-    // (no_bigk_streams); anything else that reaches here is refused before a kernel is enqueued
-    const bool counting = b->instrument && b->profile_on;
-    if (counting && b->k > DS2I_HIP_MAX_K)
-        for (int c = 0; c < NCLS; ++c)
-            for (const auto& sl : b->sub[c])
-                if (b->ncls[c] && sl.stream)
-                    return ds2i_set_error(DS2I_EINVAL, "block profile at k > DS2I_HIP_MAX_K: a stream launch group would run a class kernel that keeps DS2I_HIP_MAX_K scores");
-    if (b->use_seed) { // block-synchronous ranked_and first: its k-th score seeds the pruning floor of every unit
-        b->seed->instrument = b->instrument;
-        b->seed->profile_on = b->profile_on;
-        b->seed->prof_ptr = b->prof_ptr;
-        b->seed->alt_streams = b->alt_streams;
-        int rc = launch_batch(b->seed);
-        if (rc) return rc;
+// The kernel a launch group runs in this launch: the one the plan chose for it, except in a counting run (block profile on,
+// instrumented: profiled_run), where a stream group runs the class kernel -- the class kernels count their block decodes
+GroupKernel launched_kernel(const ds2i_hip_batch* b, const ds2i_hip_batch::SubLaunch& sl) { return b->profiled_run ? GroupKernel::cls : sl.kernel; }
+
+// one launch group's kernel (a.order / a.urec / a.nslice / a.dyn_lists already point at the group)
+hipError_t launch_group(const ds2i_hip_batch* b, GroupKernel kernel, int c, const BatchArgs& a, hipStream_t s) {
+    const int lists = (int)a.dyn_lists;
+    switch (kernel) {
+    case GroupKernel::ranked_stream: return ds2i_launch_ranked_stream(lists, &a, a.nslice, s);
+    case GroupKernel::ranked_stream_bigk: return ds2i_launch_ranked_stream_bigk(lists, &a, a.nslice, s);
+    case GroupKernel::ranked_stream_mixed: return ds2i_launch_ranked_stream_mixed(lists, &a, a.nslice, s);
+    case GroupKernel::and_rstream: return ds2i_launch_and_rstream(lists, (b->op & 0xFF) == DS2I_OP_AND_FREQ ? 1 : 0, &a, a.nslice, s);
+    case GroupKernel::union_stream: return ds2i_launch_union_stream(lists, &a, a.nslice, s);
+    case GroupKernel::union_stream_bigk: return ds2i_launch_union_stream_bigk(lists, &a, a.nslice, s);
+    case GroupKernel::cls: break;
     }
-    b->profiled_run = counting;
-    // per-unit partials, shared floors, result block and counters start from zero. The clears go to the upload
-    // stream: they depend on nothing but the slot being free, so the class kernels of this batch can start while the
-    // previous batch is still being merged
-    hipStream_t sm = idx->s_merge, su = idx->s_up;
-    HIP_OK(hipMemsetAsync(b->d_scr.p, 0, b->scr_bytes, su));
-    HIP_OK(hipMemsetAsync(b->d_out.p, 0, b->out_bytes, su));
-    if (b->instrument) HIP_OK(hipMemsetAsync(b->d_stats.p, 0, NCLS * sizeof(Stats), su));
-    HIP_OK(hipEventRecord(b->ev_clear, su)); // also orders this launch after the batch's upload (same stream)
-    // Launch order of the class kernels (they overlap on separate streams either way; measured on the GOV2-scale
-    // batch): the block-synchronous conjunctions run 3 % faster when the issue-bound <=2-list class is enqueued first,
-    // the disjunctive operators 2.5 % faster when the many-list classes are.
-    const int base_op = b->op & 0xFF;
-    const bool small_first = !(b->op & DS2I_OP_REFERENCE_ORDER) &&
-                       (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ || base_op == DS2I_OP_RANKED_AND);
-    const bool unit_clock = ds2i_knobs().unit_clock; // diagnostic: per-unit start / end times
-    if (unit_clock && b->instrument) {
-        HIP_OK(b->d_clk.reserve(16 * (size_t)(b->nunits ? b->nunits : 1)));
-        HIP_OK(hipMemsetAsync(b->d_clk.p, 0, 16 * (size_t)(b->nunits ? b->nunits : 1), idx->s_up));
-        HIP_OK(hipStreamSynchronize(idx->s_up));
-    }
-    if (b->alt_streams) { // (capi_internal.hpp: the second set exists from the first small batch on)
-        std::lock_guard<std::mutex> lk(idx->stream_alt_mu);
-        if (!idx->stream_alt[0]) {
-            int lo_pri = 0, hi_pri = 0;
-            HIP_OK(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
-            for (int c = NCLS - 1; c >= 0; --c) // (slot 0 last: it is the "set exists" mark)
-                if (!idx->stream_alt[c]) HIP_OK(hipStreamCreateWithPriority(&idx->stream_alt[c], hipStreamNonBlocking, (lo_pri + hi_pri) / 2));
-        }
-    }
-    hipStream_t* const cstreams = b->alt_streams ? idx->stream_alt : idx->stream;
-    auto cls_stream = [&](int c) { return cstreams[c]; };
-    // every class stream first waits for the upload + cleared buffers, and for the seed pass when its floors feed the kernels. (In the
-    // union decomposition the seed pass only ANSWERS the one-term queries -- copied into the result block on the merge stream below --
-    // and the kernels of the longer queries start beside it: waiting cost the wand batch the one-term kernel's 1.2 ms in series.)
-    const bool seed_feeds = b->use_seed && !b->union_stream;
-    for (int c = 0; c < NCLS; ++c) {
-        if (!b->ncls[c]) continue;
-        HIP_OK(hipStreamWaitEvent(cls_stream(c), b->ev_clear, 0));
-        if (seed_feeds) HIP_OK(hipStreamWaitEvent(cls_stream(c), b->seed->ev_done, 0));
-    }
-    HIP_OK(hipStreamWaitEvent(sm, b->ev_clear, 0));
-    if (b->use_seed) HIP_OK(hipStreamWaitEvent(sm, b->seed->ev_done, 0));
-    if (!b->sterms.empty()) { // and / and_freq of the all-dense queries: list streams beside the class kernels (nobody else writes these queries' results)
+    return ds2i_launch_batch(b->route.freq_stream ? (int)DS2I_OP_OR : (b->op & (0xFF | DS2I_OP_REFERENCE_ORDER)), c, &a, a.nslice, s);
+}
+
+// and / and_freq of the all-dense queries: list streams beside the class kernels (nobody else writes these queries' results);
+// or_freq: its freqs beside the union kernels -- nobody else writes the checksums (the union kernels and k_merge get no pointer to them).
+// On the stream of the >16-term class when the batch has no such query (else on the merge stream, ahead of the merge).
+int launch_list_streams(ds2i_hip_batch* b, hipStream_t* cstreams, hipStream_t sm) {
+    const ds2i_hip_index* idx = b->idx;
+    const bool own = b->ncls[CLS_LONG] == 0;
+    hipStream_t sf = own ? cstreams[CLS_LONG] : sm;
+    if (own) HIP_OK(hipStreamWaitEvent(sf, b->ev_clear, 0));
+    if (!b->sterms.empty()) {
+        const bool with_freqs = (b->op & 0xFF) == DS2I_OP_AND_FREQ;
         ds2i_dev::AndStreamArgs g{};
         g.arena = idx->d_arena;
         g.skip = idx->d_skip;
@@ -1071,25 +1096,12 @@ int launch_batch(ds2i_hip_batch* b) {
         g.tails = idx->d_tails;
         g.rmw = idx->d_rmw;
         g.out_count = b->d_out.at<unsigned long long>(b->o_count);
-        g.out_freq_sum = base_op == DS2I_OP_AND_FREQ ? b->d_out.at<unsigned long long>(b->o_freq_sum) : nullptr;
-        const bool own = b->ncls[CLS_LONG] == 0;
-        hipStream_t sf = own ? cstreams[CLS_LONG] : sm;
-        if (own) HIP_OK(hipStreamWaitEvent(sf, b->ev_clear, 0));
+        g.out_freq_sum = with_freqs ? b->d_out.at<unsigned long long>(b->o_freq_sum) : nullptr;
         for (size_t t0 = 0; t0 < b->sterms.size(); t0 += 32768) { // (grid.y is limited to 65535)
             g.terms = b->d_up.at<ds2i_dev::StreamTerm>(b->o_sterms) + t0;
-            HIP_OK(ds2i_launch_and_stream(&g, base_op == DS2I_OP_AND_FREQ ? 1 : 0, b->sterm_longest, (unsigned)std::min<size_t>(32768, b->sterms.size() - t0), sf));
+            HIP_OK(ds2i_launch_and_stream(&g, with_freqs ? 1 : 0, b->sterm_longest, (unsigned)std::min<size_t>(32768, b->sterms.size() - t0), sf));
         }
-        if (own) {
-            HIP_OK(hipEventRecord(b->ev_c1[CLS_LONG], sf));
-            HIP_OK(hipStreamWaitEvent(sm, b->ev_c1[CLS_LONG], 0));
-        }
-    }
-    if (b->freq_stream && !b->qterms.empty()) {
-        // beside the union kernels, on the stream of the >16-term class when the batch has no such query (else on the merge
-        // stream, ahead of the merge): nobody else writes the checksums (the union kernels and k_merge get no pointer to them)
-        const bool own = b->ncls[CLS_LONG] == 0;
-        hipStream_t sf = own ? cstreams[CLS_LONG] : sm;
-        if (own) HIP_OK(hipStreamWaitEvent(sf, b->ev_clear, 0));
+    } else {
         ds2i_dev::FreqArgs f{};
         f.arena = idx->d_arena;
         f.skip = idx->d_skip;
@@ -1107,19 +1119,138 @@ int launch_batch(ds2i_hip_batch* b) {
             g.qterm_q += t0;
             HIP_OK(ds2i_launch_freq_stream(&g, longest, (unsigned)std::min<size_t>(32768, b->qterms.size() - t0), sf));
         }
-        if (own) {
-            HIP_OK(hipEventRecord(b->ev_c1[CLS_LONG], sf));
-            HIP_OK(hipStreamWaitEvent(sm, b->ev_c1[CLS_LONG], 0));
+    }
+    if (own) {
+        HIP_OK(hipEventRecord(b->ev_c1[CLS_LONG], sf));
+        HIP_OK(hipStreamWaitEvent(sm, b->ev_c1[CLS_LONG], 0));
+    }
+    return DS2I_OK;
+}
+
+// the kernel arguments every launch group of the batch shares (launch_batch adds the group's units and the class's counters)
+BatchArgs batch_args(const ds2i_hip_batch* b, bool seed_feeds) {
+    const ds2i_hip_index* idx = b->idx;
+    const int base_op = b->op & 0xFF;
+    BatchArgs a{};
+    a.arena = idx->d_arena;
+    a.bits0 = idx->d_bits0;
+    a.bits1 = idx->d_bits1;
+    a.norm_lens = idx->d_norm_lens;
+    a.min_norm_len = idx->min_norm_len;
+    a.qterms = b->d_up.at<QTerm>(b->o_qterms);
+    a.q_off = b->d_up.at<uint32_t>(b->o_qoff);
+    a.vq_info = b->route.union_stream ? b->d_up.at<uint32_t>(b->o_vinfo) : nullptr;
+    a.ut_first = 1u;
+    a.units = b->d_up.at<Unit>(b->o_units);
+    a.num_docs = (uint32_t)idx->num_docs;
+    a.k = b->k;
+    a.codec = idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; // every freq_index layout decodes through the chunk directory
+    a.unit_clock = (idx->knobs.unit_clock && b->instrument) ? (unsigned long long*)b->d_clk.p : nullptr;
+    a.out_count = b->d_out.at<unsigned long long>(b->o_count);
+    a.out_topk = b->d_out.at<float>(b->o_topk);
+    a.out_topk_len = b->d_out.at<uint32_t>(b->o_topk_len);
+    a.out_freq_sum = b->route.freq_stream ? nullptr : b->d_out.at<unsigned long long>(b->o_freq_sum);
+    a.out_matches = b->want_matches ? (uint32_t*)b->d_matches.p : nullptr;
+    a.match_off = b->want_matches ? b->d_up.at<unsigned long long>(b->o_match_off) : nullptr;
+    a.unit_count = b->d_scr.at<unsigned long long>(b->o_unit_count);
+    a.unit_topk = b->d_scr.at<float>(b->o_unit_topk);
+    a.unit_topk_len = b->d_scr.at<uint32_t>(b->o_unit_topk_len);
+    a.unit_freq_sum = b->d_scr.at<unsigned long long>(b->o_unit_freq_sum);
+    a.seed_topk = seed_feeds ? b->seed->d_out.at<float>(b->seed->o_topk) : nullptr;
+    a.seed_len = seed_feeds ? b->seed->d_out.at<uint32_t>(b->seed->o_topk_len) : nullptr;
+    const bool disj_topk = base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR;
+    a.q_floor = (base_op == DS2I_OP_RANKED_AND || b->route.union_rstream()) ? b->d_scr.at<unsigned int>(b->o_qfloorw) : nullptr;
+    a.q_hist = (!(b->op & DS2I_OP_REFERENCE_ORDER) && b->nsplit && ((base_op == DS2I_OP_RANKED_AND && idx->d_bmw) || disj_topk))
+                   ? b->d_scr.at<unsigned int>(b->o_qfloor) : nullptr;
+    a.q_hist_slot = b->d_up.at<uint32_t>(b->o_hslot);
+    a.block_profile = (b->instrument && b->profile_on) ? b->prof_ptr : nullptr;
+    a.skip = idx->d_skip;
+    a.bmw = idx->d_bmw;
+    a.rmw = (base_op == DS2I_OP_RANKED_AND && !a.bmw) ? nullptr : idx->d_rmw;
+    a.rmw_bitmaps = (a.rmw && idx->has_bitmaps) ? 1u : 0u;
+    a.rmh = a.rmw ? idx->d_rmh : nullptr;
+    a.xslots = idx->d_xslots;
+    a.xovf = idx->d_xovf;
+    a.tails = idx->d_tails;
+    a.long_scratch = (uint32_t*)b->d_long.p;
+    a.long_stride = (uint32_t)((size_t)b->long_terms * (256 + ds2i_meta_words() + 2) + 16);
+    return a;
+}
+
+int launch_batch(ds2i_hip_batch* b) {
+    ds2i_hip_index* idx = b->idx;
+    if (!b->uploaded) return ds2i_set_error(DS2I_EINVAL, "batch has not been prepared");
+    // a counting run launches the class kernel for a stream group (launched_kernel), and the class kernels keep DS2I_HIP_MAX_K scores:
+    // at a larger k the rows would come back half written. enable_block_profile plans such batches without the k-wide streams
+    // (no_bigk_streams); anything else that reaches here is refused before a kernel is enqueued
+    b->profiled_run = b->instrument && b->profile_on;
+    if (b->k > DS2I_HIP_MAX_K)
+        for (int c = 0; c < NCLS; ++c)
+            for (const auto& sl : b->sub[c])
+                if (sl.kernel != GroupKernel::cls && launched_kernel(b, sl) == GroupKernel::cls)
+                    return ds2i_set_error(DS2I_EINVAL, "block profile at k > DS2I_HIP_MAX_K: a stream launch group would run a class kernel that keeps DS2I_HIP_MAX_K scores");
+    if (b->use_seed) { // block-synchronous ranked_and first: its k-th score seeds the pruning floor of every unit
+        b->seed->instrument = b->instrument;
+        b->seed->profile_on = b->profile_on;
+        b->seed->prof_ptr = b->prof_ptr;
+        b->seed->alt_streams = b->alt_streams;
+        int rc = launch_batch(b->seed);
+        if (rc) return rc;
+    }
+    // per-unit partials, shared floors, result block and counters start from zero. The clears go to the upload
+    // stream: they depend on nothing but the slot being free, so the class kernels of this batch can start while the
+    // previous batch is still being merged
+    hipStream_t sm = idx->s_merge, su = idx->s_up;
+    HIP_OK(hipMemsetAsync(b->d_scr.p, 0, b->scr_bytes, su));
+    HIP_OK(hipMemsetAsync(b->d_out.p, 0, b->out_bytes, su));
+    if (b->instrument) HIP_OK(hipMemsetAsync(b->d_stats.p, 0, NCLS * sizeof(Stats), su));
+    HIP_OK(hipEventRecord(b->ev_clear, su)); // also orders this launch after the batch's upload (same stream)
+    // Launch order of the class kernels (they overlap on separate streams either way; measured on the GOV2-scale
+    // batch): the block-synchronous conjunctions run 3 % faster when the issue-bound <=2-list class is enqueued first,
+    // the disjunctive operators 2.5 % faster when the many-list classes are.
+    const int base_op = b->op & 0xFF;
+    const bool small_first = !(b->op & DS2I_OP_REFERENCE_ORDER) &&
+                       (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ || base_op == DS2I_OP_RANKED_AND);
+    if (idx->knobs.unit_clock && b->instrument) { // diagnostic: per-unit start / end times
+        HIP_OK(b->d_clk.reserve(16 * (size_t)(b->nunits ? b->nunits : 1)));
+        HIP_OK(hipMemsetAsync(b->d_clk.p, 0, 16 * (size_t)(b->nunits ? b->nunits : 1), idx->s_up));
+        HIP_OK(hipStreamSynchronize(idx->s_up));
+    }
+    if (b->alt_streams) { // (capi_internal.hpp: the second set exists from the first small batch on)
+        std::lock_guard<std::mutex> lk(idx->stream_alt_mu);
+        if (!idx->stream_alt[0]) {
+            int lo_pri = 0, hi_pri = 0;
+            HIP_OK(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
+            for (int c = NCLS - 1; c >= 0; --c) // (slot 0 last: it is the "set exists" mark)
+                if (!idx->stream_alt[c]) HIP_OK(hipStreamCreateWithPriority(&idx->stream_alt[c], hipStreamNonBlocking, (lo_pri + hi_pri) / 2));
         }
+    }
+    hipStream_t* const cstreams = b->alt_streams ? idx->stream_alt : idx->stream;
+    // every class stream first waits for the upload + cleared buffers, and for the seed pass when its floors feed the kernels. (In the
+    // union decomposition the seed pass only ANSWERS the one-term queries -- copied into the result block on the merge stream below --
+    // and the kernels of the longer queries start beside it: waiting cost the wand batch the one-term kernel's 1.2 ms in series.)
+    const bool seed_feeds = b->use_seed && !b->route.union_stream;
+    for (int c = 0; c < NCLS; ++c) {
+        if (!b->ncls[c]) continue;
+        HIP_OK(hipStreamWaitEvent(cstreams[c], b->ev_clear, 0));
+        if (seed_feeds) HIP_OK(hipStreamWaitEvent(cstreams[c], b->seed->ev_done, 0));
+    }
+    HIP_OK(hipStreamWaitEvent(sm, b->ev_clear, 0));
+    if (b->use_seed) HIP_OK(hipStreamWaitEvent(sm, b->seed->ev_done, 0));
+    if (!b->sterms.empty() || (b->route.freq_stream && !b->qterms.empty())) {
+        int rc = launch_list_streams(b, cstreams, sm);
+        if (rc) return rc;
     }
     // Two launch groups leave their class stream for the stream of a class this batch has no queries in (no further hardware queue is
     // opened; spreading EVERY second group that way was measured and lost): ranked_and's one-term queries (the class kernel's group of class 0: 0.9 ms behind the two-term stream
     // kernel's 2.5 ms on that class's stream) go to a spare stream -- class 0 is one of three co-critical class streams of the step
-    const bool side_group0 = base_op == DS2I_OP_RANKED_AND && !(b->op & DS2I_OP_REFERENCE_ORDER) && b->ncls[0] && b->sub[0].size() > 1 && b->sub[0].front().stream;
+    const bool side_group0 = base_op == DS2I_OP_RANKED_AND && !(b->op & DS2I_OP_REFERENCE_ORDER) && b->ncls[0] && b->sub[0].size() > 1 &&
+                             launched_kernel(b, b->sub[0].front()) != GroupKernel::cls;
     // ... and the second stream group of the 5-8-list class (capacity 6 behind capacity 8; wand: 3.6 ms behind 7.5 ms, and: 1.3 behind 1.8)
     hipStream_t spare[NCLS];
     int nspare = 0, next_spare = 0;
-    const bool side_group2 = b->ncls[2] && b->sub[2].size() > 1 && b->sub[2][0].stream && b->sub[2][1].stream;
+    const bool side_group2 = b->ncls[2] && b->sub[2].size() > 1 && launched_kernel(b, b->sub[2][0]) != GroupKernel::cls &&
+                             launched_kernel(b, b->sub[2][1]) != GroupKernel::cls;
     if (side_group0 || side_group2)
         for (int c = NCLS - 1; c >= 0; --c)
             if (!b->ncls[c]) {
@@ -1128,61 +1259,16 @@ int launch_batch(ds2i_hip_batch* b) {
                 if (seed_feeds) HIP_OK(hipStreamWaitEvent(spare[nspare], b->seed->ev_done, 0));
                 ++nspare;
             }
+    const BatchArgs args = batch_args(b, seed_feeds);
     for (int ci = NCLS - 1; ci >= 0; --ci) {
         const int c = small_first ? NCLS - 1 - ci : ci;
         if (!b->ncls[c]) continue;
-        hipStream_t s = cls_stream(c);
+        hipStream_t s = cstreams[c];
         HIP_OK(hipEventRecord(b->ev_c0[c], s));
-        BatchArgs a{};
-        a.arena = idx->d_arena;
-        a.bits0 = idx->d_bits0;
-        a.bits1 = idx->d_bits1;
-        a.norm_lens = idx->d_norm_lens;
-        a.min_norm_len = idx->min_norm_len;
-        a.qterms = b->d_up.at<QTerm>(b->o_qterms);
-        a.q_off = b->d_up.at<uint32_t>(b->o_qoff);
-        a.vq_info = b->union_stream ? b->d_up.at<uint32_t>(b->o_vinfo) : nullptr;
-        a.ut_first = 1u;
-        a.units = b->d_up.at<Unit>(b->o_units);
-        a.order = b->d_up.at<uint32_t>(b->o_order[c]);
-        a.urec = (c < 4 && (b->union_rstream || c < rs_stream_classes())) ? b->d_up.at<ds2i_dev::UnitRec>(b->o_urec[c]) : nullptr;
-        a.nslice = b->ncls[c];
-        a.dyn_lists = 0;
-        a.num_docs = (uint32_t)idx->num_docs;
-        a.k = b->k;
-        a.codec = idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; // every freq_index layout decodes through the chunk directory
-        a.unit_clock = (unit_clock && b->instrument) ? (unsigned long long*)b->d_clk.p : nullptr;
-        a.out_count = b->d_out.at<unsigned long long>(b->o_count);
-        a.out_topk = b->d_out.at<float>(b->o_topk);
-        a.out_topk_len = b->d_out.at<uint32_t>(b->o_topk_len);
-        a.out_freq_sum = b->freq_stream ? nullptr : b->d_out.at<unsigned long long>(b->o_freq_sum);
-        a.out_matches = b->want_matches ? (uint32_t*)b->d_matches.p : nullptr;
-        a.match_off = b->want_matches ? b->d_up.at<unsigned long long>(b->o_match_off) : nullptr;
-        a.unit_count = b->d_scr.at<unsigned long long>(b->o_unit_count);
-        a.unit_topk = b->d_scr.at<float>(b->o_unit_topk);
-        a.unit_topk_len = b->d_scr.at<uint32_t>(b->o_unit_topk_len);
-        a.unit_freq_sum = b->d_scr.at<unsigned long long>(b->o_unit_freq_sum);
-        a.seed_topk = seed_feeds ? b->seed->d_out.at<float>(b->seed->o_topk) : nullptr;
-        a.seed_len = seed_feeds ? b->seed->d_out.at<uint32_t>(b->seed->o_topk_len) : nullptr;
-        const bool disj_topk = base_op == DS2I_OP_WAND || base_op == DS2I_OP_MAXSCORE || base_op == DS2I_OP_RANKED_OR;
-        a.q_floor = (base_op == DS2I_OP_RANKED_AND || b->union_rstream) ? b->d_scr.at<unsigned int>(b->o_qfloorw) : nullptr;
-        a.q_hist = (!(b->op & DS2I_OP_REFERENCE_ORDER) && b->nsplit && ((base_op == DS2I_OP_RANKED_AND && idx->d_bmw) || disj_topk))
-                       ? b->d_scr.at<unsigned int>(b->o_qfloor) : nullptr;
-        a.q_hist_slot = b->d_up.at<uint32_t>(b->o_hslot);
-        a.block_profile = (b->instrument && b->profile_on) ? b->prof_ptr : nullptr;
-        a.skip = idx->d_skip;
-        a.bmw = idx->d_bmw;
-        a.rmw = (base_op == DS2I_OP_RANKED_AND && !a.bmw) ? nullptr : idx->d_rmw;
-        a.rmw_bitmaps = (a.rmw && idx->has_bitmaps) ? 1u : 0u;
-        a.rmh = a.rmw ? idx->d_rmh : nullptr;
-        a.xslots = idx->d_xslots;
-        a.xovf = idx->d_xovf;
-        a.tails = idx->d_tails;
-        a.long_scratch = (uint32_t*)b->d_long.p;
-        a.long_stride = (uint32_t)((size_t)b->long_terms * (256 + ds2i_meta_words() + 2) + 16);
+        BatchArgs a = args;
         a.stats = b->instrument ? b->d_stats.at<Stats>(0) + c : nullptr;
-        const uint32_t* order_base = a.order;
-        const ds2i_dev::UnitRec* urec_base = a.urec;
+        const uint32_t* order_base = b->d_up.at<uint32_t>(b->o_order[c]);
+        const ds2i_dev::UnitRec* urec_base = c < b->route.urec_classes() ? b->d_up.at<ds2i_dev::UnitRec>(b->o_urec[c]) : nullptr;
         for (const auto& sl : b->sub[c]) { // one launch per group of the class (a single group for everything but the union kernels)
             a.order = order_base + sl.begin;
             a.urec = urec_base ? urec_base + sl.begin : nullptr;
@@ -1196,14 +1282,10 @@ int launch_batch(ds2i_hip_batch* b) {
                 HIP_OK(hipEventCreate(&e));
                 b->ev_g[c].push_back(e);
             }
-            hipStream_t sg = (gi > 0 && nspare && ((c == 0 && side_group0 && !sl.stream) || (c == 2 && side_group2 && gi == 1))) ? spare[next_spare++ % nspare] : s;
+            const GroupKernel kernel = launched_kernel(b, sl);
+            hipStream_t sg = (gi > 0 && nspare && ((c == 0 && side_group0 && kernel == GroupKernel::cls) || (c == 2 && side_group2 && gi == 1))) ? spare[next_spare++ % nspare] : s;
             HIP_OK(hipEventRecord(b->ev_g[c][2 * gi], sg));
-            if (sl.stream && !a.block_profile && a.skip && a.bmw && a.rmw)
-                HIP_OK(b->union_stream ? (b->k > DS2I_HIP_MAX_K ? ds2i_launch_union_stream_bigk((int)sl.lists, &a, a.nslice, sg) : ds2i_launch_union_stream((int)sl.lists, &a, a.nslice, sg))
-                       : (base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ) ? ds2i_launch_and_rstream((int)sl.lists, base_op == DS2I_OP_AND_FREQ ? 1 : 0, &a, a.nslice, sg)
-                       : idx->kind == DS2I_BLOCK_MIXED ? ds2i_launch_ranked_stream_mixed((int)sl.lists, &a, a.nslice, sg)
-                       : b->k > DS2I_HIP_MAX_K ? ds2i_launch_ranked_stream_bigk((int)sl.lists, &a, a.nslice, sg) : ds2i_launch_ranked_stream((int)sl.lists, &a, a.nslice, sg));
-            else HIP_OK(ds2i_launch_batch(b->freq_stream ? (int)DS2I_OP_OR : (b->op & (0xFF | DS2I_OP_REFERENCE_ORDER)), c, &a, a.nslice, sg));
+            HIP_OK(launch_group(b, kernel, c, a, sg));
             HIP_OK(hipEventRecord(b->ev_g[c][2 * gi + 1], sg));
             if (sg != s) HIP_OK(hipStreamWaitEvent(sm, b->ev_g[c][2 * gi + 1], 0));
         }
@@ -1224,7 +1306,7 @@ int launch_batch(ds2i_hip_batch* b) {
         m.out_count = b->d_out.at<unsigned long long>(b->o_count);
         m.out_topk = b->d_out.at<float>(b->o_topk);
         m.out_topk_len = b->d_out.at<uint32_t>(b->o_topk_len);
-        m.out_freq_sum = b->freq_stream ? nullptr : b->d_out.at<unsigned long long>(b->o_freq_sum);
+        m.out_freq_sum = b->route.freq_stream ? nullptr : b->d_out.at<unsigned long long>(b->o_freq_sum);
         HIP_OK(ds2i_launch_merge(&m, std::min<unsigned>(b->nsplit, 4096u), sm));
     }
     if (b->use_seed && b->nsingle)
@@ -1249,7 +1331,6 @@ int finish_batch(ds2i_hip_batch* b, ds2i_hip_stats* stats) {
     }
     float ms = 0.f;
     HIP_OK(hipEventElapsedTime(&ms, b->ev_clear, b->ev_done));
-    b->total_ms = ms;
     for (int c = 0; c < NCLS; ++c) {
         b->cls_ms[c] = 0.f;
         if (b->ncls[c]) HIP_OK(hipEventElapsedTime(&b->cls_ms[c], b->ev_c0[c], b->ev_c1[c]));
@@ -1259,7 +1340,7 @@ int finish_batch(ds2i_hip_batch* b, ds2i_hip_stats* stats) {
     }
     if (b->instrument) HIP_OK(hipMemcpy(b->cls_stats, b->d_stats.p, NCLS * sizeof(Stats), hipMemcpyDeviceToHost));
     else std::memset(b->cls_stats, 0, sizeof(b->cls_stats));
-    if (b->instrument && b->d_clk.p && ds2i_knobs().unit_clock) { // diagnostic: where each class kernel's time goes
+    if (b->instrument && b->d_clk.p && b->idx->knobs.unit_clock) { // diagnostic: where each class kernel's time goes
         std::vector<unsigned long long> clk(2 * (size_t)b->nunits);
         HIP_OK(hipMemcpy(clk.data(), b->d_clk.p, 16 * (size_t)b->nunits, hipMemcpyDeviceToHost));
         for (int c = 0; c < NCLS; ++c) {
@@ -1281,7 +1362,7 @@ int finish_batch(ds2i_hip_batch* b, ds2i_hip_stats* stats) {
             std::fprintf(stderr, "ds2i unit clock: class %d: %zu units, span %.0f us, sum of unit times %.0f us (= %.0f waves busy on average), median unit %.1f us, p99 %.1f us\n",
                          c, durs.size(), (t1 - t0) * tick_us, busy * tick_us, busy / (double)(t1 - t0), durs[durs.size() / 2].first * tick_us,
                          durs[durs.size() * 99 / 100].first * tick_us);
-            if (b->union_stream && !b->vinfo.empty()) { // wand / maxscore / ranked_or: where the time goes by driving list (e = its exclusion lists)
+            if (b->route.union_stream && !b->vinfo.empty()) { // wand / maxscore / ranked_or: where the time goes by driving list (e = its exclusion lists)
                 double by_e[DS2I_HIP_MAX_TERMS + 1] = {}, blocks_e[DS2I_HIP_MAX_TERMS + 1] = {};
                 size_t n_e[DS2I_HIP_MAX_TERMS + 1] = {};
                 for (const auto& d : durs) {
@@ -1364,6 +1445,16 @@ struct ds2i_hip_pipeline {
 };
 
 namespace {
+// A launch that failed part-way may have kernels of this slot in flight (the seed pass, some class kernels) with no
+// completion event recorded: wait for the device before the caller can reuse or free the slot's buffers. The error
+// being reported is kept (the drain's own status is secondary).
+int drain_after_failure(ds2i_hip_batch* b, int rc) {
+    const std::string keep = ds2i_get_error();
+    (void)hipSetDevice(b->idx->device);
+    (void)hipDeviceSynchronize();
+    return ds2i_set_error(rc, keep.c_str());
+}
+
 // plan + upload + launch of one slot
 int pipeline_launch(ds2i_hip_pipeline* p, size_t slot, int op, uint32_t k, const uint32_t* terms, const uint32_t* offs, uint32_t nq) {
     HIP_OK(hipSetDevice(p->idx->device));
@@ -1377,12 +1468,7 @@ int pipeline_launch(ds2i_hip_pipeline* p, size_t slot, int op, uint32_t k, const
     if (rc) return rc; // (nothing enqueued yet)
     rc = upload_batch(b);
     if (!rc) rc = launch_batch(b);
-    if (rc) {
-        const std::string keep = ds2i_get_error();
-        (void)hipDeviceSynchronize(); // nothing of the slot is still running when the error is reported
-        return ds2i_set_error(rc, keep.c_str());
-    }
-    return DS2I_OK;
+    return rc ? drain_after_failure(b, rc) : DS2I_OK; // (nothing of the slot is still running when the error is reported)
 }
 } // namespace
 
@@ -1411,16 +1497,6 @@ int ds2i_hip_batch_prepare(ds2i_hip_index* idx, int op, uint32_t k, const uint32
     return DS2I_OK;
 }
 
-// A launch that failed part-way may have kernels of this slot in flight (the seed pass, some class kernels) with no
-// completion event recorded: wait for the device before the caller can reuse or free the slot's buffers. The error
-// being reported is kept (the drain's own status is secondary).
-static int drain_after_failure(ds2i_hip_batch* b, int rc) {
-    const std::string keep = ds2i_get_error();
-    (void)hipSetDevice(b->idx->device);
-    (void)hipDeviceSynchronize();
-    return ds2i_set_error(rc, keep.c_str());
-}
-
 int ds2i_hip_batch_run(ds2i_hip_batch* b, ds2i_hip_stats* stats) {
     if (!b) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_run: null batch");
     HIP_OK(hipSetDevice(b->idx->device));
@@ -1439,7 +1515,7 @@ int ds2i_hip_batch_enable_block_profile(ds2i_hip_batch* b) {
     const size_t bytes = 8 * (size_t)(idx->total_blocks ? idx->total_blocks : 1);
     HIP_OK(b->d_prof.reserve(bytes));
     HIP_OK(hipMemset(b->d_prof.p, 0, bytes));
-    if ((!b->sterms.empty() || b->freq_stream || b->k > DS2I_HIP_MAX_K) && !b->keep_offs.empty()) {
+    if ((!b->sterms.empty() || b->route.freq_stream || b->k > DS2I_HIP_MAX_K) && !b->keep_offs.empty()) {
         // queries answered by list streams have no work units and their kernels count nothing: plan the batch again without them, so
         // that every block decode of the batch shows in the profile (the input of the block_mixed optimiser). At k > 64 the stream
         // groups cannot fall back to the class kernels (launch_batch): those queries go to k_daat_long, the seed pass with them
@@ -1498,14 +1574,13 @@ int ds2i_hip_batch_class_groups(ds2i_hip_batch* b, int cls, ds2i_hip_group_stats
         out[g].kernel_ms = g < b->grp_ms[cls].size() ? b->grp_ms[cls][g] : 0.0;
         out[g].lists = sl.lists;
         out[g].units = sl.end - sl.begin;
-        out[g].pipelined_stream = (sl.stream && !b->profiled_run) ? 1 : 0;
-        uint32_t nq = 0, last = 0xFFFFFFFFu; // distinct queries of the group (its units are grouped by query only loosely: count by marking)
+        out[g].pipelined_stream = launched_kernel(b, sl) != GroupKernel::cls ? 1 : 0;
+        uint32_t nq = 0; // distinct queries of the group (its units are grouped by query only loosely: count by marking)
         std::vector<char> seen(b->nq ? b->nq : 1, 0);
         for (uint32_t i = sl.begin; i < sl.end; ++i) {
-            const uint32_t q = b->union_stream ? 0u : b->units[b->order[cls][i]].q;
+            const uint32_t q = b->route.union_stream ? 0u : b->units[b->order[cls][i]].q;
             if (q < seen.size() && !seen[q]) { seen[q] = 1; ++nq; }
         }
-        (void)last;
         out[g].queries = nq;
     }
     return DS2I_OK;

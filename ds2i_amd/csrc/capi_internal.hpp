@@ -11,6 +11,7 @@
 #include "../../include/ds2i_hip.h"
 #include "abi_structs.hpp"
 #include "capi_error.hpp"
+#include "knobs.hpp"
 
 #define HIP_OK(call)                                                                               \
     do {                                                                                           \
@@ -80,6 +81,7 @@ struct ds2i_hip_batch;
 
 struct ds2i_hip_index {
     int device = 0, kind = 0, num_cus = 256;
+    Ds2iKnobs knobs{};              // read once by the upload (ds2i_hip_index_open): they hold for this index and every batch planned on it
     int kind_on_disk = -1;          // the index kind the caller uploaded when it differs from `kind` (block_mixed transcoded at upload), else -1
     uint64_t size = 0, num_docs = 0;
     uint8_t* d_arena = nullptr;
@@ -113,7 +115,13 @@ struct ds2i_hip_index {
     bool plan_hints = true, plan_slots = true;
     uint64_t table_budget = 0;      // bytes the upload was asked to stay under (0 = no budget)
     std::vector<uint64_t> list_tail_off; // postings in the partial last blocks of all preceding lists
+    // What the kernel families need of the upload, named once (the planner's route, capi_batch.cpp: plan_route):
     bool d_skip_or_pef() const { return d_skip != nullptr || kind >= DS2I_OPT; } // what the streaming kernels walk the driving list by
+    // block_optpfor with its exception side slots, tail table and skip table: what the stream kernels decode a block through
+    // (build_side_tables allocates and frees d_xslots and d_tails together, and builds them only over a skip table)
+    bool side_tables() const { return kind == DS2I_BLOCK_OPTPFOR && d_xslots && d_tails && d_skip; }
+    // block-max weights and doc-id-range tables: what the pruned kernels bound a block and a doc-id range by
+    bool bound_tables() const { return d_bmw && d_rmw; }
     bool has_bitmaps = false;       // dense lists carry an exact bitmap behind their range-table levels
     std::vector<uint32_t> list_rmw_off64, list_rmw_shift;
     std::vector<float> list_bmw;    // per list: max over its blocks of d_bmw (device-computed)

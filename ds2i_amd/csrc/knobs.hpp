@@ -1,6 +1,7 @@
 // Every environment knob of libds2i_hip.so, read in ONE place (capi.cpp: ds2i_knobs). Twenty of them: what an upload builds, how a
-// batch is cut and which kernel family answers it, diagnostics. (Re-)read by every ds2i_hip_index_open; they hold for that index and for
-// the batches planned until the next upload. ds2i_hip_set_option(name, value) sets one without the environment.
+// batch is cut and which kernel family answers it, diagnostics. Read by each upload (ds2i_hip_index_open) into its index
+// (ds2i_hip_index::knobs): they hold for that index and every batch planned on it. ds2i_hip_set_option(name, value) sets one without
+// the environment, for the uploads after it.
 // (Rounds 2-5 accumulated fifty A/B switches; the ones whose alternative lost twice are gone together with what only they reached --
 // CHANGELOG.md has the measurements.)
 #pragma once
@@ -31,4 +32,3 @@ struct Ds2iKnobs {
     bool decode_general;      // DS2I_DECODE_GENERAL: ds2i_hip_decode_list through the on-disk decoders although side slots exist
     bool unit_clock;          // DS2I_UNIT_CLOCK: instrumented runs record every unit's start / end and print where a class's time went
 };
-Ds2iKnobs ds2i_knobs(); // (a copy: an upload on another thread may be re-reading them)

@@ -1223,6 +1223,43 @@ def test_alternative_paths_give_the_same_results(built_lib, knob):
     assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_knobs_hold_for_the_index_that_read_them(built_lib, images, queries):
+    """Each upload reads the knobs once (knobs.hpp) and they hold for that index and every batch planned on it: index A, opened with
+    the default knobs, still runs ranked_and through the stream launch groups after DS2I_NO_RANKED_STREAM is set and index B is
+    opened with it; B runs the class kernels. Both answer as the oracle does."""
+    imgs, wand = images
+    img = imgs["block_optpfor"]
+    qs = [q for q in queries if 2 <= len(set(q)) <= 8]
+    oidx = o.Index("block_optpfor", img, wand)
+    ocount, otopk, otlen, _, _ = oidx.query_batch("ranked_and", qs, k=10)
+
+    def check(count, topk, tlen):
+        assert np.array_equal(count, ocount) and np.array_equal(tlen, otlen)
+        for i in range(len(qs)):
+            np.testing.assert_allclose(topk[i, :tlen[i]], otopk[i, :otlen[i]], rtol=RTOL, err_msg=str(qs[i]))
+    a = d.Index("block_optpfor", img, wand)
+    b = None
+    try:
+        d.set_option("DS2I_NO_RANKED_STREAM", "1")
+        b = d.Index("block_optpfor", img, wand)
+        pipe = d.Pipeline(a, depth=2)
+        check(*pipe.wait(pipe.submit("ranked_and", qs, k=10)))
+        groups_a = [g for c in range(5) for g in pipe.class_groups(c)]
+        pipe.close()
+        bb = d.Batch(b, "ranked_and", qs, k=10)
+        bb.run()
+        check(*bb.fetch()[:3])
+        groups_b = [g for c in range(5) for g in bb.class_groups(c)]
+        bb.close()
+    finally:
+        d.set_option("DS2I_NO_RANKED_STREAM", None)
+        if b is not None:
+            b.close()
+        a.close()
+    assert any(g["pipelined_stream"] for g in groups_a)
+    assert groups_b and not any(g["pipelined_stream"] for g in groups_b)
+
+
 @pytest.mark.parametrize("extra", ["", "DS2I_UNIT_CAP=8", "DS2I_STREAM_NT_MAX=8", "DS2I_STREAM_NT_MAX=4"])
 def test_ranked_and_through_the_stream_pipeline(built_lib, extra):
     """The 2..16-term queries of a ranked_and batch on block_optpfor run k_ranked_stream<cap>, cap = the list capacity 2 | 4 | 6 | 8 | 16 of
