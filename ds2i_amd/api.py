@@ -17,6 +17,9 @@ BLOCK_CODECS = ["block_optpfor", "block_varint", "block_interpolative", "block_q
 OPS = {"and": 0, "and_freq": 1, "or": 2, "or_freq": 3, "ranked_and": 4, "wand": 5, "maxscore": 6, "ranked_or": 7}
 REFERENCE_ORDER = 0x100
 NO_COUNTERS = 0x200  # run the kernels compiled without the statistics counters (stats then carry kernel_ms only)
+# ranked operators: return the doc-id of every top-k score as well (score descending, equal scores by doc-id ascending; on a tie at
+# the k-th place the smaller doc-ids); such a batch reports no counters
+TOPK_DOCS = 0x400
 _RANKED = {4, 5, 6, 7}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -104,6 +107,9 @@ def lib():
         L.ds2i_hip_pipeline_destroy.restype = None
         L.ds2i_hip_pipeline_submit.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_uint32, u64p]
         L.ds2i_hip_pipeline_wait.argtypes = [vp, C.c_uint64, vp, vp, vp, C.POINTER(Stats)]
+        L.ds2i_hip_pipeline_wait_docs.argtypes = [vp, C.c_uint64, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.ds2i_hip_query_batch_docs.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, C.POINTER(Stats)]
+        L.ds2i_hip_batch_fetch_topk_docs.argtypes = [vp, vp]
         L.ds2i_hip_pipeline_set_instrumented.argtypes = [vp, C.c_int]
         L.ds2i_hip_pipeline_class_stats.argtypes = [vp, C.c_int, C.POINTER(Stats), u32p]
         L.ds2i_hip_batch_enable_block_profile.argtypes = [vp]
@@ -420,12 +426,20 @@ def _op(op):
     return OPS[op] if isinstance(op, str) else int(op)
 
 
+def _docs_op(op, with_docs):
+    """op with TOPK_DOCS added when with_docs; the unranked operators have no top-k to name (refused here, before the library)"""
+    o = _op(op) | (TOPK_DOCS if with_docs else 0)
+    if (o & TOPK_DOCS) and (o & 0xFF) not in _RANKED:
+        raise ValueError("doc-ids of the top-k exist for ranked operators only (ranked_and, wand, maxscore, ranked_or)")
+    return o
+
+
 class Batch:
     """A prepared query batch resident in HBM (ds2i_hip_batch_*)."""
 
-    def __init__(self, index, op, queries, k=10, want_matches=False, reference_order=False):
+    def __init__(self, index, op, queries, k=10, want_matches=False, reference_order=False, with_docs=False):
         self.index, self.nq, self.k = index, len(queries), k
-        self.op = _op(op) | (REFERENCE_ORDER if reference_order else 0)
+        self.op = _docs_op(op, with_docs) | (REFERENCE_ORDER if reference_order else 0)
         terms, offs = _flatten(queries)
         self._h = C.c_void_p()
         _check(lib().ds2i_hip_batch_prepare(index._h, self.op, k, _ptr(terms), _ptr(offs), self.nq,
@@ -478,6 +492,12 @@ class Batch:
         _check(lib().ds2i_hip_batch_fetch(self._h, _ptr(count), _ptr(topk), _ptr(tlen), _ptr(fsum)))
         return count[:self.nq], topk[:self.nq], tlen[:self.nq], fsum[:self.nq]
 
+    def fetch_topk_docs(self):
+        """uint32[nq, k]: the doc-id of every top-k score of the last run (batches prepared with_docs; 0xFFFFFFFF past tlen)"""
+        docs = np.full((max(self.nq, 1), self.k), 0xFFFFFFFF, dtype=np.uint32)
+        _check(lib().ds2i_hip_batch_fetch_topk_docs(self._h, _ptr(docs)))
+        return docs[:self.nq]
+
     def fetch_matches(self, counts):
         tot = C.c_uint64()
         _check(lib().ds2i_hip_batch_match_total(self._h, C.byref(tot)))
@@ -512,12 +532,14 @@ class Pipeline:
     def set_instrumented(self, on):
         _check(lib().ds2i_hip_pipeline_set_instrumented(self._h, 1 if on else 0))
 
-    def submit(self, op, queries, k=10):
-        """queries: list of term lists, or an already flattened (terms uint32[], offsets uint32[nq+1]) pair."""
+    def submit(self, op, queries, k=10, with_docs=False):
+        """queries: list of term lists, or an already flattened (terms uint32[], offsets uint32[nq+1]) pair.
+        with_docs: the ticket also returns the doc-ids of the top-k (wait_docs)."""
+        o = _docs_op(op, with_docs)
         terms, offs = queries if isinstance(queries, tuple) else _flatten(queries)
         nq = len(offs) - 1
         t = C.c_uint64()
-        _check(lib().ds2i_hip_pipeline_submit(self._h, _op(op), k, _ptr(terms), _ptr(offs), nq, C.byref(t)))
+        _check(lib().ds2i_hip_pipeline_submit(self._h, o, k, _ptr(terms), _ptr(offs), nq, C.byref(t)))
         self._meta[t.value] = (nq, k if (_op(op) & 0xFF) in _RANKED else 1)
         return t.value
 
@@ -529,6 +551,19 @@ class Pipeline:
         st = Stats()
         _check(lib().ds2i_hip_pipeline_wait(self._h, ticket, _ptr(count), _ptr(topk), _ptr(tlen), C.byref(st) if stats else None))
         return (count[:nq], topk[:nq], tlen[:nq], st) if stats else (count[:nq], topk[:nq], tlen[:nq])
+
+    def wait_docs(self, ticket, stats=False):
+        """wait() for a ticket submitted with_docs -> (count, topk, docs uint32[nq, k], tlen[, stats])"""
+        nq, k = self._meta.get(ticket, (0, 1))
+        count = np.zeros(max(nq, 1), dtype=np.uint64)
+        topk = np.full((max(nq, 1), k), -np.inf, dtype=np.float32)
+        docs = np.full((max(nq, 1), k), 0xFFFFFFFF, dtype=np.uint32)
+        tlen = np.zeros(max(nq, 1), dtype=np.uint32)
+        st = Stats()
+        _check(lib().ds2i_hip_pipeline_wait_docs(self._h, ticket, _ptr(count), _ptr(topk), _ptr(docs), _ptr(tlen), C.byref(st) if stats else None))
+        self._meta.pop(ticket, None)  # (a refused wait leaves the ticket in flight)
+        r = (count[:nq], topk[:nq], docs[:nq], tlen[:nq])
+        return r + (st,) if stats else r
 
     def class_stats(self, cls):
         """(Stats, queries) of kernel class `cls` for the ticket collected last."""
@@ -634,6 +669,20 @@ class Index:
                                           _ptr(tlen), C.byref(st)))
         return count[:nq], topk[:nq], tlen[:nq], st
 
+    def query_batch_docs(self, op, queries, k=10):
+        """query_batch with the doc-ids of the top-k (ranked operators) -> (count, topk, docs uint32[nq, k], tlen, stats)"""
+        o = _docs_op(op, True)
+        terms, offs = queries if isinstance(queries, tuple) else _flatten(queries)
+        nq = len(offs) - 1
+        count = np.zeros(max(nq, 1), dtype=np.uint64)
+        topk = np.full((max(nq, 1), max(k, 1)), -np.inf, dtype=np.float32)
+        docs = np.full((max(nq, 1), max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        tlen = np.zeros(max(nq, 1), dtype=np.uint32)
+        st = Stats()
+        _check(lib().ds2i_hip_query_batch_docs(self._h, o, k, _ptr(terms), _ptr(offs), nq, _ptr(count), _ptr(topk), _ptr(docs),
+                                               _ptr(tlen), C.byref(st)))
+        return count[:nq], topk[:nq], docs[:nq], tlen[:nq], st
+
     def close(self):
         if self._h:
             lib().ds2i_hip_index_close(self._h)
@@ -651,16 +700,24 @@ class _query_op:
     op = None
     ranked = False
 
-    def __init__(self, wdata=None, k=10):
+    def __init__(self, wdata=None, k=10, with_docs=False):
+        if with_docs and not self.ranked:
+            raise ValueError("doc-ids of the top-k exist for ranked operators only (ranked_and, wand, maxscore, ranked_or)")
         self.k = k
+        self.with_docs = with_docs
         self._topk = []
+        self._topk_docs = []
 
     def __call__(self, index, terms):
         """uint64_t operator()(Index const&, term_id_vec) -- a batch of one query."""
         return int(self.batch(index, [list(terms)])[0])
 
     def batch(self, index, queries):
-        count, topk, tlen, _ = index.query_batch(self.op, queries, self.k)
+        if self.with_docs:
+            count, topk, docs, tlen, _ = index.query_batch_docs(self.op, queries, self.k)
+            self._topk_docs = [docs[i, :tlen[i]].copy() for i in range(len(queries))]
+        else:
+            count, topk, tlen, _ = index.query_batch(self.op, queries, self.k)
         if self.ranked:
             self._topk = [topk[i, :tlen[i]].copy() for i in range(len(queries))]
         return count
@@ -668,16 +725,22 @@ class _query_op:
     def topk(self, i=-1):
         return self._topk[i]
 
+    def topk_docs(self, i=-1):
+        """doc-ids of topk(i), same order (operators constructed with_docs)"""
+        if not self.with_docs:
+            raise ValueError("the operator was constructed without with_docs")
+        return self._topk_docs[i]
+
 
 class and_query(_query_op):
-    def __init__(self, with_freqs=False):
-        super().__init__()
+    def __init__(self, with_freqs=False, with_docs=False):
+        super().__init__(with_docs=with_docs)
         self.op = "and_freq" if with_freqs else "and"
 
 
 class or_query(_query_op):
-    def __init__(self, with_freqs=False):
-        super().__init__()
+    def __init__(self, with_freqs=False, with_docs=False):
+        super().__init__(with_docs=with_docs)
         self.op = "or_freq" if with_freqs else "or"
 
 

@@ -135,6 +135,10 @@ struct BatchArgs {
     uint32_t long_stride;        // dwords of scratch per unit
     uint32_t dyn_lists;          // union kernels: list slots of decoded blocks in dynamic LDS (>= the longest query of the launch)
     Stats* stats;
+    // DS2I_OP_TOPK_DOCS (the *_docs kernels only): the doc-id of every top-k score, same layout as out_topk / unit_topk, 0xFFFFFFFF
+    // past the row's length (the seed pass's ids reach the result through k_copy_seed_docs, which takes its own arguments)
+    uint32_t* out_topk_docs;
+    uint32_t* unit_topk_docs;
 };
 
 // upload-time pass computing bmw[] (k_block_max_weights): one wave per item = <=64 consecutive blocks of one list
@@ -257,6 +261,8 @@ struct MergeArgs {
     float* out_topk;
     uint32_t* out_topk_len;
     unsigned long long* out_freq_sum;
+    const uint32_t* unit_topk_docs; // DS2I_OP_TOPK_DOCS (k_merge_docs / k_merge_big_docs): the parts' doc-ids, and the merged ones
+    uint32_t* out_topk_docs;
 };
 
 struct DecodeArgs {

@@ -45,6 +45,17 @@ hipError_t ds2i_launch_union_stream(int nt, const void* args, unsigned grid, hip
 hipError_t ds2i_launch_union_stream_bigk(int cap, const void* args, unsigned grid, hipStream_t s); // union_stream.hip compiled with -DDS2I_US_BIGK_TU (k > 64)
 hipError_t ds2i_launch_ranked_stream_mixed(int nt, const void* args, unsigned grid, hipStream_t s); // ranked_stream_mixed.hip
 hipError_t ds2i_launch_merge(const void* args, unsigned grid, hipStream_t s);
+// DS2I_OP_TOPK_DOCS: the *_docs instantiations (the *_docs units of build.py; same arguments, BatchArgs / MergeArgs docs fields set)
+hipError_t ds2i_launch_batch_docs(int op, int tmax_class, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_mixed_docs(int nt, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_union_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_union_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_merge_docs(const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_copy_seed_docs(const uint32_t* queries, uint32_t n, uint32_t k, const float* seed_topk, const uint32_t* seed_docs,
+                                      const uint32_t* seed_len, const unsigned long long* seed_count, float* out_topk, uint32_t* out_docs,
+                                      uint32_t* out_len, unsigned long long* out_count, hipStream_t s);
 hipError_t ds2i_launch_copy_seed(const uint32_t* queries, uint32_t n, uint32_t k, const float* seed_topk, const uint32_t* seed_len,
                                  const unsigned long long* seed_count, float* out_topk, uint32_t* out_len,
                                  unsigned long long* out_count, hipStream_t s);
@@ -178,6 +189,9 @@ struct Route {
     uint32_t rs_nt = 0, rs_classes = 0;
     bool exact = false; // ... one launch group per list count (block_mixed native) instead of one per list capacity
     bool seeded = false; // a ranked_and seed pass runs first (plan_seed)
+    // DS2I_OP_TOPK_DOCS: every kernel of the batch is the *_docs instantiation of the one chosen above (the choice itself does not
+    // look at the flag), the seed pass included; the result block gains the doc-ids (o_topk_docs)
+    bool docs = false;
     bool goes_long(size_t nterms) const {
         if (!bigk) return nterms > DS2I_HIP_MAX_TERMS;
         if (bigk_stream) return !(nterms >= 1 && nterms <= stream_nt_max);
@@ -236,9 +250,9 @@ struct ds2i_hip_batch {
     size_t o_qterms = 0, o_qoff = 0, o_units = 0, o_q_unit_off = 0, o_split = 0, o_single = 0, o_hslot = 0, o_order[NCLS] = {}, o_urec[4] = {}, o_qterm_q = 0, o_sterms = 0,
            o_match_off = 0, up_bytes = 0;
     // ---- one result block (d_out -> pinned mirror h_out)
-    size_t o_count = 0, o_topk = 0, o_topk_len = 0, o_freq_sum = 0, out_bytes = 0;
+    size_t o_count = 0, o_topk = 0, o_topk_len = 0, o_freq_sum = 0, o_topk_docs = 0, out_bytes = 0;
     // ---- device-only scratch: per-unit partial results of split queries + the shared floors
-    size_t o_unit_count = 0, o_unit_topk = 0, o_unit_topk_len = 0, o_unit_freq_sum = 0, o_qfloor = 0, o_qfloorw = 0, scr_bytes = 0;
+    size_t o_unit_count = 0, o_unit_topk = 0, o_unit_topk_len = 0, o_unit_freq_sum = 0, o_unit_topk_docs = 0, o_qfloor = 0, o_qfloorw = 0, scr_bytes = 0;
     DevBuf d_up, d_out, d_scr, d_matches, d_prof, d_stats, d_long, d_clk;
     // union kernels (k_disjunctive) keep their decoded blocks in dynamic LDS sized per launch: a class's units are grouped
     // by the list count of their query and every group is launched with just that many list slots
@@ -298,9 +312,12 @@ static int plan_route(ds2i_hip_batch* b, int op, uint32_t k, uint32_t nq, int wa
     const ds2i_hip_index* idx = b->idx;
     const Ds2iKnobs& kn = idx->knobs;
     const int base_op = op & 0xFF;
-    if (base_op < DS2I_OP_AND || base_op > DS2I_OP_RANKED_OR || (op & ~(0xFF | DS2I_OP_REFERENCE_ORDER | DS2I_OP_NO_COUNTERS)))
+    if (base_op < DS2I_OP_AND || base_op > DS2I_OP_RANKED_OR || (op & ~(0xFF | DS2I_OP_REFERENCE_ORDER | DS2I_OP_NO_COUNTERS | DS2I_OP_TOPK_DOCS)))
         return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_prepare: unknown query operator");
+    if ((op & DS2I_OP_TOPK_DOCS) && base_op < DS2I_OP_RANKED_AND)
+        return ds2i_set_error(DS2I_EINVAL, "DS2I_OP_TOPK_DOCS: and / and_freq / or / or_freq return no top-k");
     Route r;
+    r.docs = (op & DS2I_OP_TOPK_DOCS) != 0;
     r.base_op = base_op;
     r.conj = base_op == DS2I_OP_AND || base_op == DS2I_OP_AND_FREQ || base_op == DS2I_OP_RANKED_AND;
     r.ranked = base_op >= DS2I_OP_RANKED_AND;
@@ -914,12 +931,14 @@ static void lay_out(ds2i_hip_batch* b) {
     b->o_topk = place(4 * nq1 * k);
     b->o_topk_len = place(4 * nq1);
     b->o_freq_sum = place(8 * nq1);
+    b->o_topk_docs = place(r.docs ? 4 * nq1 * k : 0); // (DS2I_OP_TOPK_DOCS; last, so the scores-only layout is unchanged)
     b->out_bytes = o;
     o = 0;
     b->o_unit_count = place(8 * nu1);
     b->o_unit_topk = place(4 * nu1 * k);
     b->o_unit_topk_len = place(4 * nu1);
     b->o_unit_freq_sum = place(8 * nu1);
+    b->o_unit_topk_docs = place(r.docs ? 4 * nu1 * k : 0);
     // ranked_and / wand / maxscore / ranked_or: a 256-bucket score histogram per split query (kernels.hip, ScoreHist)
     const bool disj_ranked = r.base_op == DS2I_OP_WAND || r.base_op == DS2I_OP_MAXSCORE || r.base_op == DS2I_OP_RANKED_OR;
     const bool hist = !r.reference && b->nsplit && ((r.base_op == DS2I_OP_RANKED_AND && b->idx->d_bmw) || disj_ranked);
@@ -970,7 +989,8 @@ static int plan_seed(ds2i_hip_batch* b, const uint32_t* terms, const uint32_t* q
     }
     b->seed->pool_batches = b->pool_batches;
     b->seed->no_bigk_streams = b->no_bigk_streams;
-    return plan_batch(b->seed, DS2I_OP_RANKED_AND, b->k, sterms.data(), soffs.data(), nq, 0);
+    // (a docs batch's seed runs with doc-ids too: it answers the one-term queries, k_copy_seed_docs)
+    return plan_batch(b->seed, DS2I_OP_RANKED_AND | (b->route.docs ? (int)DS2I_OP_TOPK_DOCS : 0), b->k, sterms.data(), soffs.data(), nq, 0);
 }
 
 // (the plan's vectors grow with the batch: an allocation failure -- on the caller's thread or on a pool thread, see PlanPool -- is
@@ -1066,6 +1086,18 @@ GroupKernel launched_kernel(const ds2i_hip_batch* b, const ds2i_hip_batch::SubLa
 // one launch group's kernel (a.order / a.urec / a.nslice / a.dyn_lists already point at the group)
 hipError_t launch_group(const ds2i_hip_batch* b, GroupKernel kernel, int c, const BatchArgs& a, hipStream_t s) {
     const int lists = (int)a.dyn_lists;
+    if (b->route.docs) {
+        switch (kernel) {
+        case GroupKernel::ranked_stream: return ds2i_launch_ranked_stream_docs(lists, &a, a.nslice, s);
+        case GroupKernel::ranked_stream_bigk: return ds2i_launch_ranked_stream_bigk_docs(lists, &a, a.nslice, s);
+        case GroupKernel::ranked_stream_mixed: return ds2i_launch_ranked_stream_mixed_docs(lists, &a, a.nslice, s);
+        case GroupKernel::union_stream: return ds2i_launch_union_stream_docs(lists, &a, a.nslice, s);
+        case GroupKernel::union_stream_bigk: return ds2i_launch_union_stream_bigk_docs(lists, &a, a.nslice, s);
+        case GroupKernel::and_rstream: return hipErrorInvalidValue; // (plan_route: the flag is for ranked operators)
+        case GroupKernel::cls: break;
+        }
+        return ds2i_launch_batch_docs(b->op & (0xFF | DS2I_OP_REFERENCE_ORDER), c, &a, a.nslice, s);
+    }
     switch (kernel) {
     case GroupKernel::ranked_stream: return ds2i_launch_ranked_stream(lists, &a, a.nslice, s);
     case GroupKernel::ranked_stream_bigk: return ds2i_launch_ranked_stream_bigk(lists, &a, a.nslice, s);
@@ -1174,6 +1206,10 @@ BatchArgs batch_args(const ds2i_hip_batch* b, bool seed_feeds) {
     a.tails = idx->d_tails;
     a.long_scratch = (uint32_t*)b->d_long.p;
     a.long_stride = (uint32_t)((size_t)b->long_terms * (256 + ds2i_meta_words() + 2) + 16);
+    if (b->route.docs) {
+        a.out_topk_docs = b->d_out.at<uint32_t>(b->o_topk_docs);
+        a.unit_topk_docs = b->d_scr.at<uint32_t>(b->o_unit_topk_docs);
+    }
     return a;
 }
 
@@ -1203,6 +1239,8 @@ int launch_batch(ds2i_hip_batch* b) {
     hipStream_t sm = idx->s_merge, su = idx->s_up;
     HIP_OK(hipMemsetAsync(b->d_scr.p, 0, b->scr_bytes, su));
     HIP_OK(hipMemsetAsync(b->d_out.p, 0, b->out_bytes, su));
+    // (DS2I_OP_TOPK_DOCS: a row no kernel writes -- an empty query -- reads as padding, 0xFFFFFFFF, like the entries past a row's length)
+    if (b->route.docs) HIP_OK(hipMemsetAsync(b->d_out.at<uint8_t>(b->o_topk_docs), 0xFF, 4 * (size_t)b->nq * b->k, su));
     if (b->instrument) HIP_OK(hipMemsetAsync(b->d_stats.p, 0, NCLS * sizeof(Stats), su));
     HIP_OK(hipEventRecord(b->ev_clear, su)); // also orders this launch after the batch's upload (same stream)
     // Launch order of the class kernels (they overlap on separate streams either way; measured on the GOV2-scale
@@ -1266,7 +1304,7 @@ int launch_batch(ds2i_hip_batch* b) {
         hipStream_t s = cstreams[c];
         HIP_OK(hipEventRecord(b->ev_c0[c], s));
         BatchArgs a = args;
-        a.stats = b->instrument ? b->d_stats.at<Stats>(0) + c : nullptr;
+        a.stats = (b->instrument && !b->route.docs) ? b->d_stats.at<Stats>(0) + c : nullptr; // (the docs kernels are built without counters)
         const uint32_t* order_base = b->d_up.at<uint32_t>(b->o_order[c]);
         const ds2i_dev::UnitRec* urec_base = c < b->route.urec_classes() ? b->d_up.at<ds2i_dev::UnitRec>(b->o_urec[c]) : nullptr;
         for (const auto& sl : b->sub[c]) { // one launch per group of the class (a single group for everything but the union kernels)
@@ -1307,9 +1345,21 @@ int launch_batch(ds2i_hip_batch* b) {
         m.out_topk = b->d_out.at<float>(b->o_topk);
         m.out_topk_len = b->d_out.at<uint32_t>(b->o_topk_len);
         m.out_freq_sum = b->route.freq_stream ? nullptr : b->d_out.at<unsigned long long>(b->o_freq_sum);
-        HIP_OK(ds2i_launch_merge(&m, std::min<unsigned>(b->nsplit, 4096u), sm));
+        if (b->route.docs) {
+            m.unit_topk_docs = b->d_scr.at<uint32_t>(b->o_unit_topk_docs);
+            m.out_topk_docs = b->d_out.at<uint32_t>(b->o_topk_docs);
+            HIP_OK(ds2i_launch_merge_docs(&m, std::min<unsigned>(b->nsplit, 4096u), sm));
+        } else {
+            HIP_OK(ds2i_launch_merge(&m, std::min<unsigned>(b->nsplit, 4096u), sm));
+        }
     }
-    if (b->use_seed && b->nsingle)
+    if (b->use_seed && b->nsingle && b->route.docs)
+        HIP_OK(ds2i_launch_copy_seed_docs(b->d_up.at<uint32_t>(b->o_single), b->nsingle, b->k, b->seed->d_out.at<float>(b->seed->o_topk),
+                                          b->seed->d_out.at<uint32_t>(b->seed->o_topk_docs), b->seed->d_out.at<uint32_t>(b->seed->o_topk_len),
+                                          b->seed->d_out.at<unsigned long long>(b->seed->o_count), b->d_out.at<float>(b->o_topk),
+                                          b->d_out.at<uint32_t>(b->o_topk_docs), b->d_out.at<uint32_t>(b->o_topk_len),
+                                          b->d_out.at<unsigned long long>(b->o_count), sm));
+    else if (b->use_seed && b->nsingle)
         HIP_OK(ds2i_launch_copy_seed(b->d_up.at<uint32_t>(b->o_single), b->nsingle, b->k, b->seed->d_out.at<float>(b->seed->o_topk),
                                      b->seed->d_out.at<uint32_t>(b->seed->o_topk_len),
                                      b->seed->d_out.at<unsigned long long>(b->seed->o_count), b->d_out.at<float>(b->o_topk),
@@ -1411,6 +1461,10 @@ void copy_results(const ds2i_hip_batch* b, uint64_t* out_count, float* out_topk,
     if (out_topk_len) std::memcpy(out_topk_len, h + b->o_topk_len, 4 * nq);
     if (out_freq_sum) std::memcpy(out_freq_sum, h + b->o_freq_sum, 8 * nq);
 }
+// ... and the doc-ids of a DS2I_OP_TOPK_DOCS batch
+void copy_topk_docs(const ds2i_hip_batch* b, uint32_t* out_docs) {
+    if (b->nq && out_docs && b->route.docs) std::memcpy(out_docs, (const uint8_t*)b->h_out.p + b->o_topk_docs, 4 * (size_t)b->nq * b->k);
+}
 
 } // namespace
 
@@ -1511,6 +1565,7 @@ int ds2i_hip_batch_enable_block_profile(ds2i_hip_batch* b) {
     if (!b) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_enable_block_profile: null batch");
     ds2i_hip_index* idx = b->idx;
     if (idx->kind >= DS2I_OPT) return ds2i_set_error(DS2I_EINVAL, "the block access profile exists for block indexes only");
+    if (b->route.docs) return ds2i_set_error(DS2I_EINVAL, "DS2I_OP_TOPK_DOCS batches run without counters: no block access profile");
     HIP_OK(hipSetDevice(idx->device));
     const size_t bytes = 8 * (size_t)(idx->total_blocks ? idx->total_blocks : 1);
     HIP_OK(b->d_prof.reserve(bytes));
@@ -1603,6 +1658,16 @@ int ds2i_hip_batch_fetch(ds2i_hip_batch* b, uint64_t* out_count, float* out_topk
     return DS2I_OK;
 }
 
+int ds2i_hip_batch_fetch_topk_docs(ds2i_hip_batch* b, uint32_t* out_docs) {
+    if (!b || !out_docs) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_fetch_topk_docs: null argument");
+    if (!b->route.docs) return ds2i_set_error(DS2I_EINVAL, "batch was prepared without DS2I_OP_TOPK_DOCS");
+    if (!b->launched) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_fetch_topk_docs: the batch has not been run");
+    HIP_OK(hipSetDevice(b->idx->device));
+    HIP_OK(hipEventSynchronize(b->ev_done));
+    copy_topk_docs(b, out_docs);
+    return DS2I_OK;
+}
+
 int ds2i_hip_batch_match_total(ds2i_hip_batch* b, uint64_t* total) {
     if (!b || !total) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_batch_match_total: null argument");
     *total = b->want_matches ? b->match_off[b->nq] : 0; // capacity: 128 per block of each query's shortest list
@@ -1641,10 +1706,9 @@ int ds2i_hip_batch_fetch_matches(ds2i_hip_batch* b, uint64_t* match_offsets, uin
 
 // One-shot form: the slot (pinned staging, device blocks, events) is cached in the index handle, so repeated calls
 // -- the per-query latency loop of the `queries` driver, the Python op(index, terms) form -- allocate nothing.
-int ds2i_hip_query_batch(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t* terms,
-                         const uint32_t* query_offsets, uint32_t nq, uint64_t* out_count, float* out_topk,
-                         uint32_t* out_topk_len, ds2i_hip_stats* stats) {
-    if (!idx) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_query_batch: null index");
+namespace {
+int query_batch_oneshot(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq,
+                        uint64_t* out_count, float* out_topk, uint32_t* out_topk_docs, uint32_t* out_topk_len, ds2i_hip_stats* stats) {
     HIP_OK(hipSetDevice(idx->device));
     if (!idx->oneshot) {
         idx->oneshot = new ds2i_hip_batch;
@@ -1659,7 +1723,24 @@ int ds2i_hip_query_batch(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t
     if (!rc) rc = launch_batch(b);
     if (!rc) rc = finish_batch(b, stats);
     if (!rc) copy_results(b, out_count, out_topk, out_topk_len, nullptr);
+    if (!rc) copy_topk_docs(b, out_topk_docs);
     return rc;
+}
+} // namespace
+
+int ds2i_hip_query_batch(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t* terms,
+                         const uint32_t* query_offsets, uint32_t nq, uint64_t* out_count, float* out_topk,
+                         uint32_t* out_topk_len, ds2i_hip_stats* stats) {
+    if (!idx) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_query_batch: null index");
+    if (op & DS2I_OP_TOPK_DOCS) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_query_batch has no doc-id output: use ds2i_hip_query_batch_docs");
+    return query_batch_oneshot(idx, op, k, terms, query_offsets, nq, out_count, out_topk, nullptr, out_topk_len, stats);
+}
+
+int ds2i_hip_query_batch_docs(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets, uint32_t nq,
+                              uint64_t* out_count, float* out_topk, uint32_t* out_topk_docs, uint32_t* out_topk_len, ds2i_hip_stats* stats) {
+    if (!idx) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_query_batch_docs: null index");
+    if (!(op & DS2I_OP_TOPK_DOCS)) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_query_batch_docs: op lacks DS2I_OP_TOPK_DOCS");
+    return query_batch_oneshot(idx, op, k, terms, query_offsets, nq, out_count, out_topk, out_topk_docs, out_topk_len, stats);
 }
 
 // ---------------------------------------------------------------- pipelined form
@@ -1700,20 +1781,28 @@ int ds2i_hip_pipeline_submit(ds2i_hip_pipeline* p, int op, uint32_t k, const uin
     return DS2I_OK;
 }
 
-int ds2i_hip_pipeline_wait(ds2i_hip_pipeline* p, uint64_t ticket, uint64_t* out_count, float* out_topk, uint32_t* out_topk_len,
-                           ds2i_hip_stats* stats) {
+int ds2i_hip_pipeline_wait_docs(ds2i_hip_pipeline* p, uint64_t ticket, uint64_t* out_count, float* out_topk, uint32_t* out_topk_docs,
+                                uint32_t* out_topk_len, ds2i_hip_stats* stats) {
     if (!p) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_pipeline_wait: null pipeline");
     const size_t slot = (size_t)(ticket % p->slots.size());
     if (!p->busy[slot] || p->slot_ticket[slot] != ticket)
         return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_pipeline_wait: unknown or already collected ticket");
-    HIP_OK(hipSetDevice(p->idx->device));
     ds2i_hip_batch* b = p->slots[slot];
+    if (out_topk_docs && !b->route.docs) // (before anything is collected: the ticket stays in flight)
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_pipeline_wait_docs: the ticket was submitted without DS2I_OP_TOPK_DOCS");
+    HIP_OK(hipSetDevice(p->idx->device));
     int rc = finish_batch(b, stats);
     p->busy[slot] = 0;
     if (rc) return rc;
     p->last_waited = b;
     copy_results(b, out_count, out_topk, out_topk_len, nullptr);
+    copy_topk_docs(b, out_topk_docs);
     return DS2I_OK;
+}
+
+int ds2i_hip_pipeline_wait(ds2i_hip_pipeline* p, uint64_t ticket, uint64_t* out_count, float* out_topk, uint32_t* out_topk_len,
+                           ds2i_hip_stats* stats) {
+    return ds2i_hip_pipeline_wait_docs(p, ticket, out_count, out_topk, nullptr, out_topk_len, stats);
 }
 
 // per kernel class of the ticket collected last (hipEvent duration of the class kernel, counters when instrumented)

@@ -831,4 +831,122 @@ struct TopKBig {
     }
 };
 
+// ---- top-k (score, doc-id) pairs (DS2I_OP_TOPK_DOCS): the same heaps with a doc-id beside every score, in the same lane / register.
+// The order is total: (score descending, doc-id ascending), and the heap keeps the k largest pairs under it whatever the arrival order
+// -- on a tie at the k-th place the smaller doc-ids stay. Every kernel prunes through would_enter() / thr with a STRICT test
+// (`bound > thr`); here thr is the float just below the k-th score, so each such test admits a bound EQUAL to the k-th score: a
+// document that ties the k-th score is never pruned, whatever order the kernel meets documents in, and insert() settles the tie by
+// doc-id. (The floors -- seed, shared histogram, q_floor -- are lower bounds of the final k-th score and are tested with >=.)
+// thr_doc is the doc-id of the k-th pair (wave-uniform, 0xFFFFFFFF until the heap is full).
+DS2I_DEV float float_below(float x) { // the largest float < x (x finite or +inf; -inf stays)
+    if (x == -__builtin_inff()) return x;
+    if (x == 0.f) return -__uint_as_float(1u);
+    const uint32_t b = __float_as_uint(x);
+    return __uint_as_float(x > 0.f ? b - 1u : b + 1u);
+}
+struct TopKD {
+    float v;      // per lane
+    uint32_t d;   // per lane: the doc-id of v (0xFFFFFFFF past n)
+    uint32_t n;
+    uint32_t k;
+    float floor;
+    float thr;    // below(k-th score), or -inf until the heap is full (see TopK::thr on divergent code)
+    uint32_t thr_doc;
+    DS2I_DEV void init(uint32_t k_) {
+        v = -__builtin_inff(); d = 0xFFFFFFFFu; n = 0; k = k_; floor = -__builtin_inff(); thr = -__builtin_inff(); thr_doc = 0xFFFFFFFFu;
+    }
+    DS2I_DEV float threshold() const { return thr; }
+    DS2I_DEV bool would_enter(float s) const { return s >= floor && (n < k || s > thr); }
+    DS2I_DEV bool insert(float s, uint32_t doc) { // s, doc wave-uniform; wave-uniform control flow only
+        if (!would_enter(s)) return false;
+        const uint32_t lane = lane_id();
+        const uint64_t before = ballot(lane < n && (v > s || (v == s && d < doc)));
+        const uint32_t p = (uint32_t)__builtin_popcountll(before);
+        if (p >= k) return false; // ties the k-th score with a larger doc-id
+        const float up = __shfl_up(v, 1);
+        const uint32_t upd = __shfl_up(d, 1);
+        v = (lane < p) ? v : (lane == p) ? s : up;
+        d = (lane < p) ? d : (lane == p) ? doc : upd;
+        if (n < k) ++n;
+        if (lane >= k) { v = -__builtin_inff(); d = 0xFFFFFFFFu; }
+        if (n == k) {
+            thr = float_below(__uint_as_float(bcast(__float_as_uint(v), k - 1)));
+            thr_doc = bcast(d, k - 1);
+        }
+        return true;
+    }
+};
+template <int NK>
+struct TopKBigD {
+    float v[NK];
+    uint32_t d[NK];
+    uint32_t n, k;
+    float floor;
+    float thr; // as TopKD::thr
+    uint32_t thr_doc;
+    DS2I_DEV void init(uint32_t k_) {
+#pragma unroll
+        for (int r = 0; r < NK; ++r) { v[r] = -__builtin_inff(); d[r] = 0xFFFFFFFFu; }
+        n = 0;
+        k = k_;
+        floor = -__builtin_inff();
+        thr = -__builtin_inff();
+        thr_doc = 0xFFFFFFFFu;
+    }
+    DS2I_DEV float threshold() const { return thr; }
+    DS2I_DEV bool would_enter(float s) const { return s >= floor && (n < k || s > thr); }
+    DS2I_DEV bool insert(float s, uint32_t doc) { // s, doc wave-uniform
+        if (!would_enter(s)) return false;
+        const uint32_t lane = lane_id();
+        uint32_t p = 0; // pairs ahead of (s, doc) keep their place
+#pragma unroll
+        for (int r = 0; r < NK; ++r)
+            p += (uint32_t)__builtin_popcountll(ballot((uint32_t)r * 64u + lane < n && (v[r] > s || (v[r] == s && d[r] < doc))));
+        if (p >= k) return false;
+#pragma unroll
+        for (int r = NK - 1; r >= 0; --r) { // descending: register r - 1 still holds its old values when r takes its carry
+            const float carry = r ? __uint_as_float(bcast(__float_as_uint(v[r > 0 ? r - 1 : 0]), 63)) : 0.f;
+            const uint32_t carryd = r ? bcast(d[r > 0 ? r - 1 : 0], 63) : 0u;
+            float up = __shfl_up(v[r], 1);
+            uint32_t upd = __shfl_up(d[r], 1);
+            if (lane == 0) { up = carry; upd = carryd; }
+            const uint32_t i = (uint32_t)r * 64u + lane;
+            float nv = (i < p) ? v[r] : (i == p) ? s : up;
+            uint32_t nd = (i < p) ? d[r] : (i == p) ? doc : upd;
+            if (i >= k) { nv = -__builtin_inff(); nd = 0xFFFFFFFFu; }
+            v[r] = nv;
+            d[r] = nd;
+        }
+        if (n < k) ++n;
+        if (n == k) {
+            float t = 0.f;
+            uint32_t td = 0u;
+#pragma unroll
+            for (int r = 0; r < NK; ++r)
+                if ((uint32_t)r == ((k - 1) >> 6)) { t = __uint_as_float(bcast(__float_as_uint(v[r]), (k - 1) & 63u)); td = bcast(d[r], (k - 1) & 63u); }
+            thr = float_below(t);
+            thr_doc = td;
+        }
+        return true;
+    }
+};
+
+// One kernel source, two builds. A translation unit compiled with -DDS2I_DOCS_TU (ds2i_amd/build.py, the *_docs units) holds the
+// doc-id instantiations of the ranked kernels: RTopK / RTopKBig are the heaps above, DS2I_KN(k_x) names the kernel k_x_docs,
+// TK_INSERT passes the candidate's doc-id and DS2I_DOCS_ARG the doc-id output. In every other unit the macros expand to exactly
+// the scores-only text, so the shipped kernels are the same code objects.
+#ifdef DS2I_DOCS_TU
+typedef TopKD RTopK;
+template <int NK> using RTopKBig = TopKBigD<NK>;
+#define DS2I_KN(name) name##_docs
+#define TK_INSERT(tk, s, doc) (tk).insert((s), (doc))
+#define DS2I_DOCS_ARG(p) , (p)
+#else
+typedef TopK RTopK;
+template <int NK> using RTopKBig = TopKBig<NK>;
+#define DS2I_KN(name) name
+#define TK_INSERT(tk, s, doc) (tk).insert(s)
+#define DS2I_DOCS_ARG(p)
+#endif
+
 } // namespace ds2i_dev

@@ -43,6 +43,76 @@ struct Batch {
 // The file is compiled once per list-count class (-DDS2I_TU_TMAX=2|4|8|16: only launch_t<TMAX> and the kernels it
 // instantiates) and once without the macro (everything else): five translation units that build.py compiles in
 // parallel -- the kernel templates are by far the slowest part of the build.
+#ifdef DS2I_DOCS_TU
+// DS2I_OP_TOPK_DOCS (-DDS2I_DOCS_TU, the kernels_t*_docs units of build.py): the ranked operators' kernels of each class with the
+// (score, doc-id) heaps (device_enum.hpp, TopKD), named *_docs. A docs batch runs without counters (a.stats == null): every kernel
+// with a STATS parameter is built uninstrumented; k_daat / k_daat_long have no such parameter and count into nothing.
+#if DS2I_TU_TMAX > 0
+template <int TMAX>
+hipError_t launch_t_docs(int op, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    dim3 g(grid), b(64);
+    const size_t dyn = 1024u * (size_t)a.dyn_lists;
+    switch (op) {
+    case OP_RANKED_AND:
+        if (optpfor_side(a)) hipLaunchKernelGGL((k_conjunctive_docs<true, true, TMAX, CODEC_OPTPFOR, false>), g, b, 0, s, a);
+        else if (a.codec == CODEC_PEF) hipLaunchKernelGGL((k_conjunctive_docs<true, true, TMAX, CODEC_PEF, false>), g, b, 0, s, a);
+        else if (a.codec == CODEC_MIXED) hipLaunchKernelGGL((k_conjunctive_docs<true, true, TMAX, CODEC_MIXED, false>), g, b, 0, s, a);
+        else hipLaunchKernelGGL((k_conjunctive_docs<true, true, TMAX, -1, false>), g, b, 0, s, a);
+        break;
+    case OP_WAND:
+    case OP_MAXSCORE:
+    case OP_RANKED_OR:
+        if (a.vq_info) {
+            if (optpfor_side(a)) hipLaunchKernelGGL((k_union_topk_docs<TMAX, CODEC_OPTPFOR, false>), g, b, 0, s, a);
+            else if (a.codec == CODEC_PEF) hipLaunchKernelGGL((k_union_topk_docs<TMAX, CODEC_PEF, false>), g, b, 0, s, a);
+            else hipLaunchKernelGGL((k_union_topk_docs<TMAX, -1, false>), g, b, 0, s, a);
+            break;
+        }
+        if (optpfor_side(a)) hipLaunchKernelGGL((k_disjunctive_docs<TMAX, CODEC_OPTPFOR, false>), g, b, dyn, s, a);
+        else if (a.codec == CODEC_PEF) hipLaunchKernelGGL((k_disjunctive_docs<TMAX, CODEC_PEF, false>), g, b, dyn, s, a);
+        else if (a.codec == CODEC_MIXED) hipLaunchKernelGGL((k_disjunctive_docs<TMAX, CODEC_MIXED, false>), g, b, dyn, s, a);
+        else hipLaunchKernelGGL((k_disjunctive_docs<TMAX, -1, false>), g, b, dyn, s, a);
+        break;
+    case 0x100 | OP_RANKED_AND: hipLaunchKernelGGL((k_daat_docs<OP_RANKED_AND, TMAX>), g, b, 0, s, a); break;
+    case 0x100 | OP_WAND: hipLaunchKernelGGL((k_daat_docs<OP_WAND, TMAX>), g, b, 0, s, a); break;
+    case 0x100 | OP_MAXSCORE: hipLaunchKernelGGL((k_daat_docs<OP_MAXSCORE, TMAX>), g, b, 0, s, a); break;
+    case 0x100 | OP_RANKED_OR: hipLaunchKernelGGL((k_daat_docs<OP_RANKED_OR, TMAX>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+template hipError_t launch_t_docs<DS2I_TU_TMAX>(int, const BatchArgs&, unsigned, hipStream_t);
+#else
+template <int TMAX>
+hipError_t launch_t_docs(int op, const BatchArgs& a, unsigned grid, hipStream_t s);
+extern template hipError_t launch_t_docs<2>(int, const BatchArgs&, unsigned, hipStream_t);
+extern template hipError_t launch_t_docs<4>(int, const BatchArgs&, unsigned, hipStream_t);
+extern template hipError_t launch_t_docs<8>(int, const BatchArgs&, unsigned, hipStream_t);
+extern template hipError_t launch_t_docs<16>(int, const BatchArgs&, unsigned, hipStream_t);
+hipError_t launch_long_docs(int op, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    dim3 g(grid), b(64);
+    if (a.k > 64) {
+        typedef RTopKBig<16> BIG;
+        switch (op & 0xFF) {
+        case OP_RANKED_AND: hipLaunchKernelGGL((k_daat_long_docs<OP_RANKED_AND, BIG>), g, b, 0, s, a); break;
+        case OP_WAND: hipLaunchKernelGGL((k_daat_long_docs<OP_WAND, BIG>), g, b, 0, s, a); break;
+        case OP_MAXSCORE: hipLaunchKernelGGL((k_daat_long_docs<OP_MAXSCORE, BIG>), g, b, 0, s, a); break;
+        case OP_RANKED_OR: hipLaunchKernelGGL((k_daat_long_docs<OP_RANKED_OR, BIG>), g, b, 0, s, a); break;
+        default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    switch (op & 0xFF) {
+    case OP_RANKED_AND: hipLaunchKernelGGL((k_daat_long_docs<OP_RANKED_AND>), g, b, 0, s, a); break;
+    case OP_WAND: hipLaunchKernelGGL((k_daat_long_docs<OP_WAND>), g, b, 0, s, a); break;
+    case OP_MAXSCORE: hipLaunchKernelGGL((k_daat_long_docs<OP_MAXSCORE>), g, b, 0, s, a); break;
+    case OP_RANKED_OR: hipLaunchKernelGGL((k_daat_long_docs<OP_RANKED_OR>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+#endif
+#else // !DS2I_DOCS_TU
 // DS2I_TU_TMAX == 0: the translation unit of the "long" class (k_daat_long, every operator in reference order)
 #if defined(DS2I_TU_TMAX) && DS2I_TU_TMAX == 0
 hipError_t launch_long(int op, const BatchArgs& a, unsigned grid, hipStream_t s) {
@@ -152,10 +222,43 @@ extern template hipError_t launch_t<4>(int, const BatchArgs&, unsigned, hipStrea
 extern template hipError_t launch_t<8>(int, const BatchArgs&, unsigned, hipStream_t);
 extern template hipError_t launch_t<16>(int, const BatchArgs&, unsigned, hipStream_t);
 #endif
+#endif // DS2I_DOCS_TU
 
 } // namespace ds2i_launch
 
-#if !defined(DS2I_TU_TMAX)
+#if defined(DS2I_DOCS_TU) && DS2I_TU_TMAX == 0
+extern "C" {
+// the *_docs counterparts of ds2i_launch_batch / ds2i_launch_merge / ds2i_launch_copy_seed (ranked operators only)
+hipError_t ds2i_launch_batch_docs(int op, int tmax_class, const void* args, unsigned grid, hipStream_t s) {
+    const BatchArgs& a = *(const BatchArgs*)args;
+    switch (tmax_class) {
+    case 0: return ds2i_launch::launch_t_docs<2>(op, a, grid, s);
+    case 1: return ds2i_launch::launch_t_docs<4>(op, a, grid, s);
+    case 2: return ds2i_launch::launch_t_docs<8>(op, a, grid, s);
+    case 3: return ds2i_launch::launch_t_docs<16>(op, a, grid, s);
+    default: return ds2i_launch::launch_long_docs(op, a, grid, s);
+    }
+}
+hipError_t ds2i_launch_merge_docs(const void* args, unsigned grid, hipStream_t s) {
+    const MergeArgs& a = *(const MergeArgs*)args;
+    if (!a.ranked) return hipErrorInvalidValue;
+    if (a.k > 256) hipLaunchKernelGGL((k_merge_big_docs<16>), dim3(grid), dim3(64), 0, s, a);
+    else if (a.k > 64) hipLaunchKernelGGL((k_merge_big_docs<4>), dim3(grid), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_merge_docs, dim3(grid), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+hipError_t ds2i_launch_copy_seed_docs(const uint32_t* queries, uint32_t n, uint32_t k, const float* seed_topk, const uint32_t* seed_docs,
+                                      const uint32_t* seed_len, const unsigned long long* seed_count, float* out_topk, uint32_t* out_docs,
+                                      uint32_t* out_len, unsigned long long* out_count, hipStream_t s) {
+    CopySeedDocsArgs a{CopySeedArgs{queries, n, k, seed_topk, seed_len, seed_count, out_topk, out_len, out_count}, seed_docs, out_docs};
+    hipLaunchKernelGGL(k_copy_seed_docs, dim3(n < 1024 ? n : 1024), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+}
+#endif
+
+
+#if !defined(DS2I_TU_TMAX) && !defined(DS2I_DOCS_TU)
 extern "C" {
 
 // tmax_class: 0 -> TMAX 2, 1 -> TMAX 4, 2 -> TMAX 8, 3 -> TMAX 16 (LDS footprint per wave grows with TMAX),

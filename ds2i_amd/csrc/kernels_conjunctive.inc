@@ -73,7 +73,7 @@ struct LdsConj : Lds<TMAX, META_IN_LDS, !RANKED, WITH_S16, (RANKED && TMAX > 2) 
 };
 
 template <bool RANKED, bool WITH_FREQS, int TMAX, int CODEC_T, bool STATS = true>
-__global__ void __launch_bounds__(64, CONJ_WAVES_R(RANKED, TMAX)) k_conjunctive(BatchArgs a) {
+__global__ void __launch_bounds__(64, CONJ_WAVES_R(RANKED, TMAX)) DS2I_KN(k_conjunctive)(BatchArgs a) {
     // <=4 lists: every list loop below is fully unrolled, so the enumerator state is addressed with constants
     // and lives in registers (MetaReg); 8/16 lists keep it in LDS (code size)
     constexpr bool REG = TMAX <= 4;
@@ -110,11 +110,11 @@ __global__ void __launch_bounds__(64, CONJ_WAVES_R(RANKED, TMAX)) k_conjunctive(
         const bool whole = u.nparts == 1;
         const uint32_t t0 = a.q_off[q], nt = a.q_off[q + 1] - t0;
         unsigned long long count = 0, fsum = 0;
-        TopK tk;
+        RTopK tk;
         tk.init(a.k);
         if (nt == 0 || nt > (uint32_t)TMAX) { // empty query -> 0 results (queries.hpp:41,335)
             if (lane == 0) { a.out_count[q] = 0; if (a.out_freq_sum) a.out_freq_sum[q] = 0; }
-            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
             continue;
         }
         // list 0 (shortest) drives; the unit owns its blocks [blk_begin, blk_end). The other lists are
@@ -784,7 +784,7 @@ __global__ void __launch_bounds__(64, CONJ_WAVES_R(RANKED, TMAX)) k_conjunctive(
 #ifdef DS2I_PHASE_TIMING
                             cx.s_phase[PH_C_HEAP] += 1;
 #endif
-                            if (tk.insert(v) && shared_floor && lane == 0) sh.add(v);
+                            if (TK_INSERT(tk, v, bcast(half ? c1 : c0, src)) && shared_floor && lane == 0) sh.add(v);
                         }
                     }
 #ifdef DS2I_PHASE_TIMING
@@ -806,13 +806,13 @@ __global__ void __launch_bounds__(64, CONJ_WAVES_R(RANKED, TMAX)) k_conjunctive(
                 a.out_count[q] = RANKED ? tk.n : count;
                 if (a.out_freq_sum) a.out_freq_sum[q] = fsum;
             }
-            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
         } else {
             if (lane == 0) {
                 a.unit_count[uid] = RANKED ? tk.n : count;
                 a.unit_freq_sum[uid] = fsum;
             }
-            if (RANKED) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk);
+            if (RANKED) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk DS2I_DOCS_ARG(a.unit_topk_docs));
         }
         if (STATS && a.unit_clock && lane == 0) { a.unit_clock[2ull * uid] = t_unit; a.unit_clock[2ull * uid + 1] = wall_clock64(); }
     }
@@ -821,7 +821,7 @@ __global__ void __launch_bounds__(64, CONJ_WAVES_R(RANKED, TMAX)) k_conjunctive(
 
 // Merges the partial results of split queries: counts add up, the top-k of a union is the top-k of
 // the parts' top-ks (scores are per-document, so the merged multiset equals the sequential one).
-__global__ void __launch_bounds__(64) k_merge(MergeArgs a) {
+__global__ void __launch_bounds__(64) DS2I_KN(k_merge)(MergeArgs a) {
     const uint32_t lane = lane_id();
     for (uint32_t w = blockIdx.x; w < a.nsplit; w += gridDim.x) {
         const uint32_t q = a.split_queries[w];
@@ -832,20 +832,23 @@ __global__ void __launch_bounds__(64) k_merge(MergeArgs a) {
             count += __shfl_xor(count, o);
             fsum += __shfl_xor(fsum, o);
         }
-        TopK tk;
+        RTopK tk;
         tk.init(a.k);
         if (a.ranked) {
             for (uint32_t u = u0; u < u1; ++u) {
                 const uint32_t len = a.unit_topk_len[u];
                 float v = lane < len ? a.unit_topk[(size_t)u * a.k + lane] : -__builtin_inff();
+#ifdef DS2I_DOCS_TU
+                const uint32_t vd = lane < len ? a.unit_topk_docs[(size_t)u * a.k + lane] : 0xFFFFFFFFu;
+#endif
                 uint64_t todo = ballot(lane < len && tk.would_enter(v));
                 while (todo) {
                     uint32_t src = (uint32_t)__builtin_ctzll(todo);
                     todo &= todo - 1;
-                    tk.insert(__uint_as_float(bcast(__float_as_uint(v), src)));
+                    TK_INSERT(tk, __uint_as_float(bcast(__float_as_uint(v), src)), bcast(vd, src));
                 }
             }
-            store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
         }
         if (lane == 0) {
             a.out_count[q] = a.ranked ? tk.n : count;
@@ -856,7 +859,7 @@ __global__ void __launch_bounds__(64) k_merge(MergeArgs a) {
 
 // ... and of ranked_and batches with 64 < k <= 64 NK (the stream kernels' big heaps, ranked_stream.hip)
 template <int NK>
-__global__ void __launch_bounds__(64) k_merge_big(MergeArgs a) {
+__global__ void __launch_bounds__(64) DS2I_KN(k_merge_big)(MergeArgs a) {
     const uint32_t lane = lane_id();
     for (uint32_t w = blockIdx.x; w < a.nsplit; w += gridDim.x) {
         const uint32_t q = a.split_queries[w];
@@ -867,7 +870,7 @@ __global__ void __launch_bounds__(64) k_merge_big(MergeArgs a) {
             count += __shfl_xor(count, o);
             fsum += __shfl_xor(fsum, o);
         }
-        TopKBig<NK> tk;
+        RTopKBig<NK> tk;
         tk.init(a.k);
         if (a.ranked) {
             for (uint32_t u = u0; u < u1; ++u) {
@@ -875,16 +878,19 @@ __global__ void __launch_bounds__(64) k_merge_big(MergeArgs a) {
                 for (uint32_t r0 = 0; r0 < len; r0 += 64) { // (a unit's scores are in descending order: once a row enters nothing, the rest cannot)
                     const uint32_t i = r0 + lane;
                     float v = i < len ? a.unit_topk[(size_t)u * a.k + i] : -__builtin_inff();
+#ifdef DS2I_DOCS_TU
+                    const uint32_t vd = i < len ? a.unit_topk_docs[(size_t)u * a.k + i] : 0xFFFFFFFFu;
+#endif
                     uint64_t todo = ballot(i < len && tk.would_enter(v));
                     if (!todo) break;
                     while (todo) {
                         uint32_t src = (uint32_t)__builtin_ctzll(todo);
                         todo &= todo - 1;
-                        tk.insert(__uint_as_float(bcast(__float_as_uint(v), src)));
+                        TK_INSERT(tk, __uint_as_float(bcast(__float_as_uint(v), src)), bcast(vd, src));
                     }
                 }
             }
-            store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
         }
         if (lane == 0) {
             a.out_count[q] = a.ranked ? tk.n : count;

@@ -25,7 +25,7 @@ DS2I_DEV void sort_ord(uint32_t* ord, uint32_t n, Key key) {
 // One unit of a reference-order operator. The per-list enumerator state (`meta`: M_WORDS dwords per slot, the same
 // memory cx.meta points to), the list order `ord` and the maxscore upper bounds `ub` live wherever the caller keeps
 // them: LDS for the <=16-term classes (k_daat), a global scratch area for longer queries (k_daat_long).
-template <int OP, class TK = TopK, class CX>
+template <int OP, class TK = RTopK, class CX>
 DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t* meta, uint32_t* ord, float* ubs, const uint32_t tmax) {
     const uint32_t lane = lane_id();
     constexpr bool RANKED = OP >= OP_RANKED_AND;
@@ -43,7 +43,7 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
         tk.init(a.k);
         if (nt == 0 || nt > tmax) {
             if (lane == 0) { a.out_count[q] = 0; if (a.out_freq_sum) a.out_freq_sum[q] = 0; }
-            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
             return;
         }
         if (whole) {
@@ -83,7 +83,7 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
                     if (OP == OP_RANKED_AND) {
                         float nl = norm_len(cand), score = 0.f;
                         for (i = 0; i < nt; ++i) score += score_of(cx, i, nl);
-                        tk.insert(score);
+                        TK_INSERT(tk, score, cand);
                     } else {
                         if (a.out_matches && lane == 0 && count < mcap) a.out_matches[mbase + count] = cand;
                         ++count;
@@ -111,7 +111,7 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
                     uint32_t d = cx.docid(i);
                     nxt = d < nxt ? d : nxt;
                 }
-                if (OP == OP_RANKED_OR) tk.insert(score); else ++count;
+                if (OP == OP_RANKED_OR) TK_INSERT(tk, score, cur); else ++count;
                 cur = nxt;
             }
         } else if (OP == OP_WAND) {
@@ -140,7 +140,7 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
                         score += score_of(cx, s, nl);
                         cx.next(s);
                     }
-                    tk.insert(score);
+                    TK_INSERT(tk, score, pivot_id);
                     sort_ord(ord, nt, by_docid);
                 } else {
                     uint32_t nl_ = pivot;
@@ -195,7 +195,7 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
                     cx.next_geq(s, cur);
                     if (cx.docid(s) == cur) score += score_of(cx, s, nl);
                 }
-                if (tk.insert(score)) {
+                if (TK_INSERT(tk, score, cur)) {
                     while (non_ess < nt && !tk.would_enter(__uint_as_float(uniform(__float_as_uint(ubs[non_ess])))))
                         ++non_ess;
                 }
@@ -207,19 +207,19 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
                 a.out_count[q] = RANKED ? tk.n : count;
                 if (a.out_freq_sum) a.out_freq_sum[q] = fsum;
             }
-            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
         } else {
             if (lane == 0) {
                 a.unit_count[uid] = RANKED ? tk.n : count;
                 a.unit_freq_sum[uid] = fsum;
             }
-            if (RANKED) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk);
+            if (RANKED) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk DS2I_DOCS_ARG(a.unit_topk_docs));
         }
     }
 }
 
 template <int OP, int TMAX, int CODEC_T = -1>
-__global__ void __launch_bounds__(64) k_daat(BatchArgs a) {
+__global__ void __launch_bounds__(64) DS2I_KN(k_daat)(BatchArgs a) {
     __shared__ Lds<TMAX> L;
     CtxT<CODEC_T, MetaLds> cx = make_ctx<CODEC_T, MetaLds>(L, a);
     for (uint32_t tkt = blockIdx.x; tkt < a.nslice; tkt += gridDim.x)
@@ -234,8 +234,8 @@ struct LdsLong {
     uint32_t exc[EXC_LDS_DW];
     uint32_t st[STAGE_DW];
 };
-template <int OP, class TK = TopK>
-__global__ void __launch_bounds__(64) k_daat_long(BatchArgs a) {
+template <int OP, class TK = RTopK>
+__global__ void __launch_bounds__(64) DS2I_KN(k_daat_long)(BatchArgs a) {
     __shared__ LdsLong L;
     CtxT<-1, MetaLds> cx;
     cx.docs = cx.freqs = nullptr;

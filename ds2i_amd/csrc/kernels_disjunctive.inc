@@ -64,7 +64,7 @@ struct LdsOr { // (the decoded blocks are in dynamic shared memory, see k_disjun
 #endif
 constexpr int DISJ_WAVES(int tmax, int mode) { return mode != 0 ? 1 : tmax <= 2 ? DS2I_DISJ_WAVES2 : tmax <= 4 ? DS2I_DISJ_WAVES4 : 1; }
 template <int TMAX, int CODEC_T, bool STATS = true, int MODE = 0>
-__global__ void __launch_bounds__(64, DISJ_WAVES(TMAX, MODE)) k_disjunctive(BatchArgs a) {
+__global__ void __launch_bounds__(64, DISJ_WAVES(TMAX, MODE)) DS2I_KN(k_disjunctive)(BatchArgs a) {
     __shared__ LdsOr<TMAX> L;
     // the decoded blocks live in DYNAMIC shared memory, sized by the launch for the longest query it contains
     // (a.dyn_lists <= TMAX list slots: docs[dyn_lists][128] then freqs[dyn_lists][128]). Residency hides this kernel's
@@ -86,16 +86,16 @@ __global__ void __launch_bounds__(64, DISJ_WAVES(TMAX, MODE)) k_disjunctive(Batc
         const uint32_t N = whole ? a.num_docs : u.blk_end; // the unit's doc-id range is [lo, N)
         uint32_t lo = whole ? 0u : u.blk_begin;
         const uint32_t t0 = a.q_off[q], nt = a.q_off[q + 1] - t0;
-        TopK tk;
+        RTopK tk;
         tk.init(a.k);
         unsigned long long count = 0, fsum = 0;
         if (nt == 0 || nt > (uint32_t)TMAX || nt > a.dyn_lists || N == 0) {
             if (whole) {
                 if (lane == 0) { a.out_count[q] = 0; if (a.out_freq_sum) a.out_freq_sum[q] = 0; }
-                if (MODE == 0) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+                if (MODE == 0) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
             } else {
                 if (lane == 0) { a.unit_count[uid] = 0; a.unit_freq_sum[uid] = 0; }
-                if (MODE == 0) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk);
+                if (MODE == 0) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk DS2I_DOCS_ARG(a.unit_topk_docs));
             }
             continue;
         }
@@ -509,7 +509,7 @@ __global__ void __launch_bounds__(64, DISJ_WAVES(TMAX, MODE)) k_disjunctive(Batc
                         const uint32_t src = (uint32_t)__builtin_ctzll(todo);
                         todo &= todo - 1;
                         const float v = __uint_as_float(bcast(__float_as_uint(sc), src));
-                        if (tk.insert(v)) {
+                        if (TK_INSERT(tk, v, bcast(half ? c1 : c0, src))) {
                             inserted = true;
                             if (shared_floor && lane == 0) sh.add(v);
                         }
@@ -525,10 +525,10 @@ __global__ void __launch_bounds__(64, DISJ_WAVES(TMAX, MODE)) k_disjunctive(Batc
         }
         if (whole) {
             if (lane == 0) { a.out_count[q] = MODE == 0 ? tk.n : count; if (a.out_freq_sum) a.out_freq_sum[q] = fsum; }
-            if (MODE == 0) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+            if (MODE == 0) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
         } else {
             if (lane == 0) { a.unit_count[uid] = MODE == 0 ? tk.n : count; a.unit_freq_sum[uid] = fsum; }
-            if (MODE == 0) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk);
+            if (MODE == 0) store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk DS2I_DOCS_ARG(a.unit_topk_docs));
         }
         if (STATS && a.unit_clock && lane == 0) { a.unit_clock[2ull * uid] = t_unit; a.unit_clock[2ull * uid + 1] = wall_clock64(); }
 #ifdef DS2I_PHASE_TIMING
@@ -562,7 +562,7 @@ template <int TMAX, bool META_IN_LDS, bool WITH_S16>
 struct LdsUnionTopk : Lds<TMAX, META_IN_LDS, false, WITH_S16, (TMAX > 2) ? 2 : TMAX> {};
 
 template <int TMAX, int CODEC_T, bool STATS = true>
-__global__ void __launch_bounds__(64, UT_WAVES(TMAX)) k_union_topk(BatchArgs a) {
+__global__ void __launch_bounds__(64, UT_WAVES(TMAX)) DS2I_KN(k_union_topk)(BatchArgs a) {
     constexpr bool REG = TMAX <= 4;
     typedef typename std::conditional<REG, MetaReg<TMAX>, MetaLds>::type META;
     __shared__ LdsUnionTopk<TMAX, !REG, CODEC_T != CODEC_PEF && CODEC_T != CODEC_OPTPFOR> L;
@@ -582,15 +582,15 @@ __global__ void __launch_bounds__(64, UT_WAVES(TMAX)) k_union_topk(BatchArgs a) 
         const float s_all = __uint_as_float(uniform(a.vq_info[3u * vq + 2u]));
         const bool whole = u.nparts == 1;
         const uint32_t t0 = a.q_off[vq], nt = a.q_off[vq + 1] - t0;
-        TopK tk;
+        RTopK tk;
         tk.init(a.k);
         auto finish_unit = [&]() __attribute__((always_inline)) {
             if (whole) {
                 if (lane == 0) a.out_count[q] = tk.n;
-                store_topk(a.out_topk, a.out_topk_len, a.k, q, tk);
+                store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));
             } else {
                 if (lane == 0) { a.unit_count[uid] = tk.n; a.unit_freq_sum[uid] = 0; }
-                store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk);
+                store_topk(a.unit_topk, a.unit_topk_len, a.k, uid, tk DS2I_DOCS_ARG(a.unit_topk_docs));
             }
             if (STATS && a.unit_clock && lane == 0) { a.unit_clock[2ull * uid] = t_unit; a.unit_clock[2ull * uid + 1] = wall_clock64(); }
         };
@@ -992,7 +992,7 @@ __global__ void __launch_bounds__(64, UT_WAVES(TMAX)) k_union_topk(BatchArgs a) 
                     const uint32_t src = (uint32_t)__builtin_ctzll(todo);
                     todo &= todo - 1;
                     const float v = __uint_as_float(bcast(__float_as_uint(sc), src));
-                    if (tk.insert(v) && shared_floor && lane == 0) sh.add(v);
+                    if (TK_INSERT(tk, v, bcast(half ? c1 : c0, src)) && shared_floor && lane == 0) sh.add(v);
                 }
             }
         }

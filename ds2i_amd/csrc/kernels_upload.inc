@@ -349,6 +349,26 @@ __global__ void __launch_bounds__(64) k_copy_seed(CopySeedArgs a) {
     }
 }
 
+#ifdef DS2I_DOCS_TU
+// ... with the doc-ids (DS2I_OP_TOPK_DOCS: the seed batch ran the docs kernels too)
+struct CopySeedDocsArgs {
+    CopySeedArgs s;
+    const uint32_t* seed_docs;
+    uint32_t* out_docs;
+};
+__global__ void __launch_bounds__(64) k_copy_seed_docs(CopySeedDocsArgs a) {
+    const uint32_t lane = lane_id();
+    for (uint32_t w = blockIdx.x; w < a.s.n; w += gridDim.x) {
+        const uint32_t q = a.s.queries[w];
+        for (uint32_t i = lane; i < a.s.k; i += 64) {
+            a.s.out_topk[(size_t)q * a.s.k + i] = a.s.seed_topk[(size_t)q * a.s.k + i];
+            a.out_docs[(size_t)q * a.s.k + i] = a.seed_docs[(size_t)q * a.s.k + i];
+        }
+        if (lane == 0) { a.s.out_len[q] = a.s.seed_len[q]; a.s.out_count[q] = a.s.seed_count[q]; }
+    }
+}
+#endif
+
 // FETCH_SIZE calibration (MI355X_MICROARCH.md §HBM): streams `ndw` dwords of the arena with the same
 // access shape as Window::load (one dword per lane, 64 consecutive lanes) and folds them into a checksum.
 __global__ void __launch_bounds__(64) k_calib_read(const uint32_t* base, unsigned long long ndw, uint32_t* out) {

@@ -83,7 +83,7 @@ struct LdsRS {
 // queries (nt = 1 in a capacity-4 launch: no list 1, every test on it passes), which otherwise keep their class kernel.
 #define RS_WAVES_K(NT, NK) ((NK) == 1 ? RS_WAVES(NT) : (RS_WAVES(NT) < ((NK) <= 4 ? 4 : 3) ? RS_WAVES(NT) : ((NK) <= 4 ? 4 : 3)))
 template <int NT, bool STATS, bool AND = false, bool FREQS = false, int NK = 1>
-__global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) k_ranked_stream(BatchArgs a_unused) {
+__global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) DS2I_KN(k_ranked_stream)(BatchArgs a_unused) {
     static_assert(AND || !FREQS, "FREQS is a variant of AND");
     static_assert(NK == 1 || !AND, "the big heap is ranked_and's");
     static_assert(NT >= 2 && NT <= 16, "list capacities 2..16");
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) k_ranked_stream(BatchA
         const uint32_t nt = NT == 2 ? 2u : uniform(u.pad);
         const bool has1 = NT == 2 || nt > 1u; // (a one-term query in a capacity-4 launch, NK > 1 only: there is no list 1)
         const QTerm* const qt = rs_uniform_ptr(a->qterms + uniform(u.qt_off)); // nt terms
-        typename std::conditional<NK == 1, TopK, TopKBig<NK>>::type tk;
+        typename std::conditional<NK == 1, RTopK, RTopKBig<NK>>::type tk;
         tk.init(a->k);
         unsigned long long and_count = 0; // (AND: results of this unit)
         unsigned long long and_fsum = 0;  // (FREQS: this lane's share of the unit's freq checksum)
@@ -717,7 +717,7 @@ __global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) k_ranked_stream(BatchA
                             todo &= todo - 1;
                             const float v = __uint_as_float(bcast(__float_as_uint(sc), src));
                             LC(PH_C_HEAP, 1);
-                            if (tk.insert(v)) {
+                            if (TK_INSERT(tk, v, bcast(half ? dB1 : dB0, src))) {
                                 refresh();
                                 inserted = 1;
                                 if (shared_floor && lane == 0) sh.add(v);
@@ -784,10 +784,10 @@ __global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) k_ranked_stream(BatchA
             }
         } else if (whole) {
             if (lane == 0) { r->out_count[q] = tk.n; if (r->out_freq_sum) r->out_freq_sum[q] = 0; }
-            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk);
+            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk DS2I_DOCS_ARG(r->out_topk_docs));
         } else {
             if (lane == 0) { r->unit_count[uid] = tk.n; r->unit_freq_sum[uid] = 0; }
-            store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk);
+            store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk DS2I_DOCS_ARG(r->unit_topk_docs));
         }
     }
     Stats* const stats = rs_args()->stats;
@@ -812,6 +812,38 @@ __global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) k_ranked_stream(BatchA
 } // namespace
 
 extern "C" {
+#ifdef DS2I_DOCS_TU
+// DS2I_OP_TOPK_DOCS: k_ranked_stream_docs, the (score, doc-id) heaps, uninstrumented only (a docs batch runs without counters);
+// the same caps and k split as the launchers below
+#ifdef DS2I_RS_BIGK_TU
+hipError_t ds2i_launch_ranked_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
+    const BatchArgs& a = *(const BatchArgs*)args;
+    const dim3 g(grid), b(64);
+#define DS2I_RSK_CASE(N) case N: \
+        if (a.k <= 256) hipLaunchKernelGGL((k_ranked_stream_docs<N, false, false, false, 4>), g, b, 0, s, a); \
+        else hipLaunchKernelGGL((k_ranked_stream_docs<N, false, false, false, 16>), g, b, 0, s, a); \
+        break;
+    switch (cap) {
+    DS2I_RSK_CASE(2) DS2I_RSK_CASE(4) DS2I_RSK_CASE(6) DS2I_RSK_CASE(8) DS2I_RSK_CASE(16)
+    default: return hipErrorInvalidValue;
+    }
+#undef DS2I_RSK_CASE
+    return hipGetLastError();
+}
+#else
+hipError_t ds2i_launch_ranked_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
+    const BatchArgs& a = *(const BatchArgs*)args;
+    const dim3 g(grid), b(64);
+#define DS2I_RS_CASE(N) case N: hipLaunchKernelGGL((k_ranked_stream_docs<N, false>), g, b, 0, s, a); break;
+    switch (cap) {
+    DS2I_RS_CASE(2) DS2I_RS_CASE(4) DS2I_RS_CASE(6) DS2I_RS_CASE(8) DS2I_RS_CASE(16)
+    default: return hipErrorInvalidValue;
+    }
+#undef DS2I_RS_CASE
+    return hipGetLastError();
+}
+#endif
+#else // !DS2I_DOCS_TU
 #ifdef DS2I_RS_BIGK_TU
 // ranked_and with 64 < k <= 1024 (compiled as a translation unit of its own: -DDS2I_RS_BIGK_TU, ds2i_amd/build.py): k <= 256 keeps four
 // scores per lane, beyond that sixteen; cap as below, one-term queries ride in the capacity-4 launch
@@ -865,4 +897,5 @@ hipError_t ds2i_launch_and_rstream(int cap, int with_freqs, const void* args, un
     return hipGetLastError();
 }
 #endif
+#endif // DS2I_DOCS_TU
 }

@@ -126,6 +126,11 @@ DS2I_DEV void store_topk_rs(float* topk, uint32_t* topk_len, uint32_t k, uint32_
     if (lane < k) topk[(size_t)slot * k + lane] = tk.v;
     if (lane == 0) topk_len[slot] = tk.n;
 }
+DS2I_DEV void store_topk_rs(float* topk, uint32_t* topk_len, uint32_t k, uint32_t slot, const TopKD& tk, uint32_t* docs) {
+    const uint32_t lane = lane_id();
+    if (lane < k) { topk[(size_t)slot * k + lane] = tk.v; docs[(size_t)slot * k + lane] = tk.d; }
+    if (lane == 0) topk_len[slot] = tk.n;
+}
 
 template <int I, int N, class F>
 DS2I_DEV void rs_for(F& f) {
@@ -208,7 +213,7 @@ DS2I_DEV uint32_t rs_decode(uint32_t* st, const uint8_t* p, uint32_t sum, uint32
 #define RS_HINT_FIRST(nt) ((nt) > 2)
 #endif
 template <int NT, bool STATS, int CODEC = CODEC_OPTPFOR>
-__global__ void __launch_bounds__(64, RS_WAVES(NT)) k_ranked_stream_mixed(BatchArgs a_unused) {
+__global__ void __launch_bounds__(64, RS_WAVES(NT)) DS2I_KN(k_ranked_stream_mixed)(BatchArgs a_unused) {
     static_assert(NT >= 2 && NT <= 4, "exact list counts 2..4");
     __shared__ LdsRS<NT> L;
     const uint32_t lane = lane_id();
@@ -252,7 +257,7 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) k_ranked_stream_mixed(BatchA
         const uint32_t q = u.q;
         const bool whole = u.nparts == 1;
         const QTerm* const qt = a->qterms + a->q_off[q]; // exactly NT terms (the planner's launch groups)
-        TopK tk;
+        RTopK tk;
         tk.init(a->k);
         // ---- list 0: the stream
         const uint32_t n0 = qt[0].n, nb0 = (n0 + 127u) >> 7;
@@ -698,7 +703,7 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) k_ranked_stream_mixed(BatchA
                             todo &= todo - 1;
                             const float v = __uint_as_float(bcast(__float_as_uint(sc), src));
                             LC(PH_C_HEAP, 1);
-                            if (tk.insert(v)) {
+                            if (TK_INSERT(tk, v, bcast(half ? dB1 : dB0, src))) {
                                 refresh();
                                 if (shared_floor && lane == 0) sh.add(v);
                             }
@@ -746,10 +751,10 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) k_ranked_stream_mixed(BatchA
         }
         if (whole) {
             if (lane == 0) { r->out_count[q] = tk.n; if (r->out_freq_sum) r->out_freq_sum[q] = 0; }
-            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk);
+            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk DS2I_DOCS_ARG(r->out_topk_docs));
         } else {
             if (lane == 0) { r->unit_count[uid] = tk.n; r->unit_freq_sum[uid] = 0; }
-            store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk);
+            store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk DS2I_DOCS_ARG(r->unit_topk_docs));
         }
     }
     Stats* const stats = rs_args()->stats;
@@ -770,6 +775,20 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) k_ranked_stream_mixed(BatchA
 } // namespace
 
 extern "C" {
+#ifdef DS2I_DOCS_TU
+// DS2I_OP_TOPK_DOCS: k_ranked_stream_mixed_docs, uninstrumented (a docs batch passes no counters)
+hipError_t ds2i_launch_ranked_stream_mixed_docs(int nt, const void* args, unsigned grid, hipStream_t s) {
+    const BatchArgs& a = *(const BatchArgs*)args;
+    const dim3 g(grid), b(64);
+    switch (nt) {
+    case 2: hipLaunchKernelGGL((k_ranked_stream_mixed_docs<2, false, CODEC_MIXED>), g, b, 0, s, a); break;
+    case 3: hipLaunchKernelGGL((k_ranked_stream_mixed_docs<3, false, CODEC_MIXED>), g, b, 0, s, a); break;
+    case 4: hipLaunchKernelGGL((k_ranked_stream_mixed_docs<4, false, CODEC_MIXED>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+#else
 // nt = exact number of distinct terms of every query of the launch (2..4); block_mixed index with skip table, block weights
 // and range tables, k <= 64 (instrumented and uninstrumented runs share the instantiation with counters)
 hipError_t ds2i_launch_ranked_stream_mixed(int nt, const void* args, unsigned grid, hipStream_t s) {
@@ -783,4 +802,5 @@ hipError_t ds2i_launch_ranked_stream_mixed(int nt, const void* args, unsigned gr
     }
     return hipGetLastError();
 }
+#endif // DS2I_DOCS_TU
 }

@@ -68,7 +68,7 @@ enum { LS_CUR = 0, LS_BMAX, LS_N, LS_BB, LS_LOLO, LS_LOHI, LS_QW, LS_TLLO, LS_TL
 // NK > 1 (k > 64; topk_queue has no limit, queries.hpp:152-197): NK scores per lane (TopKBig<NK>: k <= 64 NK), fewer waves per SIMD
 #define US_WAVES_K(NT, NK) ((NK) == 1 ? US_WAVES(NT) : (US_WAVES(NT) < ((NK) <= 4 ? 4 : 3) ? US_WAVES(NT) : ((NK) <= 4 ? 4 : 3)))
 template <int NT, bool STATS, int NK = 1>
-__global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) k_union_stream(BatchArgs a_unused) {
+__global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) DS2I_KN(k_union_stream)(BatchArgs a_unused) {
     static_assert(NT >= 2 && NT <= 16, "list capacities 2..16");
     __shared__ LdsUS<NT> L;
     const uint32_t lane = lane_id();
@@ -101,7 +101,7 @@ __global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) k_union_stream(BatchAr
         const uint32_t nt = NT == 2 ? 2u : uniform(u.pad) >> 8; // lists of this virtual query (2 .. NT)
         const bool whole = uniform(u.nparts) == 1u;
         const QTerm* const qt = rs_uniform_ptr(a->qterms + uniform(u.qt_off)); // nt terms
-        typename std::conditional<NK == 1, TopK, TopKBig<NK>>::type tk;
+        typename std::conditional<NK == 1, RTopK, RTopKBig<NK>>::type tk;
         tk.init(a->k);
         // ---- list 0: the driver
         const uint32_t n0 = uniform(qt[0].n), nb0 = (n0 + 127u) >> 7;
@@ -623,7 +623,7 @@ __global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) k_union_stream(BatchAr
                             todo &= todo - 1;
                             const float v = __uint_as_float(bcast(__float_as_uint(sc), src));
                             EV(PH_C_HEAP, 1);
-                            if (tk.insert(v)) {
+                            if (TK_INSERT(tk, v, bcast(half ? dB1 : dB0, src))) {
                                 refresh();
                                 inserted = 1;
                                 if (shared_floor && lane == 0) sh.add(v);
@@ -678,10 +678,10 @@ __global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) k_union_stream(BatchAr
         }
         if (whole) {
             if (lane == 0) r->out_count[q] = tk.n;
-            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk);
+            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk DS2I_DOCS_ARG(r->out_topk_docs));
         } else {
             if (lane == 0) { r->unit_count[uid] = tk.n; r->unit_freq_sum[uid] = 0; }
-            store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk);
+            store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk DS2I_DOCS_ARG(r->unit_topk_docs));
         }
     }
     Stats* const stats = rs_args()->stats;
@@ -703,6 +703,37 @@ __global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) k_union_stream(BatchAr
 } // namespace
 
 extern "C" {
+#ifdef DS2I_DOCS_TU
+// DS2I_OP_TOPK_DOCS: k_union_stream_docs (uninstrumented; same caps and k split as below)
+#ifdef DS2I_US_BIGK_TU
+hipError_t ds2i_launch_union_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
+    const BatchArgs& a = *(const BatchArgs*)args;
+    const dim3 g(grid), b(64);
+#define DS2I_USK_CASE(N) case N: \
+        if (a.k <= 256) hipLaunchKernelGGL((k_union_stream_docs<N, false, 4>), g, b, 0, s, a); \
+        else hipLaunchKernelGGL((k_union_stream_docs<N, false, 16>), g, b, 0, s, a); \
+        break;
+    switch (cap) {
+    DS2I_USK_CASE(2) DS2I_USK_CASE(4) DS2I_USK_CASE(6) DS2I_USK_CASE(8) DS2I_USK_CASE(16)
+    default: return hipErrorInvalidValue;
+    }
+#undef DS2I_USK_CASE
+    return hipGetLastError();
+}
+#else
+hipError_t ds2i_launch_union_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
+    const BatchArgs& a = *(const BatchArgs*)args;
+    const dim3 g(grid), b(64);
+#define DS2I_US_CASE(N) case N: hipLaunchKernelGGL((k_union_stream_docs<N, false>), g, b, 0, s, a); break;
+    switch (cap) {
+    DS2I_US_CASE(2) DS2I_US_CASE(4) DS2I_US_CASE(6) DS2I_US_CASE(8) DS2I_US_CASE(16)
+    default: return hipErrorInvalidValue;
+    }
+#undef DS2I_US_CASE
+    return hipGetLastError();
+}
+#endif
+#else // !DS2I_DOCS_TU
 #ifdef DS2I_US_BIGK_TU
 // wand / maxscore / ranked_or with 64 < k <= 1024 (a translation unit of its own: -DDS2I_US_BIGK_TU, ds2i_amd/build.py): k <= 256 keeps
 // four scores per lane, beyond that sixteen; cap as below
@@ -738,4 +769,5 @@ hipError_t ds2i_launch_union_stream(int cap, const void* args, unsigned grid, hi
     return hipGetLastError();
 }
 #endif
+#endif // DS2I_DOCS_TU
 }

@@ -119,9 +119,18 @@ public:
         std::vector<uint32_t> len(nq, 0);
         // the device counters are an instrumentation option (the reference's block_profiler is a template flag too):
         // off unless asked for, so timing loops run the uninstrumented kernels; kernel_ms is always filled
-        check(ds2i_hip_query_batch(index.handle(), OP | (m_counters ? 0 : DS2I_OP_NO_COUNTERS), k, terms.data(), offs.data(), nq,
-                                   m_counts.data(), topk.data(), len.data(), &m_stats),
-              "ds2i_hip_query_batch");
+        const int op = OP | (m_counters ? 0 : DS2I_OP_NO_COUNTERS);
+        m_topk_docs.assign(nq, std::vector<uint32_t>());
+        if (m_docs) { // (DS2I_OP_TOPK_DOCS: the doc-id of every score; a docs batch reports no counters)
+            std::vector<uint32_t> docs((size_t)nq * k, 0xFFFFFFFFu);
+            check(ds2i_hip_query_batch_docs(index.handle(), op | DS2I_OP_TOPK_DOCS, k, terms.data(), offs.data(), nq, m_counts.data(), topk.data(),
+                                            docs.data(), len.data(), &m_stats),
+                  "ds2i_hip_query_batch_docs");
+            for (uint32_t q = 0; q < nq; ++q) m_topk_docs[q].assign(docs.begin() + (size_t)q * k, docs.begin() + (size_t)q * k + len[q]);
+        } else {
+            check(ds2i_hip_query_batch(index.handle(), op, k, terms.data(), offs.data(), nq, m_counts.data(), topk.data(), len.data(), &m_stats),
+                  "ds2i_hip_query_batch");
+        }
         m_topk.assign(nq, std::vector<float>());
         if (ranked())
             for (uint32_t q = 0; q < nq; ++q) m_topk[q].assign(topk.begin() + (size_t)q * k, topk.begin() + (size_t)q * k + len[q]);
@@ -132,15 +141,28 @@ public:
         return m_topk.empty() ? none : m_topk.back();
     }
     std::vector<std::vector<float>> const& topk_batch() const { return m_topk; }
+    // the doc-ids of topk() / topk_batch(), same order (score descending, equal scores by doc-id ascending; on a tie at the k-th
+    // place the smaller doc-ids): filled while collect_docs(true) is in force, empty otherwise
+    std::vector<uint32_t> const& topk_docs() const {
+        static const std::vector<uint32_t> none;
+        return m_topk_docs.empty() ? none : m_topk_docs.back();
+    }
+    std::vector<std::vector<uint32_t>> const& topk_docs_batch() const { return m_topk_docs; }
     ds2i_hip_stats const& stats() const { return m_stats; }
     void collect_counters(bool on) { m_counters = on; }
+    // ranked operators: also return the doc-id of every top-k score (DS2I_OP_TOPK_DOCS; such a batch reports no counters)
+    void collect_docs(bool on) {
+        if (on && !ranked()) throw std::invalid_argument("collect_docs: and / or have no top-k");
+        m_docs = on;
+    }
     static constexpr bool ranked() { return OP >= DS2I_OP_RANKED_AND; }
 
 private:
     uint32_t m_k;
-    bool m_counters = false;
+    bool m_counters = false, m_docs = false;
     std::vector<uint64_t> m_counts;
     std::vector<std::vector<float>> m_topk;
+    std::vector<std::vector<uint32_t>> m_topk_docs;
     ds2i_hip_stats m_stats{};
 };
 
@@ -151,6 +173,7 @@ public:
     struct result {
         std::vector<uint64_t> counts;
         std::vector<float> topk; // nq * k, descending per query, padded with -inf (ranked operators)
+        std::vector<uint32_t> topk_docs; // nq * k doc-ids of topk, padded with 0xFFFFFFFF (tickets submitted with DS2I_OP_TOPK_DOCS; else empty)
         std::vector<uint32_t> topk_len;
         ds2i_hip_stats stats{};
     };
@@ -176,6 +199,8 @@ public:
         check(ds2i_hip_pipeline_submit(m_h, op, k, terms.data(), offs.data(), (uint32_t)nq, &ticket), "ds2i_hip_pipeline_submit");
         if (m_meta.size() <= ticket % m_depth) m_meta.resize(m_depth);
         m_meta[ticket % m_depth] = {(uint32_t)nq, ((op & 0xFF) >= DS2I_OP_RANKED_AND) ? k : 1u};
+        if (m_docs.size() < m_depth) m_docs.resize(m_depth);
+        m_docs[ticket % m_depth] = (op & DS2I_OP_TOPK_DOCS) != 0;
         return ticket;
     }
     void set_instrumented(bool on) { check(ds2i_hip_pipeline_set_instrumented(m_h, on ? 1 : 0), "ds2i_hip_pipeline_set_instrumented"); }
@@ -185,7 +210,10 @@ public:
         r.counts.assign(meta.first, 0);
         r.topk.assign((size_t)meta.first * meta.second, -std::numeric_limits<float>::infinity());
         r.topk_len.assign(meta.first, 0);
-        check(ds2i_hip_pipeline_wait(m_h, ticket, r.counts.data(), r.topk.data(), r.topk_len.data(), &r.stats), "ds2i_hip_pipeline_wait");
+        if (m_docs.at(ticket % m_depth)) r.topk_docs.assign((size_t)meta.first * meta.second, 0xFFFFFFFFu);
+        check(ds2i_hip_pipeline_wait_docs(m_h, ticket, r.counts.data(), r.topk.data(), r.topk_docs.empty() ? nullptr : r.topk_docs.data(),
+                                          r.topk_len.data(), &r.stats),
+              "ds2i_hip_pipeline_wait");
         return r;
     }
 
@@ -193,6 +221,7 @@ private:
     ds2i_hip_pipeline* m_h = nullptr;
     uint32_t m_depth;
     std::vector<std::pair<uint32_t, uint32_t>> m_meta;
+    std::vector<char> m_docs; // per slot: the ticket was submitted with DS2I_OP_TOPK_DOCS
 };
 
 // ---- several devices of one node. The path shards by QUERY: every device holds a full replica of the
@@ -262,8 +291,10 @@ public:
         if (ntickets <= 1) { // one ticket: inline, through the one-shot call of replica 0
             if (m_ops.empty()) m_ops.assign(1, gpu_query_op<OP>(m_k));
             m_ops[0].collect_counters(m_counters);
+            m_ops[0].collect_docs(m_docs);
             m_counts = m_ops[0](set.replica(0), queries);
             m_topk = m_ops[0].topk_batch();
+            m_topk_docs = m_ops[0].topk_docs_batch();
             m_stats = m_ops[0].stats();
             return m_counts;
         }
@@ -274,7 +305,9 @@ public:
         }
         m_counts.assign(n, 0);
         m_topk.assign(n, std::vector<float>());
+        m_topk_docs.assign(m_docs ? n : 0, std::vector<uint32_t>());
         const uint32_t k = ranked() ? (uint32_t)m_k : 1u;
+        const int op = OP | (m_docs ? DS2I_OP_TOPK_DOCS : 0);
         std::atomic<size_t> next(0);
         std::vector<std::string> errors(parts);
         std::vector<ds2i_hip_stats> stats(parts, ds2i_hip_stats{});
@@ -288,7 +321,7 @@ public:
                         const size_t t = next.fetch_add(1);
                         if (t >= ntickets) break;
                         const size_t lo = t * per, hi = std::min(n, lo + per);
-                        inflight.emplace_back(pipe.submit(OP, k, queries.begin() + lo, queries.begin() + hi), lo);
+                        inflight.emplace_back(pipe.submit(op, k, queries.begin() + lo, queries.begin() + hi), lo);
                     }
                     if (inflight.empty()) break;
                     const auto head = inflight.front();
@@ -297,6 +330,7 @@ public:
                     for (size_t i = 0; i < res.counts.size(); ++i) {
                         m_counts[head.second + i] = res.counts[i];
                         if (ranked()) m_topk[head.second + i].assign(res.topk.begin() + i * k, res.topk.begin() + i * k + res.topk_len[i]);
+                        if (m_docs) m_topk_docs[head.second + i].assign(res.topk_docs.begin() + i * k, res.topk_docs.begin() + i * k + res.topk_len[i]);
                     }
                     stats[r].kernel_ms += res.stats.kernel_ms;
                     stats[r].docs_blocks_decoded += res.stats.docs_blocks_decoded;
@@ -320,6 +354,7 @@ public:
                 release();
                 m_counts.clear();
                 m_topk.clear();
+                m_topk_docs.clear();
                 throw std::runtime_error(e);
             }
         for (size_t r = 0; r < parts; ++r) {
@@ -339,8 +374,18 @@ public:
         return m_topk.empty() ? none : m_topk.back();
     }
     std::vector<std::vector<float>> const& topk_batch() const { return m_topk; } // one entry per query (empty for and / or)
+    // the doc-ids of topk() / topk_batch() (collect_docs(true); gpu_query_op::topk_docs): the same ids whatever the replica count
+    std::vector<uint32_t> const& topk_docs() const {
+        static const std::vector<uint32_t> none;
+        return m_topk_docs.empty() ? none : m_topk_docs.back();
+    }
+    std::vector<std::vector<uint32_t>> const& topk_docs_batch() const { return m_topk_docs; }
     ds2i_hip_stats const& stats() const { return m_stats; } // kernel_ms = busiest replica (sum of its tickets' windows), counters summed
     void collect_counters(bool on) { m_counters = on; }
+    void collect_docs(bool on) {
+        if (on && !ranked()) throw std::invalid_argument("collect_docs: and / or have no top-k");
+        m_docs = on;
+    }
     // drops the per-replica pipelines (they hold device buffers of the set's indexes): call it before the set is destroyed if
     // the operator is to outlive it; the next batch creates new ones
     void release() {
@@ -359,12 +404,13 @@ public:
 
 private:
     uint64_t m_k;
-    bool m_counters = false, m_latency = false;
+    bool m_counters = false, m_latency = false, m_docs = false;
     std::vector<gpu_query_op<OP>> m_ops;
     std::vector<std::unique_ptr<gpu_pipeline>> m_pipes;
     uint64_t m_pipes_of = 0; // gpu_index_set::id() the pipelines belong to (0 = none)
     std::vector<uint64_t> m_counts;
     std::vector<std::vector<float>> m_topk;
+    std::vector<std::vector<uint32_t>> m_topk_docs;
     ds2i_hip_stats m_stats{};
 };
 

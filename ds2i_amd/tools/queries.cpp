@@ -7,6 +7,8 @@
 // --gpus N: N replicas of the index, one per device (devices are taken round robin, so N may exceed the device count:
 // two replicas on one GPU answer like two GPUs would); every batch is cut into N contiguous slices, one host thread
 // and one set of streams per replica (ds2i_hip::gpu_index_set).
+// --dump FILE: the answers, one line per query (operator, result, top-k score bits). --dump-docs FILE: the ranked operators'
+// top-k with doc-ids (DS2I_OP_TOPK_DOCS), one line per query: operator, top-k length, then docid:scorebits pairs (scores in hex).
 // Where the reference times one query at a time on one core (op_perftest, queries.cpp:13-62), this driver
 // sends the whole log through the batched C ABI: 1 untimed + 2 timed passes; "avg" = batch time / queries.
 // Quantiles come from a latency pass that submits (a sample of) the queries one per call.
@@ -20,6 +22,7 @@
 using namespace ds2i_hip;
 
 static FILE* g_dump = nullptr;
+static FILE* g_dump_docs = nullptr;
 
 template <class Index, class Op>
 void op_perftest(Index const& index, Op&& op, std::vector<term_id_vec> const& queries, std::string const& type,
@@ -62,6 +65,18 @@ void op_perftest(Index const& index, Op&& op, std::vector<term_id_vec> const& qu
             std::fprintf(g_dump, "\n");
         }
     }
+    if (g_dump_docs && op.ranked()) { // --dump-docs <file>: ranked operators, one line per query: operator, top-k length, doc-id:score bits
+        op.collect_docs(true);
+        op(index, queries);
+        op.collect_docs(false);
+        for (size_t q = 0; q < queries.size(); ++q) {
+            auto const& sc = op.topk_batch()[q];
+            auto const& ids = op.topk_docs_batch()[q];
+            std::fprintf(g_dump_docs, "%s %zu", query_type.c_str(), sc.size());
+            for (size_t i = 0; i < sc.size(); ++i) { uint32_t b; std::memcpy(&b, &sc[i], 4); std::fprintf(g_dump_docs, " %u:%08x", ids[i], b); }
+            std::fprintf(g_dump_docs, "\n");
+        }
+    }
     auto quantile = [&](size_t pct) { return lat[std::min(lat.size() - 1, pct * lat.size() / 100)]; };
     const double q50 = quantile(50), q90 = quantile(90), q95 = quantile(95);
     std::ostringstream os;
@@ -83,6 +98,7 @@ int main(int argc, const char** argv) {
     for (int i = 0; i < argc; ++i) {
         if (std::string(argv[i]) == "--gpus" && i + 1 < argc) { gpus = std::max(1, std::atoi(argv[++i])); continue; }
         if (std::string(argv[i]) == "--dump" && i + 1 < argc) { g_dump = std::fopen(argv[++i], "w"); continue; }
+        if (std::string(argv[i]) == "--dump-docs" && i + 1 < argc) { g_dump_docs = std::fopen(argv[++i], "w"); continue; }
         pos.push_back(argv[i]);
     }
     argc = (int)pos.size();
@@ -135,5 +151,6 @@ int main(int argc, const char** argv) {
         return 2;
     }
     if (g_dump) std::fclose(g_dump);
+    if (g_dump_docs) std::fclose(g_dump_docs);
     return 0;
 }

@@ -52,7 +52,16 @@ enum ds2i_hip_op {
     DS2I_OP_REFERENCE_ORDER = 0x100,
     /* OR this flag into the operator of ds2i_hip_query_batch / ds2i_hip_pipeline_submit to run the kernels compiled
        without the statistics counters even though a stats struct is passed (it then carries kernel_ms only). */
-    DS2I_OP_NO_COUNTERS = 0x200
+    DS2I_OP_NO_COUNTERS = 0x200,
+    /* OR this flag into a ranked operator (ranked_and / wand / maxscore / ranked_or) of ds2i_hip_batch_prepare,
+       ds2i_hip_pipeline_submit or ds2i_hip_query_batch_docs to get the doc-id of every top-k score as well
+       (ds2i_hip_batch_fetch_topk_docs / ds2i_hip_pipeline_wait_docs). Each row is ordered by score descending, equal
+       scores by doc-id ascending, and holds the k largest (score, -doc-id) pairs: on a tie at the k-th place the smaller
+       doc-ids are returned. Entries past the row's length are 0xFFFFFFFF. Scores, lengths and counts are the same bits as
+       without the flag. With and / and_freq / or / or_freq, or with ds2i_hip_query_batch: DS2I_EINVAL. A docs batch
+       reports no counters, as with DS2I_OP_NO_COUNTERS (stats carry kernel_ms only; its kernels are the uninstrumented
+       instantiations wherever a kernel has one), and ds2i_hip_batch_enable_block_profile refuses it (DS2I_EINVAL). */
+    DS2I_OP_TOPK_DOCS = 0x400
 };
 
 enum ds2i_hip_error {
@@ -162,6 +171,10 @@ int ds2i_hip_decode_list(ds2i_hip_index* idx, uint32_t term, uint32_t* docs, uin
 int ds2i_hip_query_batch(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t* terms,
                          const uint32_t* query_offsets, uint32_t nq, uint64_t* out_count, float* out_topk,
                          uint32_t* out_topk_len, ds2i_hip_stats* stats);
+/* ds2i_hip_query_batch with DS2I_OP_TOPK_DOCS in op (required): out_topk_docs has nq*k entries */
+int ds2i_hip_query_batch_docs(ds2i_hip_index* idx, int op, uint32_t k, const uint32_t* terms,
+                              const uint32_t* query_offsets, uint32_t nq, uint64_t* out_count, float* out_topk,
+                              uint32_t* out_topk_docs, uint32_t* out_topk_len, ds2i_hip_stats* stats);
 
 /* Split form: prepare() does query normalisation (query_freqs / remove_duplicate_terms,
  * queries.hpp:29-33,136-150), BM25 query weights, list-length ordering and uploads everything;
@@ -204,6 +217,8 @@ int ds2i_hip_batch_fetch(ds2i_hip_batch* b, uint64_t* out_count, float* out_topk
 /* doc-id lists of `and` (want_matches): match_offsets has nq+1 entries; matches has match_offsets[nq] */
 int ds2i_hip_batch_match_total(ds2i_hip_batch* b, uint64_t* total);
 int ds2i_hip_batch_fetch_matches(ds2i_hip_batch* b, uint64_t* match_offsets, uint32_t* matches);
+/* doc-ids of the top-k (DS2I_OP_TOPK_DOCS): nq*k entries, same layout as out_topk; DS2I_EINVAL on a batch prepared without the flag */
+int ds2i_hip_batch_fetch_topk_docs(ds2i_hip_batch* b, uint32_t* out_docs);
 void ds2i_hip_batch_free(ds2i_hip_batch* b);
 
 /* Pipelined form -- the serving loop. A pipeline owns `depth` reusable batch slots. submit() does the host half of
@@ -220,6 +235,11 @@ int ds2i_hip_pipeline_submit(ds2i_hip_pipeline* p, int op, uint32_t k, const uin
                              const uint32_t* query_offsets, uint32_t nq, uint64_t* ticket);
 int ds2i_hip_pipeline_wait(ds2i_hip_pipeline* p, uint64_t ticket, uint64_t* out_count, float* out_topk,
                            uint32_t* out_topk_len, ds2i_hip_stats* stats);
+/* wait() with the doc-ids of a ticket submitted with DS2I_OP_TOPK_DOCS (out_topk_docs: nq*k entries, or NULL). A ticket
+ * submitted without the flag and a non-NULL out_topk_docs: DS2I_EINVAL, and the ticket stays uncollected. Plain wait()
+ * on a docs ticket returns its scores and drops the ids. */
+int ds2i_hip_pipeline_wait_docs(ds2i_hip_pipeline* p, uint64_t ticket, uint64_t* out_count, float* out_topk,
+                                uint32_t* out_topk_docs, uint32_t* out_topk_len, ds2i_hip_stats* stats);
 /* like ds2i_hip_batch_class_stats, for the ticket collected last */
 int ds2i_hip_pipeline_class_stats(ds2i_hip_pipeline* p, int cls, ds2i_hip_stats* out, uint32_t* nqueries);
 int ds2i_hip_pipeline_class_groups(ds2i_hip_pipeline* p, int cls, ds2i_hip_group_stats* out, uint32_t capacity, uint32_t* ngroups);
