@@ -8,6 +8,9 @@ over one FRESH 4096-query batch per GPU, end to end through the public pipelined
 only the index is resident in HBM). K distinct batches are timed, `--depth` of them in flight.
 Rank 0 prints ONE JSON line.
 
+A plain run does only what its headline figure needs: it builds and uploads the index, warms up, times the K steps, writes
+--dump-outputs and prints the line. --full adds every other measurement and check, each after the timed region:
+
   value        whole-job queries/s = (queries all ranks processed) / max-over-ranks wall time
   kernel_resident_qps  the same kernels over ONE prepared batch re-run K times (round 1's figure), beside it
   roofline     the class kernel with the most GPU time: algorithmic bytes (the reference traversal's A_skip,
@@ -84,6 +87,19 @@ def dump_outputs(path, result, ranked, dist, rank, world):
     log("--dump-outputs: %s of the last timed step (%d of %d queries) in %s" % (", ".join(sorted(arrays)), len(arrays["count"]), n, path))
 
 
+def cpu_budget():
+    """-> (CPUs in this process's affinity mask, its cgroup v2 CPU quota in whole CPUs or None)"""
+    ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    quota = None
+    try:  # cgroup v2 cpu.max = "<quota> <period>" or "max <period>"
+        qv, per = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if qv != "max":
+            quota = max(1, int(int(qv) / int(per)))
+    except Exception:  # noqa: BLE001
+        pass
+    return ncores, quota
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -96,12 +112,15 @@ def main():
     ap.add_argument("--codec", default="block_optpfor")
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--k", type=int, default=10, help="results kept per query (the metric is quoted at 10; > 64 runs the big-heap kernels, queries.hpp:152-197)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-oracle", action="store_true", help="skip every oracle leg (A_skip profile, parity sample, cpu baseline)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure and check what the headline figure does not need: the kernel-resident rate, "
+                         "the prepared-batch and instrumented re-runs, per-class kernel times, the oracle legs and the roofline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-oracle", action="store_true", help="--full: skip every oracle leg (A_skip profile, parity sample, cpu baseline)")
     ap.add_argument("--depth", type=int, default=3, help="batches in flight in the pipelined timed region")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="N>1: weak = every rank its own 4096-query batches; strong = one stream of batches cut into N slices")
-    ap.add_argument("--traffic-json", default=None, help="rocprofv3 --pmc derived HBM bytes per launch (profiles/*.json)")
+    ap.add_argument("--traffic-json", default=None, help="--full: rocprofv3 --pmc derived HBM bytes per launch (profiles/*.json)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write the answer of the last timed step (what Pipeline.wait returned) as DIR/<name>.npy, for comparing two "
                          "builds output for output; pass --workload too so that the collection does not hang on the host's build rate")
@@ -131,7 +150,10 @@ def main():
 
     # ---------------------------------------------------------------- workload
     wl = args.workload
-    threads = max(1, (os.cpu_count() or 8))
+    # the builders take one thread per CPU this process may use: threads beyond a cgroup quota only get throttled (a GOV2-scale
+    # build under a 16-CPU quota took 17.0 s on one thread per visible CPU, 256, and 12.9 s on 16; the image does not depend on it)
+    ncores, quota = cpu_budget()
+    threads = max(1, min(ncores, quota or ncores))
     if wl == "auto":
         # probe the host's index-build rate; GOV2-scale (~1 B postings) must build in ~2 minutes
         if rank == 0:
@@ -203,7 +225,8 @@ def main():
     # Every step is a FRESH batch through the public pipelined ABI: host-side query normalisation + BM25 query weights
     # + work-unit planning, H2D of the plan, kernels, merge, D2H of the results. Nothing is pre-staged. `depth` batches
     # are in flight: the host plans batch i+1 while batch i runs. The kernels are the uninstrumented instantiations
-    # (statistics are a compile-time option, like the reference's block_profiler).
+    # (statistics are a compile-time option, like the reference's block_profiler). Every run reads the per-class kernel times
+    # as it reaps a batch, whether or not --full reports them, so that --full times the same steps as a plain run.
     def run_stream(first, n, collect):
         tickets, results, cls_ms = [], [], [[0.0, 0] for _ in range(NCLS)]
         def reap():
@@ -259,38 +282,40 @@ def main():
     # the workload's as much as the machine's), carried over to `value` as a relative +-
     rel_ci = float(1.96 * steady.std(ddof=1) / np.sqrt(len(steady)) / steady.mean()) if len(steady) > 2 else None
 
-    # ---- untimed extras: kernel-resident rate (one prepared batch re-run, round-1's figure) and the instrumented pass
-    batch = d.Batch(idx, args.op, my_queries[args.warmup], k=args.k)
-    batch.set_instrumented(False)
-    batch.run()
-    first_res_ms = [batch.class_stats(c)[0].kernel_ms for c in range(NCLS)]
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    res_ms = [0.0] * NCLS
-    res_grp_ms = {}
-    for _ in range(args.steps):
-        batch.run()
-        for c in range(NCLS):
-            res_ms[c] += batch.class_stats(c)[0].kernel_ms
-            for g in batch.class_groups(c):
-                acc = res_grp_ms.setdefault((c, g["lists"], g["pipelined_stream"]), [0.0, 0])
-                acc[0] += g["kernel_ms"]
-                acc[1] += 1
-    torch.cuda.synchronize()
-    resident_s = (time.perf_counter() - t1) / args.steps
-    count_r, topk_r, tlen_r, _ = batch.fetch()
-    conj = args.op in ("and", "and_freq", "ranked_and")
     if args.op in ("and", "and_freq", "or", "or_freq"):  # no top-k: counts only
-        topk = topk_r = np.zeros((len(count), 1), dtype=np.float32)
-    fin = np.isfinite(topk_r)
-    # every operator is bit-stable from run to run (the disjunctive kernel sums term scores in fixed point, so the order
-    # its parts meet a document's terms in does not show)
-    same = np.array_equal(topk, topk_r)
-    assert np.array_equal(count, count_r) and np.array_equal(tlen, tlen_r) and same, "pipelined / prepared-batch results disagree"
-    batch.set_instrumented(True)
-    batch.run()
-    count_i, topk_i, tlen_i, _ = batch.fetch()
-    assert np.array_equal(count, count_i) and np.array_equal(tlen, tlen_i), "instrumented / uninstrumented kernels disagree"
+        topk = np.zeros((len(count), 1), dtype=np.float32)
+
+    if args.full:
+        # ---- untimed extras: kernel-resident rate (one prepared batch re-run, round-1's figure) and the instrumented pass
+        batch = d.Batch(idx, args.op, my_queries[args.warmup], k=args.k)
+        batch.set_instrumented(False)
+        batch.run()
+        first_res_ms = [batch.class_stats(c)[0].kernel_ms for c in range(NCLS)]
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        res_ms = [0.0] * NCLS
+        res_grp_ms = {}
+        for _ in range(args.steps):
+            batch.run()
+            for c in range(NCLS):
+                res_ms[c] += batch.class_stats(c)[0].kernel_ms
+                for g in batch.class_groups(c):
+                    acc = res_grp_ms.setdefault((c, g["lists"], g["pipelined_stream"]), [0.0, 0])
+                    acc[0] += g["kernel_ms"]
+                    acc[1] += 1
+        torch.cuda.synchronize()
+        resident_s = (time.perf_counter() - t1) / args.steps
+        count_r, topk_r, tlen_r, _ = batch.fetch()
+        if args.op in ("and", "and_freq", "or", "or_freq"):  # counts only, as above
+            topk_r = topk
+        # every operator is bit-stable from run to run (the disjunctive kernel sums term scores in fixed point, so the order
+        # its parts meet a document's terms in does not show)
+        same = np.array_equal(topk, topk_r)
+        assert np.array_equal(count, count_r) and np.array_equal(tlen, tlen_r) and same, "pipelined / prepared-batch results disagree"
+        batch.set_instrumented(True)
+        batch.run()
+        count_i, topk_i, tlen_i, _ = batch.fetch()
+        assert np.array_equal(count, count_i) and np.array_equal(tlen, tlen_i), "instrumented / uninstrumented kernels disagree"
     if strong:  # the gathered answer of the first timed batch must be the whole batch, in order
         g_count = sh.gather_concat(dist, rank, world, count)
         g_topk = sh.gather_concat(dist, rank, world, topk)
@@ -309,16 +334,6 @@ def main():
     per_rank_q = (hi_ - lo_) if strong else args.batch
     total_q = (args.batch if strong else args.batch * world) * args.steps
     qps = total_q / elapsed
-    cls_stats = [batch.class_stats(c) for c in range(NCLS)]
-    mean_ms = [cls_ms[c][0] / cls_ms[c][1] if cls_ms[c][1] else 0.0 for c in range(NCLS)]
-    dom = max(range(NCLS), key=lambda c: cls_ms[c][0])  # provisional: re-chosen below by algorithmic bytes when the oracle ran
-    for c in range(NCLS):
-        log("class %d: %d queries, kernel %.3f ms/launch in the pipelined region (%.3f ms alone), %s"
-            % (c, cls_stats[c][1], mean_ms[c], res_ms[c] / args.steps, cls_stats[c][0].as_dict()))
-        pc = batch.phase_cycles(c)
-        if pc["total"]:
-            log("   phase cycles (diagnostic build): " + ", ".join("%s %.1f%%" % (k, 100.0 * v / pc["total"]) for k, v in pc.items()))
-    dom_ms = mean_ms[dom]
     out = {
         "metric": "queries/sec (%s, %s)" % (args.op, args.codec), "value": qps, "unit": "queries/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -330,8 +345,6 @@ def main():
                   "%d in flight" % (args.steps, args.depth),
         "host_submit_ms_per_step": host_submit_ms,  # the caller's thread inside submit: when this approaches ms_per_step the step is host-bound
         "first_batch_checksum": checksum,
-        "kernel_resident_qps": per_rank_q * world / resident_s,  # one prepared batch re-run (rank 0's rate x ranks)
-        "end_to_end_over_resident": qps / (per_rank_q * world / resident_s),
         "config": {"workload": "%s, %s, %s, batch=%d" % (W["label"], args.codec, args.op, args.batch), "num_docs": W["num_docs"], "postings": int(postings), "index_bytes": len(img),
                    "batch_per_gpu": per_rank_q, "k": args.k, "parallelism": "query-batch sharding x%d (%s), index replicated" % (world, args.scaling)},
     }
@@ -340,6 +353,23 @@ def main():
     if info["transcoded_from"] >= 0:  # block_mixed / opt / ef / single / uniform: decoded once at upload, queried as block_optpfor + side tables
         out["config"]["upload"] = ("%s image transcoded to block_optpfor at upload (DS2I_MIXED_NATIVE=1 / DS2I_PEF_NATIVE=1 "
                                    "query the image as it is)" % args.codec)
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    out["kernel_resident_qps"] = per_rank_q * world / resident_s  # one prepared batch re-run (rank 0's rate x ranks)
+    out["end_to_end_over_resident"] = qps / (per_rank_q * world / resident_s)
+    cls_stats = [batch.class_stats(c) for c in range(NCLS)]
+    mean_ms = [cls_ms[c][0] / cls_ms[c][1] if cls_ms[c][1] else 0.0 for c in range(NCLS)]
+    dom = max(range(NCLS), key=lambda c: cls_ms[c][0])  # provisional: re-chosen below by algorithmic bytes when the oracle ran
+    for c in range(NCLS):
+        log("class %d: %d queries, kernel %.3f ms/launch in the pipelined region (%.3f ms alone), %s"
+            % (c, cls_stats[c][1], mean_ms[c], res_ms[c] / args.steps, cls_stats[c][0].as_dict()))
+        pc = batch.phase_cycles(c)
+        if pc["total"]:
+            log("   phase cycles (diagnostic build): " + ", ".join("%s %.1f%%" % (k, 100.0 * v / pc["total"]) for k, v in pc.items()))
+    dom_ms = mean_ms[dom]
 
     # ---------------------------------------------------------------- oracle legs (rank 0 only; the only place this file touches oracle/)
     cls_of = lambda n: 0 if n <= 2 else 1 if n <= 4 else 2 if n <= 8 else 3 if n <= 16 else 4
@@ -413,15 +443,7 @@ def main():
             # N = the CPUs this process may actually use (affinity mask, cgroup quota), i.e. physical cores when the
             # container is granted them.
             import threading
-            ncores = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
-            quota = None
-            try:  # cgroup v2 cpu.max = "<quota> <period>" or "max <period>"
-                qv, per = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
-                if qv != "max":
-                    quota = max(1, int(int(qv) / int(per)))
-            except Exception:  # noqa: BLE001
-                pass
-            nthreads = max(1, min(ncores, quota or ncores, 256))
+            nthreads = min(threads, 256)
             per_thread = max(16, min(nsample // 4, len(queries)))
             slices = [[queries[(t * per_thread + i) % len(queries)] for i in range(per_thread)] for t in range(nthreads)]
             errs = []

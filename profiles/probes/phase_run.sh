@@ -2,5 +2,5 @@
 export TMPDIR=/tmp
 cp ds2i_amd/libds2i_hip.so /tmp/orig.so
 cp profiles/tmp_libs/lib_phase.so ds2i_amd/libds2i_hip.so
-python bench.py --workload gov2 --steps 3 --warmup 1 --no-oracle "$@" 2>&1 | grep -E "^class|phase cycles" | cut -c1-400
+python bench.py --full --workload gov2 --steps 3 --warmup 1 --no-oracle "$@" 2>&1 | grep -E "^class|phase cycles" | cut -c1-400
 cp /tmp/orig.so ds2i_amd/libds2i_hip.so

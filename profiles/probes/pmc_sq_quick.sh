@@ -6,7 +6,7 @@ OUT=gpurun_out/pmc_sq_quick
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_LDS --output-format csv -d $OUT/pmc -o pmc -- \
-    python bench.py --workload gov2 --op $OP --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/pmc.err
+    python bench.py --full --workload gov2 --op $OP --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/pmc.err
 python - "$OUT" <<'PY'
 import csv, glob, collections, sys
 out = sys.argv[1]
@@ -23,7 +23,7 @@ for (k, n), v in sorted(agg.items()):
 print("per batch:", {n: "%.4g" % v for n, v in tot.items()}, "SALU/VALU %.3f" % (tot["SQ_INSTS_SALU"] / max(1.0, tot["SQ_INSTS_VALU"])))
 PY
 rm -rf $OUT/pmc
-python bench.py --workload gov2 --op $OP --steps 30 --warmup 4 --no-oracle 2>/dev/null | python -c "
+python bench.py --full --workload gov2 --op $OP --steps 30 --warmup 4 --no-oracle 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$OP', round(d['value']), round(d['ms_per_step'],2), d['step_ms_spread'])"

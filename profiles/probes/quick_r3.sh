@@ -4,7 +4,7 @@ OUT=gpurun_out/${1:-r03_q}
 mkdir -p $OUT
 timeout 1500 python -m pytest tests/test_gpu.py -m gpu -x -q -k "${2:-query_ops or fuzz or full_size_c2 or prun or uninstrumented or topk or long_queries or alternative or block_mixed_image}" > $OUT/tests.log 2>&1
 tail -5 $OUT/tests.log
-python bench.py --workload gov2 --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --workload gov2 --steps 10 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 grep -E "^class|postings|docs_blocks" $OUT/bench.err | cut -c1-300 | head -20
 python - <<PY
 import json

@@ -4,7 +4,7 @@ OUT=gpurun_out/${1:-r04_q}
 mkdir -p $OUT
 timeout 1500 python -m pytest tests/test_gpu.py -m gpu -x -q -k "${2:-query_ops or fuzz or full_size_c2_prop or prun or uninstrumented or topk or alternative}" > $OUT/tests.log 2>&1
 tail -5 $OUT/tests.log
-python bench.py --workload gov2 --steps ${3:-20} --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --workload gov2 --steps ${3:-20} --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 grep -E "^class|postings|docs_blocks" $OUT/bench.err | cut -c1-300 | head -20
 python - <<PY
 import json

@@ -8,7 +8,7 @@ bash profiles/probes/run_r4_prof.sh r04 gov2 ranked_and > gpurun_out/r04_close/p
 tail -25 gpurun_out/r04_close/prof.log
 OUT=gpurun_out/prof_r04_wand; mkdir -p $OUT
 timeout 420 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- \
-    python bench.py --workload gov2 --op wand --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/pmc_fetch.err
+    python bench.py --full --workload gov2 --op wand --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/pmc_fetch.err
 python - "$OUT" fetch <<'PY'
 import csv, glob, collections, sys
 out, name = sys.argv[1], sys.argv[2]

@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/r04_hints_all; mkdir -p $OUT
 timeout 1500 python -m pytest tests/test_gpu.py -m gpu -x -q -k "fuzz or query_ops or prun or full_size_c2 or brute or mixed" > $OUT/tests.log 2>&1; tail -4 $OUT/tests.log
-one() { name=$1; shift; python bench.py "$@" --steps 30 --warmup 4 --no-oracle 2>/dev/null | python -c "
+one() { name=$1; shift; python bench.py --full "$@" --steps 30 --warmup 4 --no-oracle 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$name', round(d['value']), round(d['ms_per_step'],2), [(k['kernel'][:22], round(k['ms_per_launch'],2)) for k in d['roofline']['per_kernel']])"; }
@@ -11,6 +11,6 @@ one gov2_and_freq --workload gov2 --op and_freq
 one gov2_opt --workload gov2 --codec opt
 one cw09_mixed_fixed --workload cw09 --codec block_mixed --mixed-policy fixed
 one cw09_mixed_optimised --workload cw09 --codec block_mixed --mixed-policy optimised
-DS2I_NO_RANKED_STREAM=1 python bench.py --workload cw09 --codec block_mixed --mixed-policy fixed --steps 30 --warmup 4 --no-oracle 2>/dev/null | python -c "
+DS2I_NO_RANKED_STREAM=1 python bench.py --full --workload cw09 --codec block_mixed --mixed-policy fixed --steps 30 --warmup 4 --no-oracle 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('cw09_mixed_fixed class kernels only', round(d['value']), round(d['ms_per_step'],2))"

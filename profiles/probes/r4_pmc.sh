@@ -10,7 +10,7 @@ for PASS in "sq:SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAV
             "fetch:FETCH_SIZE"; do
   NAME=${PASS%%:*}; CTRS=${PASS#*:}
   timeout 300 rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT/pmc_$NAME -o pmc -- \
-      python bench.py --workload gov2 --op $OP --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/pmc_$NAME.err
+      python bench.py --full --workload gov2 --op $OP --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/pmc_$NAME.err
   python - "$OUT" "$NAME" <<'PY'
 import csv, glob, collections, sys
 out, name = sys.argv[1], sys.argv[2]

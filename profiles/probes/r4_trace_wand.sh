@@ -1,7 +1,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/r04_trace; rm -rf $OUT; mkdir -p $OUT
 OP=${1:-wand}
-timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/kt -o kt -- python bench.py --workload gov2 --op $OP --steps 12 --warmup 3 --no-oracle > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/kt -o kt -- python bench.py --full --workload gov2 --op $OP --steps 12 --warmup 3 --no-oracle > $OUT/bench.json 2> $OUT/bench.err
 python - "$OUT" <<'PY'
 import csv, glob, sys
 out = sys.argv[1]

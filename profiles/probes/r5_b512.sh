@@ -1,7 +1,7 @@
 #!/bin/bash
 # Usage (GPU box): bash profiles/probes/r5_b512.sh  -- strong-scaling proxy: the per-GPU share (512 queries) of a 4096-query batch over 8 GPUs, knob sweep
 export TMPDIR=/tmp
-run() { echo "== $*"; env "$@" python bench.py --workload gov2 --batch 512 --steps 80 --warmup 8 --no-oracle $EXTRA 2>/dev/null | python -c "
+run() { echo "== $*"; env "$@" python bench.py --full --workload gov2 --batch 512 --steps 80 --warmup 8 --no-oracle $EXTRA 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), round(d['ms_per_step'],3), 'resident', round(d.get('kernel_resident_qps',0)), d.get('step_ms_spread'))"; }

@@ -1,6 +1,6 @@
 #!/bin/bash
 export TMPDIR=/tmp
-run() { echo "== $* $EXTRA"; env "$@" python bench.py --workload gov2 --batch 512 --no-oracle $EXTRA 2>/dev/null | python -c "
+run() { echo "== $* $EXTRA"; env "$@" python bench.py --full --workload gov2 --batch 512 --no-oracle $EXTRA 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), round(d['ms_per_step'],3), 'resident', round(d.get('kernel_resident_qps',0)), d.get('step_ms_spread'))"; }

@@ -3,7 +3,7 @@
 # default bench (GOV2 scale, ranked_and), resident bytes beside the rate
 export TMPDIR=/tmp
 mkdir -p gpurun_out/r5_budget
-run() { env "$@" python bench.py --no-oracle --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | python -c "
+run() { env "$@" python bench.py --full --no-oracle --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), 'q/s', round(d['ms_per_step'],3), 'ms/step', round(d['config'].get('device_bytes',0)/1e9,2), 'GB resident')"; }

@@ -16,7 +16,7 @@ except Exception as e:
     print(sys.argv[2], "FAILED", e)
 PY
 }
-bench() { name=$1; shift; timeout 400 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; line $OUT/bench_$name.json $name; }
+bench() { name=$1; shift; timeout 400 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; line $OUT/bench_$name.json $name; }
 T0=$(date +%s)
 bench gov2_opt --workload gov2 --codec opt --steps 30 --warmup 3
 bench gov2_opt_wand --workload gov2 --codec opt --op wand --steps 30 --warmup 3 --no-oracle
@@ -28,7 +28,7 @@ bench gov2_b2048 --batch 2048 --depth 4 --steps 80 --warmup 20 --no-oracle
 echo "t=$(( $(date +%s) - T0 ))s"
 bench cw09_optpfor --workload cw09 --codec block_optpfor --steps 30 --warmup 3
 bench cw09_mixed_fixed --workload cw09 --codec block_mixed --mixed-policy fixed --steps 30 --warmup 3 --no-oracle
-DS2I_MIXED_NATIVE=1 timeout 400 python bench.py --workload cw09 --codec block_mixed --mixed-policy fixed --steps 30 --warmup 3 --no-oracle > $OUT/bench_cw09_mixed_fixed_native.json 2> $OUT/bench_cw09_mixed_fixed_native.err; line $OUT/bench_cw09_mixed_fixed_native.json cw09_mixed_fixed_native
+DS2I_MIXED_NATIVE=1 timeout 400 python bench.py --full --workload cw09 --codec block_mixed --mixed-policy fixed --steps 30 --warmup 3 --no-oracle > $OUT/bench_cw09_mixed_fixed_native.json 2> $OUT/bench_cw09_mixed_fixed_native.err; line $OUT/bench_cw09_mixed_fixed_native.json cw09_mixed_fixed_native
 echo "t=$(( $(date +%s) - T0 ))s"
 bench cw09_mixed_optimised --workload cw09 --codec block_mixed --mixed-policy optimised --steps 30 --warmup 3 --no-oracle
 grep -i "upload\|built" $OUT/bench_cw09_mixed_fixed.err $OUT/bench_cw09_mixed_fixed_native.err | head -6

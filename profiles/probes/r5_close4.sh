@@ -9,7 +9,7 @@ T0=$(date +%s)
 timeout 800 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -6 $OUT/pytest_gpu.log
 echo "t=$(( $(date +%s) - T0 ))s"
 timeout 100 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $OUT/smoke.log
-run() { env "$@" timeout 120 python bench.py --no-oracle --steps 60 --warmup 5 2>$OUT/bench_$1.err | tee $OUT/bench_$1.json | python -c "
+run() { env "$@" timeout 120 python bench.py --full --no-oracle --steps 60 --warmup 5 2>$OUT/bench_$1.err | tee $OUT/bench_$1.json | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), 'q/s', round(d['ms_per_step'],3), 'ms/step')"; grep "^class 2" $OUT/bench_$1.err | cut -c1-110; }

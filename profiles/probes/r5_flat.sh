@@ -2,7 +2,7 @@
 # Usage (GPU box): bash profiles/probes/r5_flat.sh -- equal stream priorities (the default since round 5) against DS2I_CLASS_PRIORITY=1, per operator
 export TMPDIR=/tmp
 mkdir -p gpurun_out/r5_flat
-run() { python bench.py --no-oracle --no-cpu-baseline "$@" 2>/dev/null | python -c "
+run() { python bench.py --full --no-oracle --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(d['value']), round(d['ms_per_step'],3), 'resident', round(d.get('kernel_resident_qps',0)))"; }

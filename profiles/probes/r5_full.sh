@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests -x -q -m gpu > $OUT/pytest.txt 2>&1
 tail -6 $OUT/pytest.txt
-python bench.py --steps 60 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 60 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
 python - <<'PY' $OUT
 import json,sys
 d=json.loads(open(sys.argv[1]+"/bench_default.json").read().strip().splitlines()[-1])

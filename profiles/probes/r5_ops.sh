@@ -7,7 +7,7 @@ OUT=gpurun_out/r5_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 for op in $OPS; do
-  python bench.py --steps 20 --warmup 3 --op $op --no-cpu-baseline --no-oracle > $OUT/bench_$op.json 2> $OUT/bench_$op.err
+  python bench.py --full --steps 20 --warmup 3 --op $op --no-cpu-baseline --no-oracle > $OUT/bench_$op.json 2> $OUT/bench_$op.err
   python - $OUT/bench_$op.json $op <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

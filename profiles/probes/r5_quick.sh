@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu.py -x -q -m gpu -k "decode_every_list or adversarial or exception_count_sweep or fuzz_bit_identical or test_query_ops_match_oracle or gov2_scale_properties or uninstrumented" > $OUT/pytest.txt 2>&1
 tail -15 $OUT/pytest.txt
-python bench.py --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
 tail -3 $OUT/bench_default.err
 python - <<'PY' $OUT
 import json,sys

@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu.py -x -q -m gpu -k "transcoded or without_side_tables or both_decoders or test_query_ops_match_oracle or fuzz_bit_identical or partition_shapes or recovers" > $OUT/pytest.txt 2>&1
 tail -8 $OUT/pytest.txt
-python bench.py --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline > $OUT/bench_default.json 2> $OUT/bench_default.err
 python - <<'PY' $OUT
 import json,sys
 d=json.loads(open(sys.argv[1]+"/bench_default.json").read().strip().splitlines()[-1])

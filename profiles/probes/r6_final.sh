@@ -15,7 +15,7 @@ except Exception as e:
     print(sys.argv[2], "FAILED", e)
 PY
 }
-bench() { name=$1; shift; timeout 900 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; line $OUT/bench_$name.json $name; }
+bench() { name=$1; shift; timeout 900 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; line $OUT/bench_$name.json $name; }
 if [ $PART = ops ]; then
   bench default_gov2 --steps 60 --warmup 5
   for op in wand maxscore ranked_or and and_freq or or_freq; do bench gov2_$op --workload gov2 --op $op --steps 30 --warmup 3; done

@@ -20,21 +20,21 @@ PY
 }
 if [ $PART = g2 ]; then
   for op in ranked_and wand maxscore and and_freq or; do
-    run g4_$op A=1 python bench.py --op $op --no-oracle --steps 40 --warmup 5
-    run g2_$op DS2I_RMW_G=2 python bench.py --op $op --no-oracle --steps 40 --warmup 5
+    run g4_$op A=1 python bench.py --full --op $op --no-oracle --steps 40 --warmup 5
+    run g2_$op DS2I_RMW_G=2 python bench.py --full --op $op --no-oracle --steps 40 --warmup 5
   done
 fi
 if [ $PART = and ]; then
   for extra in A=1 DS2I_UNIT_CAP=8 DS2I_NO_RMH=1 DS2I_RMW_G=1; do
     env DS2I_AND_RSTREAM=1 $extra timeout 300 python profiles/probes/and_rstream_probe.py 1 2 3 > $OUT/and_probe_$extra.txt 2>&1; echo "probe $extra rc=$?"; tail -2 $OUT/and_probe_$extra.txt
   done
-  run and_default A=1 python bench.py --op and --steps 30 --warmup 3
-  run and_rstream DS2I_AND_RSTREAM=1 python bench.py --op and --steps 30 --warmup 3
-  run and_default2 A=1 python bench.py --op and --no-oracle --steps 30 --warmup 3
-  run and_rstream2 DS2I_AND_RSTREAM=1 python bench.py --op and --no-oracle --steps 30 --warmup 3
+  run and_default A=1 python bench.py --full --op and --steps 30 --warmup 3
+  run and_rstream DS2I_AND_RSTREAM=1 python bench.py --full --op and --steps 30 --warmup 3
+  run and_default2 A=1 python bench.py --full --op and --no-oracle --steps 30 --warmup 3
+  run and_rstream2 DS2I_AND_RSTREAM=1 python bench.py --full --op and --no-oracle --steps 30 --warmup 3
 fi
 if [ $PART = prof ]; then
-  timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --steps 60 --warmup 5 > $OUT/prof_bench.json 2> $OUT/prof_bench.err
+  timeout 420 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --full --steps 60 --warmup 5 > $OUT/prof_bench.json 2> $OUT/prof_bench.err
   KS=$(find $OUT/kt -name "*kernel_stats.csv" | head -1); if [ -n "$KS" ]; then cp "$KS" $OUT/kernel_stats.csv; fi; rm -rf $OUT/kt
   head -16 $OUT/kernel_stats.csv
   bash profiles/probes/r5_pmc.sh final ranked_and

@@ -7,10 +7,10 @@ TAG=${1:-r06}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT/ranked_and $OUT/wand
 export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --steps 60 --warmup 5 > $OUT/ranked_and/bench.json 2> $OUT/ranked_and/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --full --steps 60 --warmup 5 > $OUT/ranked_and/bench.json 2> $OUT/ranked_and/bench.err
 KS=$(find $OUT/kt -name "*kernel_stats.csv" | head -1); if [ -n "$KS" ]; then cp "$KS" $OUT/ranked_and/kernel_stats.csv; fi; rm -rf $OUT/kt
 head -14 $OUT/ranked_and/kernel_stats.csv | cut -c1-160
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --op wand --steps 40 --warmup 5 --no-oracle > $OUT/wand/bench.json 2> $OUT/wand/bench.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python bench.py --full --op wand --steps 40 --warmup 5 --no-oracle > $OUT/wand/bench.json 2> $OUT/wand/bench.err
 KS=$(find $OUT/kt -name "*kernel_stats.csv" | head -1); if [ -n "$KS" ]; then cp "$KS" $OUT/wand/kernel_stats.csv; fi; rm -rf $OUT/kt
 head -10 $OUT/wand/kernel_stats.csv | cut -c1-160
 for OP in ranked_and wand; do
@@ -21,7 +21,7 @@ for PASS in "sq1:SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_W
             "fetch:FETCH_SIZE"; do
   NAME=${PASS%%:*}; CTRS=${PASS#*:}
   timeout 300 rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT/pmc_$NAME -o pmc -- \
-      python bench.py --workload gov2 --op $OP --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/$OP/pmc_$NAME.err
+      python bench.py --full --workload gov2 --op $OP --steps 4 --warmup 1 --no-oracle > /dev/null 2> $OUT/$OP/pmc_$NAME.err
   python - "$OUT" "$NAME" "$OP" <<'PY'
 import csv, glob, collections, sys
 out, name, op = sys.argv[1], sys.argv[2], sys.argv[3]

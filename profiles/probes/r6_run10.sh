@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6k}
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="timeout 400 python bench.py --no-oracle --steps 40 --warmup 5"
+B="timeout 400 python bench.py --full --no-oracle --steps 40 --warmup 5"
 for i in 1 2 3; do
   $B --op ranked_and > $OUT/bench_ra_occ6_$i.json 2> $OUT/bench_ra_occ6_$i.err
   DS2I_LIB_VARIANT=occ5 $B --op ranked_and > $OUT/bench_ra_occ5_$i.json 2> $OUT/bench_ra_occ5_$i.err

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout 600 python tests/ranked_stream_probe.py 1 2 > $OUT/ranked_probe.txt 2>&1; echo "ranked probe rc=$?"; tail -1 $OUT/ranked_probe.txt
 timeout 600 python tests/union_stream_probe.py 1 2 > $OUT/union_probe.txt 2>&1; echo "union probe rc=$?"; tail -1 $OUT/union_probe.txt
 timeout 600 python tests/and_stream_probe.py 1 2 > $OUT/and_probe.txt 2>&1; echo "and probe rc=$?"; tail -1 $OUT/and_probe.txt
-B="timeout 400 python bench.py --no-oracle --steps 40 --warmup 5"
+B="timeout 400 python bench.py --full --no-oracle --steps 40 --warmup 5"
 for op in ranked_and wand and and_freq; do $B --op $op > $OUT/bench_$op.json 2> $OUT/bench_$op.err; done
 $B --op ranked_and > $OUT/bench_ranked_and2.json 2> $OUT/bench_ranked_and2.err
 python - $OUT <<'PY'

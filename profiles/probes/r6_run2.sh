@@ -4,7 +4,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 600 python tests/union_stream_probe.py 1 2 3 4 > $OUT/union_probe.txt 2>&1; echo "union probe rc=$?"; tail -3 $OUT/union_probe.txt
 for op in wand ranked_and; do
-  timeout 400 python bench.py --op $op --steps 30 --warmup 3 > $OUT/bench_$op.json 2> $OUT/bench_$op.err; echo "bench $op rc=$?"
+  timeout 400 python bench.py --full --op $op --steps 30 --warmup 3 > $OUT/bench_$op.json 2> $OUT/bench_$op.err; echo "bench $op rc=$?"
 done
 python - $OUT <<'PY'
 import json,sys

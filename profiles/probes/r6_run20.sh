@@ -4,9 +4,9 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python tests/union_stream_probe.py 1 2 > $OUT/union_probe.txt 2>&1; echo "union probe rc=$?"; tail -2 $OUT/union_probe.txt
 for op in wand maxscore ranked_or; do
-timeout 600 python bench.py --op $op --steps 30 --warmup 3 --no-cpu-baseline --no-oracle > $OUT/bench_gov2_$op.json 2> $OUT/bench_gov2_$op.err
+timeout 600 python bench.py --full --op $op --steps 30 --warmup 3 --no-cpu-baseline --no-oracle > $OUT/bench_gov2_$op.json 2> $OUT/bench_gov2_$op.err
 done
-timeout 600 python bench.py --workload gov2c --op wand --steps 30 --warmup 3 --no-cpu-baseline --no-oracle > $OUT/bench_gov2c_wand.json 2> $OUT/bench_gov2c_wand.err
+timeout 600 python bench.py --full --workload gov2c --op wand --steps 30 --warmup 3 --no-cpu-baseline --no-oracle > $OUT/bench_gov2c_wand.json 2> $OUT/bench_gov2c_wand.err
 python - $OUT <<'PY'
 import json,sys,glob
 for f in sorted(glob.glob(sys.argv[1]+"/bench_*.json")):
@@ -15,7 +15,7 @@ for f in sorted(glob.glob(sys.argv[1]+"/bench_*.json")):
         print(f.split("/")[-1], round(d["value"]), "q/s", round(d["ms_per_step"],3), "ms/step", " ".join("%s=%.2f"%(k["kernel"][-7:],k["ms_alone"]) for k in d["roofline"].get("per_kernel",[])))
     except Exception as e: print(f, "FAILED", e)
 PY
-timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python bench.py --workload gov2 --op wand --steps 4 --warmup 1 --no-oracle --no-cpu-baseline > /dev/null 2> $OUT/pmc_fetch.err
+timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o pmc -- python bench.py --full --workload gov2 --op wand --steps 4 --warmup 1 --no-oracle --no-cpu-baseline > /dev/null 2> $OUT/pmc_fetch.err
 python - $OUT <<'PY'
 import csv, glob, collections, sys
 out = sys.argv[1]

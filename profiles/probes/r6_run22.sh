@@ -3,7 +3,7 @@ OUT=gpurun_out/${1:-r6w}
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu.py -x -q -k "pipeline or ticket or index_set or union_through" > $OUT/pytest_subset.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_subset.txt
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 b gov2_b512 --batch 512 --depth 8 --steps 160 --warmup 80
 b gov2_b1024 --batch 1024 --depth 6 --steps 120 --warmup 40
 b gov2_b256 --batch 256 --depth 8 --steps 200 --warmup 80

@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6z}
 mkdir -p $OUT
 export TMPDIR=/tmp
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 for cap in 1 1.5 2 3; do
 export DS2I_POOL_CAP=$cap
 b gov2_b256_cap$cap --batch 256 --depth 8 --steps 200 --warmup 80

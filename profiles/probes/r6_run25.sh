@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6aa}
 mkdir -p $OUT
 export TMPDIR=/tmp
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 for alt in 1 0; do
 if [ $alt = 0 ]; then export DS2I_NO_ALT=1; fi
 b gov2_b256_alt$alt --batch 256 --depth 8 --steps 200 --warmup 80

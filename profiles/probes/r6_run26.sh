@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6ab}
 mkdir -p $OUT
 export TMPDIR=/tmp
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 for ut in 320 160 96; do
 export DS2I_UT_BLOCKS=$ut
 b gov2_wand_b512_ut$ut --op wand --batch 512 --depth 8 --steps 100 --warmup 40

@@ -3,7 +3,7 @@ OUT=gpurun_out/${1:-r6ac}
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 2400 python -m pytest tests -q -m gpu > $OUT/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -6 $OUT/pytest_gpu.txt
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 b gov2_b512 --batch 512 --depth 8 --steps 160 --warmup 80
 python - $OUT <<'PY'
 import json,sys,glob

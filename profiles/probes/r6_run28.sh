@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6ad}
 mkdir -p $OUT
 export TMPDIR=/tmp
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 for aub in 96 48 24; do
 DS2I_AUB=$aub b gov2_and_freq_aub$aub --op and_freq --steps 24 --warmup 3
 done

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu.py -x -q -k "pruning_fuzz or ranked_stream_5_to_8 or and_through or test_query_ops_match_oracle" > $OUT/pytest_subset.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_subset.txt
 DS2I_UNIT_CLOCK=1 timeout 400 python profiles/probes/unit_clock_probe.py wand > $OUT/unit_clock_wand.txt 2>&1; grep -A9 'unit clock' $OUT/unit_clock_wand.txt | head -60
 for op in ranked_and and; do
-  timeout 400 python bench.py --op $op --steps 30 --warmup 3 > $OUT/bench_$op.json 2> $OUT/bench_$op.err; echo "bench $op rc=$?"
+  timeout 400 python bench.py --full --op $op --steps 30 --warmup 3 > $OUT/bench_$op.json 2> $OUT/bench_$op.err; echo "bench $op rc=$?"
 done
 python - $OUT <<'PY'
 import json,sys

@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6af}
 mkdir -p $OUT
 export TMPDIR=/tmp
-b() { name=$1; shift; timeout 600 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 600 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 b wand_multi --op wand --steps 24 --warmup 3
 b ranked_multi --steps 40 --warmup 4
 export DS2I_ONE_STREAM=1

@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6ah}
 mkdir -p $OUT
 export TMPDIR=/tmp
-b() { name=$1; shift; timeout 400 python bench.py "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
+b() { name=$1; shift; timeout 400 python bench.py --full "$@" --no-cpu-baseline --no-oracle > $OUT/bench_$name.json 2> $OUT/bench_$name.err; }
 for ns in 2 3; do
 export DS2I_NSETS=$ns
 b gov2_b256_ns$ns --batch 256 --depth 9 --steps 200 --warmup 80

@@ -2,7 +2,7 @@ set -u
 OUT=gpurun_out/${1:-r6f}
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="timeout 400 python bench.py --no-oracle --steps 30 --warmup 3"
+B="timeout 400 python bench.py --full --no-oracle --steps 30 --warmup 3"
 $B --op wand > $OUT/bench_wand.json 2> $OUT/bench_wand.err
 DS2I_UT_WARM=16 $B --op wand > $OUT/bench_wand_warm16.json 2> $OUT/bench_wand_warm16.err
 DS2I_UT_WARM=32 DS2I_UT_BLOCKS=320 $B --op wand > $OUT/bench_wand_warm32_utb320.json 2> $OUT/bench_wand_warm32_utb320.err

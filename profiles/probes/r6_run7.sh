@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 timeout 900 python tests/union_stream_probe.py 1 2 3 > $OUT/union_probe.txt 2>&1; echo "union probe rc=$?"; tail -2 $OUT/union_probe.txt
 timeout 600 python tests/ranked_stream_probe.py 1 2 3 > $OUT/ranked_probe.txt 2>&1; echo "ranked probe rc=$?"; tail -2 $OUT/ranked_probe.txt
 timeout 900 python -m pytest tests/test_gpu.py -x -q -k "pruning_fuzz or test_query_ops_match_oracle or disjunctive_scores or topk_other_k" > $OUT/pytest_subset.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_subset.txt
-B="timeout 400 python bench.py --no-oracle --steps 30 --warmup 3"
+B="timeout 400 python bench.py --full --no-oracle --steps 30 --warmup 3"
 $B --op wand > $OUT/bench_wand.json 2> $OUT/bench_wand.err
 $B --op maxscore > $OUT/bench_maxscore.json 2> $OUT/bench_maxscore.err
 $B --op ranked_and > $OUT/bench_ranked_and.json 2> $OUT/bench_ranked_and.err

@@ -3,7 +3,7 @@ OUT=gpurun_out/${1:-r6j}
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 600 python tests/union_stream_probe.py 1 2 > $OUT/union_probe.txt 2>&1; echo "union probe rc=$?"; tail -1 $OUT/union_probe.txt
-B="timeout 400 python bench.py --no-oracle --steps 40 --warmup 5"
+B="timeout 400 python bench.py --full --no-oracle --steps 40 --warmup 5"
 for i in 1 2; do
   $B --op wand > $OUT/bench_wand_l1_$i.json 2> $OUT/bench_wand_l1_$i.err
   DS2I_LIB_VARIANT=fwsc1 $B --op wand > $OUT/bench_wand_sc1_$i.json 2> $OUT/bench_wand_sc1_$i.err

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 timeout 1500 python -m pytest tests/test_gpu.py -x -q -k "alternative_paths or union_through or and_through or ranked_stream_5_to_8 or table_budget or transcoded or error_behaviour" > $OUT/pytest_knobs.txt 2>&1; echo "pytest rc=$?"; tail -3 $OUT/pytest_knobs.txt
 for op in ranked_and wand and and_freq or or_freq; do
   for g in 4 2; do
-    DS2I_RMW_G=$g timeout 400 python bench.py --op $op --no-oracle --steps 40 --warmup 5 > $OUT/g${g}_$op.json 2> $OUT/g${g}_$op.err
+    DS2I_RMW_G=$g timeout 400 python bench.py --full --op $op --no-oracle --steps 40 --warmup 5 > $OUT/g${g}_$op.json 2> $OUT/g${g}_$op.err
     python - $OUT/g${g}_$op.json g${g}_$op <<'PY'
 import json,sys
 try:

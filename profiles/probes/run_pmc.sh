@@ -6,7 +6,7 @@ OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --pmc $CTRS --output-format csv -d $OUT/raw -o pmc -- \
-    python bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/err.txt
+    python bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/err.txt
 python - "$OUT" <<'PY'
 import csv, glob, collections, sys
 out = sys.argv[1]

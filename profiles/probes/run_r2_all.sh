@@ -6,7 +6,7 @@ TAG=${1:-r02}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-run() { name=$1; shift; timeout 1500 python bench.py "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; echo "$name: $(cut -c1-160 $OUT/bench_$name.json)"; }
+run() { name=$1; shift; timeout 1500 python bench.py --full "$@" > $OUT/bench_$name.json 2> $OUT/bench_$name.err; echo "$name: $(cut -c1-160 $OUT/bench_$name.json)"; }
 run default_gov2
 run c2 --workload c2
 run gov2_opt --workload gov2 --codec opt

@@ -1,12 +1,13 @@
 set -x
-mkdir -p gpurun_out/r2a
+export OUT=${OUT:-r2a}  # output directory
+mkdir -p $OUT
 export TMPDIR=/tmp
-timeout 2700 python -m pytest tests -m gpu -x -q --durations=15 > gpurun_out/r2a/pytest.log 2>&1
-echo "pytest rc=$?" >> gpurun_out/r2a/pytest.log
-tail -30 gpurun_out/r2a/pytest.log
-timeout 600 python bench.py --workload c2 --steps 10 --warmup 2 > gpurun_out/r2a/bench_c2.json 2> gpurun_out/r2a/bench_c2.err
-tail -12 gpurun_out/r2a/bench_c2.err; cat gpurun_out/r2a/bench_c2.json
-timeout 900 python bench.py --workload gov2 --steps 20 --warmup 3 > gpurun_out/r2a/bench_gov2.json 2> gpurun_out/r2a/bench_gov2.err
-tail -14 gpurun_out/r2a/bench_gov2.err; cat gpurun_out/r2a/bench_gov2.json
-DS2I_NO_BMW_PRUNE=1 timeout 900 python bench.py --workload gov2 --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/r2a/bench_gov2_noprune.json 2> gpurun_out/r2a/bench_gov2_noprune.err
-tail -8 gpurun_out/r2a/bench_gov2_noprune.err; cat gpurun_out/r2a/bench_gov2_noprune.json
+timeout 2700 python -m pytest tests -m gpu -x -q --durations=15 > $OUT/pytest.log 2>&1
+echo "pytest rc=$?" >> $OUT/pytest.log
+tail -30 $OUT/pytest.log
+timeout 600 python bench.py --full --workload c2 --steps 10 --warmup 2 > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+tail -12 $OUT/bench_c2.err; cat $OUT/bench_c2.json
+timeout 900 python bench.py --full --workload gov2 --steps 20 --warmup 3 > $OUT/bench_gov2.json 2> $OUT/bench_gov2.err
+tail -14 $OUT/bench_gov2.err; cat $OUT/bench_gov2.json
+DS2I_NO_BMW_PRUNE=1 timeout 900 python bench.py --full --workload gov2 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_gov2_noprune.json 2> $OUT/bench_gov2_noprune.err
+tail -8 $OUT/bench_gov2_noprune.err; cat $OUT/bench_gov2_noprune.json

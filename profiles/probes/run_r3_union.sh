@@ -2,7 +2,7 @@
 export TMPDIR=/tmp
 OUT=gpurun_out/${1:-r03_union}
 mkdir -p $OUT
-run() { name=$1; shift; python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err; python - <<PY
+run() { name=$1; shift; python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err; python - <<PY
 import json
 d=json.loads(open("$OUT/$name.json").read().strip().splitlines()[-1])
 print("$name", "qps", round(d["value"]), "ms/step", round(d["ms_per_step"],2), d["step_ms_spread"], "cpu", (d.get("cpu_baseline") or {}).get("value"))

@@ -1,7 +1,7 @@
 # round-4 bench lines of the shipped build (one JSON line each under gpurun_out/r04_all/)
 export TMPDIR=/tmp
 O=gpurun_out/r04_all; mkdir -p $O
-run() { name=$1; shift; python bench.py "$@" > $O/$name.json 2> $O/$name.err; python -c "
+run() { name=$1; shift; python bench.py --full "$@" > $O/$name.json 2> $O/$name.err; python -c "
 import json
 d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1])
 r=d['roofline']

@@ -8,13 +8,13 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 # pass 1: kernel trace + stats (no counters)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- \
-    python bench.py --workload $WL --steps $STEPS --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+    python bench.py --full --workload $WL --steps $STEPS --warmup 2 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 KS=$(find $OUT/kt -name "*kernel_stats.csv" | head -1)
 if [ -n "$KS" ]; then cp "$KS" $OUT/kernel_stats.csv; fi
 # pass 2/3: HBM traffic counters, each in its own run (MI355X_MICROARCH.md §HBM)
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -o pmc -- \
-      python bench.py --workload $WL --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$C.err
+      python bench.py --full --workload $WL --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2> $OUT/pmc_$C.err
   python - "$OUT" "$C" <<'PY'
 import csv, glob, collections, sys
 out, c = sys.argv[1], sys.argv[2]

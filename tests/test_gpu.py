@@ -1121,13 +1121,13 @@ def test_optpfor_exception_count_sweep(built_lib, codec):
 
 
 def test_bench_contract(built_lib):
-    """bench.py prints ONE JSON line with the contract's keys (driver contract + roofline + cpu_baseline)."""
+    """bench.py --full prints ONE JSON line with the contract's keys (driver contract + roofline + cpu_baseline)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c2", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c2", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -1163,6 +1163,7 @@ def test_bench_dump_outputs(built_lib, tmp_path):
         j = _run_bench(["--workload", "c2", "--steps", str(steps), "--warmup", str(warmup), "--batch", str(nq), "--no-oracle",
                         "--dump-outputs", str(dump)])
         assert j["steps"] == steps and j["warmup"] == warmup and j["ms_per_step"] > 0
+        assert not {"roofline", "cpu_baseline", "kernel_resident_qps"} & set(j)  # a plain run: the --full figures are not measured
         assert sorted(os.listdir(dump)) == ["count.npy", "tlen.npy", "topk.npy"]
         runs.append({n: np.load(dump / (n + ".npy")) for n in ("count", "topk", "tlen")})
     a, b = runs
@@ -1318,7 +1319,7 @@ def test_bench_two_ranks_on_one_device(built_lib):
     gathered with gather_concat). The answers must be the 1-rank answers (profile_queries.cpp:21-39 shares one index
     between threads the same way)."""
     two = {"DS2I_BENCH_BACKEND": "gloo", "DS2I_BENCH_ONE_DEVICE": "1"}
-    common = ["--workload", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--workload", "c2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     one_w = _run_bench(common)
     two_w = _run_bench(common, nproc=2, env_extra=two)
     assert one_w["n_gpus"] == 1 and two_w["n_gpus"] == 2 and two_w["scaling"] == "weak"
