@@ -838,6 +838,11 @@ struct TopKBig {
 // document that ties the k-th score is never pruned, whatever order the kernel meets documents in, and insert() settles the tie by
 // doc-id. (The floors -- seed, shared histogram, q_floor -- are lower bounds of the final k-th score and are tested with >=.)
 // thr_doc is the doc-id of the k-th pair (wave-uniform, 0xFFFFFFFF until the heap is full).
+// in_order (set after init() by a traversal that meets the documents of its unit in ascending doc-id order: kernels_daat.inc): thr is the
+// k-th score itself, as in the scores-only heaps. A document that ties it arrives after every document in the heap, so it has the larger
+// doc-id and is rightly refused, and so is everything under a bound equal to it; the traversal then takes the very steps of the
+// scores-only run, whose sums depend on those steps (the reference's wand and maxscore add a document's terms in the order the lists
+// stand in), and returns the same score bits.
 DS2I_DEV float float_below(float x) { // the largest float < x (x finite or +inf; -inf stays)
     if (x == -__builtin_inff()) return x;
     if (x == 0.f) return -__uint_as_float(1u);
@@ -852,8 +857,10 @@ struct TopKD {
     float floor;
     float thr;    // below(k-th score), or -inf until the heap is full (see TopK::thr on divergent code)
     uint32_t thr_doc;
+    bool in_order;
     DS2I_DEV void init(uint32_t k_) {
         v = -__builtin_inff(); d = 0xFFFFFFFFu; n = 0; k = k_; floor = -__builtin_inff(); thr = -__builtin_inff(); thr_doc = 0xFFFFFFFFu;
+        in_order = false;
     }
     DS2I_DEV float threshold() const { return thr; }
     DS2I_DEV bool would_enter(float s) const { return s >= floor && (n < k || s > thr); }
@@ -870,7 +877,8 @@ struct TopKD {
         if (n < k) ++n;
         if (lane >= k) { v = -__builtin_inff(); d = 0xFFFFFFFFu; }
         if (n == k) {
-            thr = float_below(__uint_as_float(bcast(__float_as_uint(v), k - 1)));
+            const float t = __uint_as_float(bcast(__float_as_uint(v), k - 1));
+            thr = in_order ? t : float_below(t);
             thr_doc = bcast(d, k - 1);
         }
         return true;
@@ -884,6 +892,7 @@ struct TopKBigD {
     float floor;
     float thr; // as TopKD::thr
     uint32_t thr_doc;
+    bool in_order; // as TopKD::in_order
     DS2I_DEV void init(uint32_t k_) {
 #pragma unroll
         for (int r = 0; r < NK; ++r) { v[r] = -__builtin_inff(); d[r] = 0xFFFFFFFFu; }
@@ -892,6 +901,7 @@ struct TopKBigD {
         floor = -__builtin_inff();
         thr = -__builtin_inff();
         thr_doc = 0xFFFFFFFFu;
+        in_order = false;
     }
     DS2I_DEV float threshold() const { return thr; }
     DS2I_DEV bool would_enter(float s) const { return s >= floor && (n < k || s > thr); }
@@ -924,7 +934,7 @@ struct TopKBigD {
 #pragma unroll
             for (int r = 0; r < NK; ++r)
                 if ((uint32_t)r == ((k - 1) >> 6)) { t = __uint_as_float(bcast(__float_as_uint(v[r]), (k - 1) & 63u)); td = bcast(d[r], (k - 1) & 63u); }
-            thr = float_below(t);
+            thr = in_order ? t : float_below(t);
             thr_doc = td;
         }
         return true;
@@ -940,12 +950,14 @@ typedef TopKD RTopK;
 template <int NK> using RTopKBig = TopKBigD<NK>;
 #define DS2I_KN(name) name##_docs
 #define TK_INSERT(tk, s, doc) (tk).insert((s), (doc))
+#define TK_IN_ORDER(tk) ((tk).in_order = true)
 #define DS2I_DOCS_ARG(p) , (p)
 #else
 typedef TopK RTopK;
 template <int NK> using RTopKBig = TopKBig<NK>;
 #define DS2I_KN(name) name
 #define TK_INSERT(tk, s, doc) (tk).insert(s)
+#define TK_IN_ORDER(tk)
 #define DS2I_DOCS_ARG(p)
 #endif
 

@@ -41,6 +41,7 @@ DS2I_DEV void daat_unit(CX& cx, const BatchArgs& a, const uint32_t uid, uint32_t
         unsigned long long count = 0, fsum = 0;
         TK tk;
         tk.init(a.k);
+        TK_IN_ORDER(tk); // (every traversal below meets the unit's documents in ascending doc-id order: device_enum.hpp, TopKD::in_order)
         if (nt == 0 || nt > tmax) {
             if (lane == 0) { a.out_count[q] = 0; if (a.out_freq_sum) a.out_freq_sum[q] = 0; }
             if (RANKED) store_topk(a.out_topk, a.out_topk_len, a.k, q, tk DS2I_DOCS_ARG(a.out_topk_docs));

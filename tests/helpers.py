@@ -246,3 +246,74 @@ def edge_queries(num_terms):
     qs += [[(11 * j + L) % T for j in range(L)] for L in range(2, 17)]
     qs.append(list(range(0, 40, 2)))
     return qs
+
+
+# ---------------------------------------------------------------- a collection where equal scores are the norm, past doc-id 2^24
+TIE_EDGE = 1 << 24            # the first doc-id a float32 (or a 24-bit field) cannot tell from its neighbour
+TIE_NUM_DOCS = TIE_EDGE + (1 << 18)
+TIE_WINDOW_LO = TIE_EDGE - 64  # the window lists live in [TIE_WINDOW_LO, TIE_NUM_DOCS): a few ids below 2^24, the rest above
+TIE_SIZES = (60, 150, 150, 400)
+TIE_FREQS = (1, 1, 1, 2, 3)
+TIE_HALF = 16                 # lists per half: terms 0 .. 15 spread over the universe, 16 .. 31 in the window, term 32 dense
+TIE_CORE = 1500               # documents common to every list of a half (an AND of any of them is not empty)
+TIE_STRADDLE = (TIE_EDGE - 2, TIE_EDGE - 1, TIE_EDGE, TIE_EDGE + 1)  # in every window list, same size and freq: a tie across 2^24
+
+
+def tie_ladder(lo, hi, n=TIE_HALF):
+    """n list lengths, geometric from lo to hi"""
+    return [int(round(lo * (hi / lo) ** (i / (n - 1)))) for i in range(n)]
+
+
+def tie_collection(seed=0x71E5):
+    """Documents of three distinct sizes and freqs from {1, 2, 3} (skewed to 1): a query sees a few dozen distinct scores, so
+    almost every k-th place is tied, across blocks, units and lists. Terms 0 .. 15 are spread over all 2^24 + 2^18 documents,
+    a geometric ladder of about 2 k .. 2 M postings (the longest are cut into several units by the default planner); terms
+    16 .. 31 (2 k .. 128 k postings) sit in a window that starts 64 documents below 2^24 and ends with the last document, so
+    their top-k ids are mostly above 2^24 and reach below it. Each half shares a core of TIE_CORE documents (present in all
+    of its lists with one freq per document), which keeps every AND inside a half non-empty and tied at every length; the
+    window core holds TIE_STRADDLE, four neighbours around 2^24 of equal size and freq. Term 32 is dense: every document of
+    the first, the last and the 2^16 documents around 2^24, so it holds doc 0 and doc num_docs - 1."""
+    rng = np.random.default_rng(seed)
+    n = TIE_NUM_DOCS
+    sizes = rng.choice(np.array(TIE_SIZES, dtype=np.uint32), n)
+    sizes[list(TIE_STRADDLE)] = 150
+    fr = np.array(TIE_FREQS, dtype=np.uint32)
+    lists = []
+    for lo, hi, lens in ((0, n, tie_ladder(2000, 2000000)), (TIE_WINDOW_LO, n, tie_ladder(2000, 128000))):
+        core = np.unique(rng.integers(lo, hi, TIE_CORE))
+        if lo:
+            core = np.union1d(core, np.array(TIE_STRADDLE))
+        core_freq = rng.choice(fr, len(core))
+        if lo:
+            core_freq[np.searchsorted(core, np.array(TIE_STRADDLE))] = 3
+        for m in lens:
+            own = np.setdiff1d(np.unique(rng.integers(lo, hi, max(m - len(core), 1))), core, assume_unique=True)
+            docs = np.concatenate([core, own])
+            freqs = np.concatenate([core_freq, rng.choice(fr, len(own))])
+            o = np.argsort(docs, kind="stable")
+            lists.append((docs[o], freqs[o]))
+    run = 1 << 15
+    dense = np.concatenate([np.arange(0, run), np.arange(TIE_EDGE - run, TIE_EDGE + run), np.arange(n - run, n)])
+    lists.append((dense, rng.choice(fr, len(dense))))
+    return Collection.from_lists(n, lists, sizes)
+
+
+def tie_queries(coll, seed=0x71E6):
+    """The empty query, one-term queries, duplicated terms, every length 2 .. 16 drawn within each half, random 2 .. 4-term queries
+    within each half (more of them in the window, whose ids are the ones past 2^24), queries with the dense list, mixed-half
+    queries (for the union operators: an AND across the halves is nearly empty) and, last, two queries of more than 16 terms."""
+    assert len(coll.lists) == 2 * TIE_HALF + 1
+    rng = np.random.default_rng(seed)
+    spread, window, dense = np.arange(TIE_HALF), TIE_HALF + np.arange(TIE_HALF), 2 * TIE_HALF
+    pick = lambda pool, m: [int(t) for t in rng.choice(pool, m, replace=False)]
+    qs = [[]] + [[t] for t in (0, TIE_HALF - 1, TIE_HALF, 2 * TIE_HALF - 1, dense)]
+    qs += [[5, 5], [20, 20, 25], [31, 31, 16], [12, 3, 12, 3]]
+    for L in range(2, TIE_HALF + 1):
+        qs += [pick(spread, L), pick(window, L)]
+    qs += [pick(spread, int(rng.integers(2, 5))) for _ in range(30)]
+    qs += [pick(window, int(rng.integers(2, 5))) for _ in range(50)]
+    qs += [[dense] + pick(window, m) for m in (1, 2, 3)] + [[dense] + pick(spread[8:], m) for m in (1, 2)]
+    qs += [pick(spread, a) + pick(window, b) for a, b in ((1, 1), (1, 2), (2, 1), (2, 2), (3, 3), (1, 4), (4, 4), (2, 6))]
+    qs += [[dense] + pick(spread, 2) + pick(window, 2)]
+    qs += [[int(t) for t in window] + [dense, 15], [int(t) for t in range(0, 2 * TIE_HALF, 2)] + [17, 21, 25, dense]]
+    return qs
