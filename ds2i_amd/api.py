@@ -122,6 +122,10 @@ def lib():
         L.ds2i_hybrid_freeze.argtypes = [vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(C.c_double), u64p,
                                          C.POINTER(C.c_double), u64p]
         L.ds2i_synth_build_hybrid.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.POINTER(vp), C.POINTER(vp), u64p, u64p]
+        L.ds2i_hybrid_hull.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_int, vp, C.c_uint32, u32p]
+        L.ds2i_hip_hybrid_analyse.argtypes = [vp, C.c_int, u64p, u64p, C.POINTER(C.c_double)]
+        L.ds2i_hip_hybrid_freeze.argtypes = [vp, C.c_int, C.c_uint64, C.POINTER(vp), C.POINTER(C.c_double), u64p,
+                                             C.POINTER(C.c_double), u64p, C.POINTER(C.c_double)]
         L.ds2i_hybrid_free.argtypes = [vp]
         L.ds2i_hybrid_free.restype = None
         L.ds2i_hip_calibration_read.argtypes = [vp, u64p]
@@ -300,6 +304,9 @@ class HybridModel(C.Structure):
         return m
 
 
+HULL_POINT = np.dtype([("time", np.float32), ("space", np.uint16), ("type", np.uint8), ("b", np.int8)])
+
+
 class HybridBuilder:
     """block_mixed space/time optimiser (ds2i_hybrid_*; reference optimal_hybrid_index.cpp)."""
 
@@ -316,20 +323,43 @@ class HybridBuilder:
             assert a.size == 2 * ((len(d) + 127) // 128)
         _check(lib().ds2i_hybrid_add_posting_list(self._h, len(d), _ptr(d), _ptr(f), _ptr(a) if a is not None else None))
 
-    def analyse(self, threads=0):
+    def analyse(self, threads=0, device=None):
+        """-> (min_space, max_space). device=None analyses on `threads` host threads, an integer on that GPU
+        (ds2i_hip_hybrid_analyse; self.device_ms then holds the kernel time): the hulls are the same bit for bit."""
         lo, hi = C.c_uint64(), C.c_uint64()
-        _check(lib().ds2i_hybrid_analyse(self._h, threads, C.byref(lo), C.byref(hi)))
+        if device is None:
+            _check(lib().ds2i_hybrid_analyse(self._h, threads, C.byref(lo), C.byref(hi)))
+        else:
+            ms = C.c_double()
+            _check(lib().ds2i_hip_hybrid_analyse(self._h, int(device), C.byref(lo), C.byref(hi), C.byref(ms)))
+            self.device_ms = ms.value
         return lo.value, hi.value
 
-    def freeze(self, budget_bytes=None, threads=0):
-        """-> (image bytes, dict(rate, space, model_time, type_counts))"""
+    def freeze(self, budget_bytes=None, threads=0, device=None):
+        """-> (image bytes, dict(rate, space, model_time, type_counts)); with device=<int> the image is written on that
+        GPU (ds2i_hip_hybrid_freeze), byte-identical, and the dict also holds device_ms"""
         h = C.c_void_p()
         rate, t, space = C.c_double(), C.c_double(), C.c_uint64()
         tc = (C.c_uint64 * 6)()
         budget = 0xFFFFFFFFFFFFFFFF if budget_bytes is None else int(budget_bytes)
-        _check(lib().ds2i_hybrid_freeze(self._h, budget, threads, C.byref(h), C.byref(rate), C.byref(space), C.byref(t), tc))
-        return _take_blob(h), {"rate": rate.value, "space": space.value, "model_time": t.value,
-                               "type_counts": {"docs": list(tc[0:3]), "freqs": list(tc[3:6])}}
+        extra = {}
+        if device is None:
+            _check(lib().ds2i_hybrid_freeze(self._h, budget, threads, C.byref(h), C.byref(rate), C.byref(space), C.byref(t), tc))
+        else:
+            ms = C.c_double()
+            _check(lib().ds2i_hip_hybrid_freeze(self._h, int(device), budget, C.byref(h), C.byref(rate), C.byref(space),
+                                                C.byref(t), tc, C.byref(ms)))
+            extra["device_ms"] = ms.value
+        return _take_blob(h), dict({"rate": rate.value, "space": space.value, "model_time": t.value,
+                                    "type_counts": {"docs": list(tc[0:3]), "freqs": list(tc[3:6])}}, **extra)
+
+    def hull(self, list, block, side):
+        """The lower convex hull of one part after analyse (ds2i_hybrid_hull): side 0 = docs, 1 = freqs. A structured array
+        (HULL_POINT: time, space, type, b) by increasing space and decreasing time."""
+        n = C.c_uint32()
+        pts = np.zeros(24, dtype=HULL_POINT)  # a part has at most 19 candidates
+        _check(lib().ds2i_hybrid_hull(self._h, int(list), int(block), int(side), _ptr(pts), len(pts), C.byref(n)))
+        return pts[:n.value]
 
     def close(self):
         if self._h:

@@ -9,6 +9,7 @@
 #include "../../include/ds2i_build.h"
 #include "capi_blob.hpp"
 #include "capi_error.hpp"
+#include "capi_hybrid.hpp"
 #include "host_encode.hpp"
 #include "host_index.hpp"
 #include "host_pef.hpp"
@@ -20,9 +21,6 @@ using namespace ds2i_host;
 struct ds2i_builder {
     std::unique_ptr<block_index_builder> b;   // kinds 0..4
     std::unique_ptr<opt_index_builder> opt;   // kinds 5..8 (DS2I_OPT / EF / SINGLE / UNIFORM)
-};
-struct ds2i_hybrid {
-    std::unique_ptr<hybrid_index_builder> b;
 };
 struct ds2i_wand_builder {
     std::vector<float> norm_lens, max_w;
@@ -385,6 +383,17 @@ int ds2i_hybrid_freeze(ds2i_hybrid* h, uint64_t budget_bytes, int threads, ds2i_
     if (model_time) *model_time = t;
     return 0;
     DS2I_CATCH
+}
+int ds2i_hybrid_hull(const ds2i_hybrid* h, uint64_t list, uint64_t block, int side, void* points, uint32_t capacity, uint32_t* n) {
+    if (!h || !n || (!points && capacity)) return ds2i_set_error(-1, "ds2i_hybrid_hull: null argument");
+    if (!h->b->analysed()) return ds2i_set_error(-1, "ds2i_hybrid_hull: the builder is not analysed");
+    static_assert(sizeof(hybrid_point) == 8, "hybrid_point is the published {float, uint16, uint8, int8}");
+    uint32_t cnt = 0;
+    const hybrid_point* p = h->b->hull(list, block, side, cnt);
+    if (!p) return ds2i_set_error(-1, "ds2i_hybrid_hull: no such part");
+    *n = cnt;
+    if (points && capacity) std::memcpy(points, p, sizeof(hybrid_point) * std::min(cnt, capacity));
+    return 0;
 }
 void ds2i_hybrid_free(ds2i_hybrid* h) { delete h; }
 

@@ -2,19 +2,26 @@
 // postings, runs the plan pass (findBestB per block part, sizes), lays the lists out from the sizes
 // (block_posting_list::write's layout, block_posting_list.hpp:13-53), runs the write pass, and freezes the
 // block_freq_index image around the device-written list bytes (block_freq_index.hpp:18-70, 124-134).
+// The block_mixed optimiser's device half lives here too (ds2i_hip_hybrid_analyse / ds2i_hip_hybrid_freeze; §8(f) item
+// 3): the plan kernel measures every candidate of every part, the host builds hulls and solves the budget
+// (host_hybrid.hpp, shared with the host path), and one write pass lays the chosen encodings down.
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "capi_blob.hpp"
+#include "capi_hybrid.hpp"
 #include "capi_internal.hpp"
 #include "host_index.hpp"
 
 extern "C" {
 size_t ds2i_sizeof_enc_args();
-hipError_t ds2i_launch_encode(int write, const void* args, unsigned grid, hipStream_t s);
+size_t ds2i_sizeof_hyb_rec();
+hipError_t ds2i_launch_encode(int mode, int write, const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_hybrid_plan(const void* args, unsigned grid, hipStream_t s);
 }
 
 namespace {
@@ -31,6 +38,8 @@ struct EncArgsHost { // mirrors EncArgs in encode_kernels.hip
     const uint64_t* blk_out;
     const uint64_t* list_out;
     uint8_t* out;
+    const uint8_t* choice;
+    void* rec;
 };
 struct DevFree {
     std::vector<void*> p;
@@ -43,120 +52,304 @@ struct DevFree {
         return e;
     }
 };
+struct Events { // destroyed on every path out of a function
+    hipEvent_t e[4] = {};
+    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+int check_device(const char* who, int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return ds2i_set_error(DS2I_EDEVICE, (std::string(who) + ": no such HIP device").c_str());
+    return DS2I_OK;
+}
+
+// A collection in CSR form staged on the device, with the block tables both kernels walk
+struct EncStage {
+    DevFree dev;
+    EncArgsHost a{};
+    uint64_t nlists = 0, nblocks = 0;
+    const uint64_t* list_offsets = nullptr;
+    std::vector<uint32_t> list_blk0;
+    unsigned grid = 1;
+    uint64_t* d_blk_out = nullptr;
+    uint64_t* d_list_out = nullptr;
+
+    int upload(const char* who, int device, uint64_t nl, const uint64_t* offs, const uint32_t* docs, const uint32_t* freqs) {
+        if (sizeof(EncArgsHost) != ds2i_sizeof_enc_args() || sizeof(ds2i_host::hybrid_part_rec) != ds2i_sizeof_hyb_rec())
+            return ds2i_set_error(DS2I_EINVAL, "EncArgs layout mismatch");
+        const int rc = check_device(who, device);
+        if (rc != DS2I_OK) return rc;
+        nlists = nl;
+        list_offsets = offs;
+        const uint64_t total = offs[nlists];
+        std::vector<uint32_t> blk_list;
+        list_blk0.resize(nlists);
+        for (uint64_t t = 0; t < nlists; ++t) {
+            if (offs[t + 1] <= offs[t]) return ds2i_set_error(DS2I_EINVAL, "List must be nonempty"); // block_freq_index.hpp:31
+            const uint64_t n = offs[t + 1] - offs[t];
+            if (n > 0xFFFFFFFFull) return ds2i_set_error(DS2I_EINVAL, "posting list longer than 2^32");
+            list_blk0[t] = (uint32_t)nblocks;
+            nblocks += (n + 127) / 128;
+        }
+        if (nblocks >= (1ull << 32)) return ds2i_set_error(DS2I_EINVAL, "more than 2^32 blocks");
+        try {
+            blk_list.resize(nblocks);
+        } catch (std::bad_alloc const&) {
+            return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+        }
+        for (uint64_t t = 0; t < nlists; ++t) {
+            const uint64_t nb = (offs[t + 1] - offs[t] + 127) / 128;
+            std::fill(blk_list.begin() + list_blk0[t], blk_list.begin() + list_blk0[t] + nb, (uint32_t)t);
+        }
+        HIP_OK(hipSetDevice(device));
+        hipDeviceProp_t prop;
+        HIP_OK(hipGetDeviceProperties(&prop, device));
+        grid = (unsigned)std::min<uint64_t>(nblocks ? nblocks : 1, (uint64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * 32);
+        uint32_t *d_docs, *d_freqs, *d_blk_list, *d_list_blk0;
+        uint64_t* d_list_in;
+        HIP_OK(dev.alloc(&d_docs, 4 * total));
+        HIP_OK(dev.alloc(&d_freqs, 4 * total));
+        HIP_OK(dev.alloc(&d_list_in, 8 * (nlists + 1)));
+        HIP_OK(dev.alloc(&d_blk_list, 4 * nblocks));
+        HIP_OK(dev.alloc(&d_list_blk0, 4 * nlists));
+        HIP_OK(dev.alloc(&a.bsel, 2 * nblocks));
+        HIP_OK(dev.alloc(&a.psize, 8 * nblocks));
+        HIP_OK(dev.alloc(&a.bmax, 4 * nblocks));
+        HIP_OK(dev.alloc(&d_blk_out, 8 * (nblocks + 1)));
+        HIP_OK(dev.alloc(&d_list_out, 8 * nlists));
+        HIP_OK(hipMemcpy(d_docs, docs, 4 * total, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_freqs, freqs, 4 * total, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_list_in, offs, 8 * (nlists + 1), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_blk_list, blk_list.data(), 4 * nblocks, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_list_blk0, list_blk0.data(), 4 * nlists, hipMemcpyHostToDevice));
+        a.docs = d_docs;
+        a.freqs = d_freqs;
+        a.list_in = d_list_in;
+        a.blk_list = d_blk_list;
+        a.list_blk0 = d_list_blk0;
+        a.nblocks = (uint32_t)nblocks;
+        return DS2I_OK;
+    }
+
+    // layout from the part sizes (2 per block): vbyte(n) | block_max[nb] | block_endpoint[nb - 1] | blocks (docs part,
+    // freqs part each); allocates the output and uploads the offsets. list_end receives the end of every list.
+    int lay_out(const std::vector<uint32_t>& psize, std::vector<uint64_t>& list_end, uint64_t& bytes) {
+        std::vector<uint64_t> blk_out(nblocks + 1), list_out(nlists);
+        list_end.resize(nlists);
+        uint64_t cursor = 0;
+        for (uint64_t t = 0; t < nlists; ++t) {
+            const uint64_t n = list_offsets[t + 1] - list_offsets[t], nb = (n + 127) / 128;
+            const uint32_t vl = 1u + (n >= (1u << 7)) + (n >= (1u << 14)) + (n >= (1u << 21)) + (n >= (1u << 28));
+            list_out[t] = cursor;
+            cursor += vl + 8 * nb - 4;
+            for (uint64_t b = 0; b < nb; ++b) {
+                const uint64_t g = list_blk0[t] + b;
+                blk_out[g] = cursor;
+                cursor += (uint64_t)psize[2 * g] + psize[2 * g + 1];
+            }
+            list_end[t] = cursor;
+        }
+        blk_out[nblocks] = cursor;
+        bytes = cursor;
+        HIP_OK(dev.alloc(&a.out, cursor + 4096));
+        HIP_OK(hipMemcpy(d_blk_out, blk_out.data(), 8 * (nblocks + 1), hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_list_out, list_out.data(), 8 * nlists, hipMemcpyHostToDevice));
+        a.blk_out = d_blk_out;
+        a.list_out = d_list_out;
+        return DS2I_OK;
+    }
+
+    // the device-written list bytes wrapped into the block_freq_index image of that codec
+    int wrap(int codec, uint64_t num_docs, uint64_t bytes, const std::vector<uint64_t>& list_end, ds2i_blob** image) {
+        try {
+            ds2i_host::bytes_t lists(bytes);
+            HIP_OK(hipMemcpy(lists.data(), a.out, bytes, hipMemcpyDeviceToHost));
+            ds2i_host::block_index_builder builder(codec, num_docs);
+            builder.set_encoded_lists(std::move(lists), list_end);
+            std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
+            builder.freeze(blob->data);
+            *image = blob.release();
+        } catch (std::bad_alloc const&) {
+            return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+        } catch (std::exception const& e) {
+            return ds2i_set_error(DS2I_EFORMAT, e.what());
+        }
+        return DS2I_OK;
+    }
+};
+#define STAGE_OK(call)                 \
+    do {                               \
+        const int rc_ = (call);        \
+        if (rc_ != DS2I_OK) return rc_; \
+    } while (0)
 } // namespace
 
 extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                                      const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms) {
     if (!list_offsets || !docs || !freqs || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: null argument");
-    if (index_kind != DS2I_BLOCK_OPTPFOR) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: the GPU encoder writes block_optpfor indexes");
-    if (sizeof(EncArgsHost) != ds2i_sizeof_enc_args()) return ds2i_set_error(DS2I_EINVAL, "EncArgs layout mismatch");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return ds2i_set_error(DS2I_EDEVICE, "ds2i_hip_encode_index: no such HIP device");
-    const uint64_t total = list_offsets[nlists];
-    std::vector<uint32_t> blk_list, list_blk0(nlists);
-    uint64_t nblocks = 0;
-    for (uint64_t t = 0; t < nlists; ++t) {
-        if (list_offsets[t + 1] <= list_offsets[t]) return ds2i_set_error(DS2I_EINVAL, "List must be nonempty"); // block_freq_index.hpp:31
-        const uint64_t n = list_offsets[t + 1] - list_offsets[t];
-        if (n > 0xFFFFFFFFull) return ds2i_set_error(DS2I_EINVAL, "posting list longer than 2^32");
-        list_blk0[t] = (uint32_t)nblocks;
-        nblocks += (n + 127) / 128;
-    }
-    if (nblocks >= (1ull << 32)) return ds2i_set_error(DS2I_EINVAL, "more than 2^32 blocks");
-    try {
-        blk_list.resize(nblocks);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    }
-    for (uint64_t t = 0; t < nlists; ++t) {
-        const uint64_t nb = (list_offsets[t + 1] - list_offsets[t] + 127) / 128;
-        std::fill(blk_list.begin() + list_blk0[t], blk_list.begin() + list_blk0[t] + nb, (uint32_t)t);
-    }
-    HIP_OK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    HIP_OK(hipGetDeviceProperties(&prop, device));
-    const unsigned grid = (unsigned)std::min<uint64_t>(nblocks ? nblocks : 1, (uint64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * 32);
-    DevFree dev;
-    uint32_t *d_docs, *d_freqs, *d_blk_list, *d_list_blk0, *d_psize, *d_bmax;
-    uint64_t *d_list_in, *d_blk_out, *d_list_out;
-    uint8_t *d_bsel, *d_out = nullptr;
-    HIP_OK(dev.alloc(&d_docs, 4 * total));
-    HIP_OK(dev.alloc(&d_freqs, 4 * total));
-    HIP_OK(dev.alloc(&d_list_in, 8 * (nlists + 1)));
-    HIP_OK(dev.alloc(&d_blk_list, 4 * nblocks));
-    HIP_OK(dev.alloc(&d_list_blk0, 4 * nlists));
-    HIP_OK(dev.alloc(&d_bsel, 2 * nblocks));
-    HIP_OK(dev.alloc(&d_psize, 8 * nblocks));
-    HIP_OK(dev.alloc(&d_bmax, 4 * nblocks));
-    HIP_OK(dev.alloc(&d_blk_out, 8 * (nblocks + 1)));
-    HIP_OK(dev.alloc(&d_list_out, 8 * nlists));
-    HIP_OK(hipMemcpy(d_docs, docs, 4 * total, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_freqs, freqs, 4 * total, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_list_in, list_offsets, 8 * (nlists + 1), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_blk_list, blk_list.data(), 4 * nblocks, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_list_blk0, list_blk0.data(), 4 * nlists, hipMemcpyHostToDevice));
-    struct Events { // destroyed on every path out of the function
-        hipEvent_t e[4] = {};
-        ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-    } evs;
+    if (index_kind != DS2I_BLOCK_OPTPFOR && index_kind != DS2I_BLOCK_VARINT && index_kind != DS2I_BLOCK_INTERPOLATIVE)
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: the GPU encoder writes block_optpfor, block_varint and block_interpolative indexes");
+    const int codec = index_kind == DS2I_BLOCK_OPTPFOR ? ds2i_host::CODEC_OPTPFOR
+                      : index_kind == DS2I_BLOCK_VARINT ? ds2i_host::CODEC_VARINT : ds2i_host::CODEC_INTERPOLATIVE;
+    EncStage st;
+    STAGE_OK(st.upload("ds2i_hip_encode_index", device, nlists, list_offsets, docs, freqs));
+    const uint64_t nblocks = st.nblocks;
+    Events evs;
     for (auto& x : evs.e) HIP_OK(hipEventCreate(&x));
     const hipEvent_t e0 = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
-    EncArgsHost a{};
-    a.docs = d_docs;
-    a.freqs = d_freqs;
-    a.list_in = d_list_in;
-    a.blk_list = d_blk_list;
-    a.list_blk0 = d_list_blk0;
-    a.nblocks = (uint32_t)nblocks;
-    a.bsel = d_bsel;
-    a.psize = d_psize;
-    a.bmax = d_bmax;
     // ---- plan pass
     HIP_OK(hipEventRecord(e0, nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_encode(0, &a, grid, nullptr));
+    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 0, &st.a, st.grid, nullptr));
     HIP_OK(hipEventRecord(e1, nullptr));
     std::vector<uint32_t> psize(2 * nblocks);
-    HIP_OK(hipMemcpy(psize.data(), d_psize, 8 * nblocks, hipMemcpyDeviceToHost));
-    // ---- layout: vbyte(n) | block_max[nb] | block_endpoint[nb - 1] | blocks (docs part, freqs part each)
-    std::vector<uint64_t> blk_out(nblocks + 1), list_out(nlists), list_end(nlists);
-    uint64_t cursor = 0;
-    for (uint64_t t = 0; t < nlists; ++t) {
-        const uint64_t n = list_offsets[t + 1] - list_offsets[t], nb = (n + 127) / 128;
-        const uint32_t vl = 1u + (n >= (1u << 7)) + (n >= (1u << 14)) + (n >= (1u << 21)) + (n >= (1u << 28));
-        list_out[t] = cursor;
-        cursor += vl + 8 * nb - 4;
-        for (uint64_t b = 0; b < nb; ++b) {
-            const uint64_t g = list_blk0[t] + b;
-            blk_out[g] = cursor;
-            cursor += (uint64_t)psize[2 * g] + psize[2 * g + 1];
-        }
-        list_end[t] = cursor;
-    }
-    blk_out[nblocks] = cursor;
-    HIP_OK(dev.alloc(&d_out, cursor + 64));
-    HIP_OK(hipMemcpy(d_blk_out, blk_out.data(), 8 * (nblocks + 1), hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_list_out, list_out.data(), 8 * nlists, hipMemcpyHostToDevice));
-    a.blk_out = d_blk_out;
-    a.list_out = d_list_out;
-    a.out = d_out;
+    HIP_OK(hipMemcpy(psize.data(), st.a.psize, 8 * nblocks, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> list_end;
+    uint64_t bytes = 0;
+    STAGE_OK(st.lay_out(psize, list_end, bytes));
     // ---- write pass
     HIP_OK(hipEventRecord(e2, nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_encode(1, &a, grid, nullptr));
+    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 1, &st.a, st.grid, nullptr));
     HIP_OK(hipEventRecord(e3, nullptr));
     HIP_OK(hipEventSynchronize(e3));
     float ms_plan = 0.f, ms_write = 0.f;
     HIP_OK(hipEventElapsedTime(&ms_plan, e0, e1));
     HIP_OK(hipEventElapsedTime(&ms_write, e2, e3));
     if (device_ms) *device_ms = (double)ms_plan + ms_write;
+    return st.wrap(codec, num_docs, bytes, list_end, image);
+}
+
+// ---------------------------------------------------------------- block_mixed optimiser on the device
+namespace {
+// the builder's lists in CSR form
+int hybrid_csr(const char* who, const ds2i_host::hybrid_index_builder& hb, std::vector<uint64_t>& offs, std::vector<uint32_t>& docs,
+               std::vector<uint32_t>& freqs) {
+    if (hb.has_virtual()) return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": the builder holds virtual lists (ds2i_synth_build_hybrid stays on the host)").c_str());
+    const uint64_t V = hb.lists();
+    offs.assign(V + 1, 0);
+    for (uint64_t t = 0; t < V; ++t) offs[t + 1] = offs[t] + hb.list_size(t);
+    docs.resize(offs[V] ? offs[V] : 1);
+    freqs.resize(offs[V] ? offs[V] : 1);
+    for (uint64_t t = 0; t < V; ++t) {
+        std::memcpy(docs.data() + offs[t], hb.list_docs(t), 4 * hb.list_size(t));
+        std::memcpy(freqs.data() + offs[t], hb.list_freqs(t), 4 * hb.list_size(t));
+    }
+    return DS2I_OK;
+}
+
+// plan kernel -> records -> hulls (host): leaves the builder analysed. ms accumulates the kernel's hipEvent time.
+int hybrid_analyse_on(EncStage& st, ds2i_host::hybrid_index_builder& hb, double& ms) {
+    const uint64_t nblocks = st.nblocks;
+    HIP_OK(st.dev.alloc(&st.a.rec, sizeof(ds2i_host::hybrid_part_rec) * 2 * nblocks));
+    Events evs;
+    HIP_OK(hipEventCreate(&evs.e[0]));
+    HIP_OK(hipEventCreate(&evs.e[1]));
+    HIP_OK(hipEventRecord(evs.e[0], nullptr));
+    if (nblocks) HIP_OK(ds2i_launch_hybrid_plan(&st.a, st.grid, nullptr));
+    HIP_OK(hipEventRecord(evs.e[1], nullptr));
+    HIP_OK(hipEventSynchronize(evs.e[1]));
+    float t = 0.f;
+    HIP_OK(hipEventElapsedTime(&t, evs.e[0], evs.e[1]));
+    ms += t;
+    std::vector<ds2i_host::hybrid_part_rec> recs(2 * nblocks);
+    HIP_OK(hipMemcpy(recs.data(), st.a.rec, sizeof(ds2i_host::hybrid_part_rec) * 2 * nblocks, hipMemcpyDeviceToHost));
+    hb.analyse_from_records(recs.data(), 0);
+    return DS2I_OK;
+}
+} // namespace
+
+extern "C" int ds2i_hip_hybrid_analyse(ds2i_hybrid* h, int device, uint64_t* min_space, uint64_t* max_space, double* device_ms) {
+    if (!h) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_analyse: null argument");
     try {
-        ds2i_host::bytes_t lists(cursor);
-        HIP_OK(hipMemcpy(lists.data(), d_out, cursor, hipMemcpyDeviceToHost));
-        ds2i_host::block_index_builder builder(ds2i_host::CODEC_OPTPFOR, num_docs);
-        builder.set_encoded_lists(std::move(lists), list_end);
-        std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
-        builder.freeze(blob->data);
-        *image = blob.release();
+        ds2i_host::hybrid_index_builder& hb = *h->b;
+        double ms = 0.0;
+        if (hb.analysed()) {
+            STAGE_OK(check_device("ds2i_hip_hybrid_analyse", device));
+        } else {
+            std::vector<uint64_t> offs;
+            std::vector<uint32_t> docs, freqs;
+            STAGE_OK(hybrid_csr("ds2i_hip_hybrid_analyse", hb, offs, docs, freqs));
+            EncStage st;
+            STAGE_OK(st.upload("ds2i_hip_hybrid_analyse", device, hb.lists(), offs.data(), docs.data(), freqs.data()));
+            STAGE_OK(hybrid_analyse_on(st, hb, ms));
+        }
+        if (min_space) *min_space = hb.min_space();
+        if (max_space) *max_space = hb.max_space();
+        if (device_ms) *device_ms = ms;
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    }
+    return DS2I_OK;
+}
+
+extern "C" int ds2i_hip_hybrid_freeze(ds2i_hybrid* h, int device, uint64_t budget_bytes, ds2i_blob** image, double* rate,
+                                      uint64_t* space, double* model_time, uint64_t type_counts[6], double* device_ms) {
+    if (!h || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_freeze: null argument");
+    try {
+        ds2i_host::hybrid_index_builder& hb = *h->b;
+        double ms = 0.0;
+        std::vector<uint64_t> offs;
+        std::vector<uint32_t> docs, freqs;
+        STAGE_OK(hybrid_csr("ds2i_hip_hybrid_freeze", hb, offs, docs, freqs));
+        EncStage st;
+        STAGE_OK(st.upload("ds2i_hip_hybrid_freeze", device, hb.lists(), offs.data(), docs.data(), freqs.data()));
+        if (!hb.analysed()) STAGE_OK(hybrid_analyse_on(st, hb, ms));
+        if (budget_bytes < hb.min_space()) return ds2i_set_error(DS2I_EINVAL, "budget below the smallest possible index");
+        const double r = hb.solve(budget_bytes);
+        uint64_t s = 0;
+        double t = 0;
+        hb.evaluate(r, s, t);
+        // the choice of every part: (type, b) for the kernel, its bytes for the layout (a hull point's space IS the
+        // size of the part in that encoding, type byte included), the counts of the full blocks
+        const uint64_t nblocks = st.nblocks;
+        std::vector<uint8_t> choice(4 * nblocks);
+        std::vector<uint32_t> psize(2 * nblocks);
+        uint64_t tc[6] = {0, 0, 0, 0, 0, 0};
+        {
+            uint64_t part = 0;
+            uint64_t t_list = 0, left = hb.lists() ? hb.list_size(0) : 0; // postings of the current list from this block on
+            hb.for_each_choice(r, [&](ds2i_host::hybrid_point const& c) {
+                choice[2 * part] = c.type;
+                choice[2 * part + 1] = (uint8_t)c.b;
+                psize[part] = c.space;
+                if (left >= ds2i_host::BLOCK) ++tc[3 * (part & 1) + c.type];
+                if (part & 1) {
+                    left -= std::min<uint64_t>(left, ds2i_host::BLOCK);
+                    if (!left && ++t_list < hb.lists()) left = hb.list_size(t_list);
+                }
+                ++part;
+            });
+            if (part != 2 * nblocks) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_freeze: the analysis does not match the lists");
+        }
+        uint8_t* d_choice = nullptr;
+        HIP_OK(st.dev.alloc(&d_choice, 4 * nblocks));
+        HIP_OK(hipMemcpy(d_choice, choice.data(), 4 * nblocks, hipMemcpyHostToDevice));
+        st.a.choice = d_choice;
+        std::vector<uint64_t> list_end;
+        uint64_t bytes = 0;
+        STAGE_OK(st.lay_out(psize, list_end, bytes));
+        Events evs;
+        HIP_OK(hipEventCreate(&evs.e[0]));
+        HIP_OK(hipEventCreate(&evs.e[1]));
+        HIP_OK(hipEventRecord(evs.e[0], nullptr));
+        if (nblocks) HIP_OK(ds2i_launch_encode(ds2i_host::CODEC_MIXED, 1, &st.a, st.grid, nullptr));
+        HIP_OK(hipEventRecord(evs.e[1], nullptr));
+        HIP_OK(hipEventSynchronize(evs.e[1]));
+        float tw = 0.f;
+        HIP_OK(hipEventElapsedTime(&tw, evs.e[0], evs.e[1]));
+        ms += tw;
+        // the kernel reports what it wrote: it must be what the hulls promised, or the layout is wrong
+        std::vector<uint32_t> wrote(2 * nblocks);
+        HIP_OK(hipMemcpy(wrote.data(), st.a.psize, 8 * nblocks, hipMemcpyDeviceToHost));
+        if (wrote != psize) return ds2i_set_error(DS2I_EFORMAT, "ds2i_hip_hybrid_freeze: a part was written at another size than its hull point");
+        STAGE_OK(st.wrap(ds2i_host::CODEC_MIXED, hb.num_docs(), bytes, list_end, image));
+        if (rate) *rate = r;
+        if (space) *space = s;
+        if (model_time) *model_time = t;
+        if (type_counts) for (int i = 0; i < 6; ++i) type_counts[i] = tc[i];
+        if (device_ms) *device_ms = ms;
     } catch (std::bad_alloc const&) {
         return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
     } catch (std::exception const& e) {

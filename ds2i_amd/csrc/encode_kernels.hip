@@ -7,6 +7,12 @@
 //          block_posting_list.hpp:13-53: vbyte(n) | block_max[] | block_endpoint[] | docs part, freqs part per block)
 // The output is byte-identical to the host encoder (host_encode.hpp / host_index.hpp::write_posting_list) -- that is the
 // parity contract, tested in tests/test_gpu.py::test_gpu_encode_is_byte_identical.
+// The same two passes write block_varint and block_interpolative lists (every full block VarInt-G8IU / interpolative), and
+// the block_mixed optimiser runs its build side here (host_hybrid.hpp):
+//   k_hybrid_plan     per 128-value part one record of INTEGERS: payload words and exception count of OptPFor at every
+//                     candidate b, VarInt-G8IU bytes, interpolative bytes + live tree nodes. The host turns the records
+//                     into (space, time) points and hulls -- no float is computed here, which keeps the hulls bit-equal
+//   k_encode<.., MIXED>  writes type byte + part of the (type, b) the optimiser chose for every part
 #include <hip/hip_runtime.h>
 
 #include "device_codecs.hpp"
@@ -28,7 +34,43 @@ struct EncArgs {
     const uint64_t* blk_out;   // write pass: byte offset of the block's bytes in `out` (nblocks + 1 entries)
     const uint64_t* list_out;  // write pass: byte offset of the list (its vbyte(n)) in `out`
     uint8_t* out;
+    const uint8_t* choice;     // block_mixed write pass: 2 per part (4 per block): mixed type, OptPFor b
+    void* rec;                 // optimiser plan: 2 HybRec per block (docs part, freqs part)
 };
+
+// which encoder the full blocks of k_encode take (host_encode.hpp codec_kind; QMX has no encoder here)
+enum : int { ENC_OPTPFOR = 0, ENC_VARINT = 1, ENC_INTERP = 2, ENC_MIXED = 4 };
+enum : uint32_t { MIX_PFOR = 0, MIX_VARINT = 1, MIX_INTERP = 2 };
+
+// One part as the optimiser sees it (mirrors hybrid_part_rec in host_hybrid.hpp): sizes and counts only
+struct HybRec {
+    uint16_t pfor_words[17]; // payload words of OptPFor at ENC_LOGS[i] (packed values + Simple16 exceptions), 0xFFFF: not a candidate
+    uint8_t nexc[17];        // exceptions at that b
+    uint8_t interp_ok;       // the values sum to less than 2^32 - 1: interpolative can code the part
+    uint16_t varint_bytes;
+    uint16_t interp_bytes;   // full blocks: valid if interp_ok; partial blocks: the only field that is read
+    uint16_t live;           // interpolative tree nodes whose range is not degenerate
+    uint16_t pad[3];
+};
+static_assert(sizeof(HybRec) == 64, "HybRec layout");
+
+// Shape of write_interpolative(pre, 127, 0, sum) for a full block: the node that codes pre[p] has the range
+// (lo[p] ? pre[lo[p] - 1] : 0) .. pre[hi[p]]. It depends on the block size alone.
+struct InterpTree { uint8_t lo[128], hi[128]; };
+constexpr void interp_tree_fill(InterpTree& t, uint32_t off, uint32_t cnt, uint32_t lo, uint32_t hi) {
+    if (!cnt) return;
+    const uint32_t h = cnt / 2, pos = off + h;
+    t.lo[pos] = (uint8_t)lo;
+    t.hi[pos] = (uint8_t)hi;
+    interp_tree_fill(t, off, h, lo, pos);
+    interp_tree_fill(t, pos + 1, cnt - h - 1, pos + 1, hi);
+}
+constexpr InterpTree make_interp_tree() {
+    InterpTree t{};
+    interp_tree_fill(t, 0, 127, 0, 127);
+    return t;
+}
+__device__ static const InterpTree INTERP_TREE = make_interp_tree();
 
 __device__ static const uint8_t ENC_LOGS[17] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 16, 20, 32};
 // Simple16 layouts as (count, width) runs -- the same table the decoder uses (device_codecs.hpp S16_DESC)
@@ -278,61 +320,184 @@ DS2I_DEV uint32_t interpolative_part(EncLds& L, const uint32_t* vals, uint32_t n
     return bcast(bytes, 0);
 }
 
+// ---- VarInt-G8IU (host_encode.hpp varint_g8iu_encode): groups of 1 descriptor + 8 data bytes, an integer never
+// straddles groups, descriptor bit j cleared iff data byte j ends an integer, the last group zero padded.
+// The greedy grouping is a serial chain over the 128 byte lengths; they travel as four ballots, so the chain runs on the
+// scalar unit, the same in every lane, and each lane picks up the (group, offset) of its own two values on the way.
+// Returns the bytes (9 x groups); with WRITE the part is built in L.outw.
+template <bool WRITE>
+DS2I_DEV uint32_t varint_part(EncLds& L, uint32_t v0, uint32_t v1) {
+    const uint32_t lane = lane_id();
+    const uint32_t n0 = (v0 >= (1u << 8)) + (v0 >= (1u << 16)) + (v0 >= (1u << 24)); // byte length - 1
+    const uint32_t n1 = (v1 >= (1u << 8)) + (v1 >= (1u << 16)) + (v1 >= (1u << 24));
+    const uint64_t lo_bits[2] = {ballot(n0 & 1u), ballot(n1 & 1u)}, hi_bits[2] = {ballot(n0 >> 1), ballot(n1 >> 1)};
+    uint32_t g = 0, len = 0, my_g[2] = {0, 0}, my_off[2] = {0, 0};
+    for (int half = 0; half < 2; ++half) {
+        const uint64_t lb = lo_bits[half], hb = hi_bits[half];
+        for (uint32_t i = 0; i < 64; ++i) {
+            const uint32_t need = 1u + (uint32_t)((lb >> i) & 1u) + 2u * (uint32_t)((hb >> i) & 1u);
+            if (len + need > 8) { ++g; len = 0; }
+            if (WRITE && lane == i) { my_g[half] = g; my_off[half] = len; }
+            len += need;
+        }
+    }
+    const uint32_t groups = g + 1;
+    if (WRITE) {
+        for (uint32_t w = lane; w < (9 * groups + 3) / 4; w += 64) L.outw[w] = 0;
+        wave_sync();
+        uint8_t* ob = (uint8_t*)L.outw;
+        for (uint32_t q = lane; q < groups; q += 64) ob[9 * q] = 0xFF;
+        wave_sync();
+        for (int half = 0; half < 2; ++half) {
+            const uint32_t v = half ? v1 : v0, need = (half ? n1 : n0) + 1u, at = 9u * my_g[half] + 1u + my_off[half];
+            for (uint32_t j = 0; j < need; ++j) ob[at + j] = (uint8_t)(v >> (8 * j));
+        }
+        wave_sync();
+        for (int half = 0; half < 2; ++half) { // descriptors: up to 8 values clear a bit each in the same byte
+            const uint32_t at = 9u * my_g[half], end = my_off[half] + (half ? n1 : n0) + 1u;
+            atomicAnd(&L.outw[at >> 2], ~((1u << (end - 1)) << (8 * (at & 3u))));
+        }
+        wave_sync();
+    }
+    return 9 * groups;
+}
+
+// the values of the part sum to less than 2^32 - 1 (interp_ok, host_hybrid.hpp): 16-bit halves summed apart, no carry lost
+DS2I_DEV bool part_sum_fits(uint32_t v0, uint32_t v1) {
+    const uint32_t lo = bcast(wave_incl_scan((v0 & 0xFFFFu) + (v1 & 0xFFFFu)), 63);
+    const uint32_t hi = bcast(wave_incl_scan((v0 >> 16) + (v1 >> 16)), 63);
+    return (((uint64_t)hi << 16) + lo) < 0xFFFFFFFFull;
+}
+
+// Size of the interpolative code of a FULL block whose values sum to less than 2^32 - 1, every tree node at once: node p
+// costs the truncated-binary length of pre[p] - lo in a range of hi - lo + 1 (bit_writer32::write_int), and it is live
+// (host interp_live_nodes) iff hi != lo -- a degenerate node has only degenerate descendants. Returns the bytes, with the
+// vbyte of the sum in front where the part carries it (freqs); `live` receives the live-node count.
+DS2I_DEV uint32_t interp_size128(EncLds& L, const InterpTree& T, uint32_t v0, uint32_t v1, bool with_vbyte, uint32_t& live) {
+    const uint32_t lane = lane_id();
+    const uint32_t s0 = wave_incl_scan(v0);
+    const uint32_t s1 = wave_incl_scan(v1) + bcast(s0, 63);
+    L.exc[lane] = s0;
+    L.exc[64 + lane] = s1;
+    wave_sync();
+    uint32_t bits = 0, nl = 0;
+    for (uint32_t p = lane; p < 127; p += 64) {
+        const uint32_t li = T.lo[p], lo = li ? L.exc[li - 1] : 0u, hi = L.exc[T.hi[p]], val = L.exc[p] - lo;
+        const uint32_t u = hi - lo + 1u; // >= 1: the sum is below 2^32 - 1
+        const uint32_t b = 31u - (uint32_t)__builtin_clz(u);
+        const uint64_t m = (1ull << (b + 1)) - u;
+        bits += val < m ? b : b + 1u;
+        nl += hi != lo;
+    }
+    const uint32_t sum = L.exc[127];
+    const uint32_t packed = bcast(wave_incl_scan(bits | (nl << 16)), 63); // bits <= 127 * 32 < 2^16, live <= 127
+    wave_sync();
+    live = packed >> 16;
+    uint32_t bytes = ((packed & 0xFFFFu) + 7u) / 8u;
+    if (with_vbyte) bytes += 1u + (sum >= (1u << 7)) + (sum >= (1u << 14)) + (sum >= (1u << 21)) + (sum >= (1u << 28));
+    return bytes;
+}
+
+DS2I_DEV void interp_tree_init(InterpTree& T) {
+    const uint32_t lane = lane_id();
+    T.lo[lane] = INTERP_TREE.lo[lane];
+    T.lo[lane + 64] = INTERP_TREE.lo[lane + 64];
+    T.hi[lane] = INTERP_TREE.hi[lane];
+    T.hi[lane + 64] = INTERP_TREE.hi[lane + 64];
+    wave_sync();
+}
+
 DS2I_DEV void copy_out(const EncLds& L, uint8_t* dst, uint32_t bytes) {
     const uint8_t* src = (const uint8_t*)L.outw;
     for (uint32_t i = lane_id(); i < bytes; i += 64) dst[i] = src[i];
 }
 
-template <bool WRITE>
+// gap - 1 and freq - 1 of one block, index order (block_posting_list.hpp:31-37): in registers (value `lane` and
+// `lane + 64`) and in L.v[0] / L.v[1]
+struct BlockIn {
+    uint32_t t, lb, n, sz; // list, block of the list, postings of the list, postings of the block
+    uint32_t g0, g1, f0, f1;
+    uint32_t last_doc, block_base;
+};
+DS2I_DEV BlockIn load_block(const EncArgs& a, EncLds& L, uint32_t blk) {
+    const uint32_t lane = lane_id();
+    BlockIn B;
+    B.t = a.blk_list[blk];
+    B.lb = blk - a.list_blk0[B.t];
+    const uint64_t in0 = a.list_in[B.t];
+    B.n = (uint32_t)(a.list_in[B.t + 1] - in0);
+    const uint64_t k0 = in0 + 128ull * B.lb;
+    const uint32_t sz = B.n - 128u * B.lb < 128u ? B.n - 128u * B.lb : 128u;
+    B.sz = sz;
+    const uint32_t d0 = lane < sz ? a.docs[k0 + lane] : 0, d1 = lane + 64 < sz ? a.docs[k0 + 64 + lane] : 0;
+    const uint32_t prev_last = B.lb ? a.docs[k0 - 1] : 0xFFFFFFFFu;
+    L.v[1][lane] = d0;
+    L.v[1][lane + 64] = d1;
+    wave_sync();
+    const uint32_t p0 = lane ? L.v[1][lane - 1] : prev_last, p1 = L.v[1][lane + 63];
+    B.g0 = lane < sz ? d0 - p0 - 1u : 0u;
+    B.g1 = lane + 64 < sz ? d1 - p1 - 1u : 0u;
+    B.f0 = lane < sz ? a.freqs[k0 + lane] - 1u : 0u;
+    B.f1 = lane + 64 < sz ? a.freqs[k0 + 64 + lane] - 1u : 0u;
+    B.last_doc = uniform(L.v[1][sz - 1]);
+    wave_sync();
+    L.v[0][lane] = B.g0;
+    L.v[0][lane + 64] = B.g1;
+    L.v[1][lane] = B.f0;
+    L.v[1][lane + 64] = B.f1;
+    wave_sync();
+    B.block_base = B.lb ? prev_last + 1u : 0u;
+    return B;
+}
+
+template <bool WRITE, int MODE>
 __global__ void __launch_bounds__(64) k_encode(EncArgs a) {
+    static_assert(MODE != ENC_MIXED || WRITE, "the sizes of a block_mixed image come from the optimiser's hulls");
     __shared__ EncLds L;
+    __shared__ InterpTree T; // (unused, and dropped, where MODE is ENC_OPTPFOR)
     const uint32_t lane = lane_id();
     enc_tables_init(L);
+    if (MODE == ENC_INTERP && !WRITE) interp_tree_init(T);
     for (uint32_t blk = blockIdx.x; blk < a.nblocks; blk += gridDim.x) {
-        const uint32_t t = a.blk_list[blk];
-        const uint32_t lb = blk - a.list_blk0[t];
-        const uint64_t in0 = a.list_in[t];
-        const uint32_t n = (uint32_t)(a.list_in[t + 1] - in0);
-        const uint64_t k0 = in0 + 128ull * lb;
-        const uint32_t sz = n - 128u * lb < 128u ? n - 128u * lb : 128u;
-        // gap - 1 and freq - 1, index order (block_posting_list.hpp:31-37)
-        const uint32_t d0 = lane < sz ? a.docs[k0 + lane] : 0, d1 = lane + 64 < sz ? a.docs[k0 + 64 + lane] : 0;
-        const uint32_t prev_last = lb ? a.docs[k0 - 1] : 0xFFFFFFFFu;
-        L.v[1][lane] = d0;
-        L.v[1][lane + 64] = d1;
-        wave_sync();
-        const uint32_t p0 = lane ? L.v[1][lane - 1] : prev_last, p1 = L.v[1][lane + 63];
-        const uint32_t g0 = lane < sz ? d0 - p0 - 1u : 0u, g1 = lane + 64 < sz ? d1 - p1 - 1u : 0u;
-        const uint32_t f0 = lane < sz ? a.freqs[k0 + lane] - 1u : 0u, f1 = lane + 64 < sz ? a.freqs[k0 + 64 + lane] - 1u : 0u;
-        const uint32_t last_doc = uniform(L.v[1][sz - 1]);
-        wave_sync();
-        L.v[0][lane] = g0;
-        L.v[0][lane + 64] = g1;
-        L.v[1][lane] = f0;
-        L.v[1][lane + 64] = f1;
-        wave_sync();
-        const uint32_t block_base = lb ? prev_last + 1u : 0u;
+        const BlockIn B = load_block(a, L, blk);
+        const uint32_t t = B.t, lb = B.lb, n = B.n, sz = B.sz, last_doc = B.last_doc;
+        const uint32_t sum_docs = last_doc - B.block_base - (sz - 1);
         uint8_t* dst = nullptr;
         if (WRITE) dst = a.out + a.blk_out[blk];
         for (int part = 0; part < 2; ++part) {
-            const uint32_t v0 = part ? f0 : g0, v1 = part ? f1 : g1;
+            const uint32_t v0 = part ? B.f0 : B.g0, v1 = part ? B.f1 : B.g1;
+            const uint32_t sum = part ? 0xFFFFFFFFu : sum_docs;
             uint32_t bytes;
-            if (sz == 128) {
+            if (sz != 128) {
+                bytes = interpolative_part(L, L.v[part], sz, sum);
+            } else if (MODE == ENC_OPTPFOR) {
                 uint32_t b;
                 if (WRITE) b = a.bsel[2ull * blk + part];
                 else b = optpfor_find_best_b(L, v0, v1);
                 bytes = optpfor_part<WRITE>(L, v0, v1, b);
                 if (!WRITE && lane == 0) a.bsel[2ull * blk + part] = (uint8_t)b;
-            } else {
-                bytes = interpolative_part(L, L.v[part], sz, part ? 0xFFFFFFFFu : last_doc - block_base - (sz - 1));
+            } else if (MODE == ENC_VARINT) {
+                bytes = varint_part<WRITE>(L, v0, v1);
+            } else if (MODE == ENC_INTERP) {
+                uint32_t live;
+                // a part whose sum wraps is sized by the writer itself: both code the same wrapped prefix sums
+                if (!WRITE && part_sum_fits(v0, v1)) bytes = interp_size128(L, T, v0, v1, part != 0, live);
+                else bytes = interpolative_part(L, L.v[part], sz, sum);
+            } else { // ENC_MIXED: type byte, then the part in the chosen encoding (mixed_encode_type)
+                const uint32_t type = a.choice[4ull * blk + 2 * part], b = a.choice[4ull * blk + 2 * part + 1];
+                if (type == MIX_PFOR) bytes = optpfor_part<true>(L, v0, v1, b);
+                else if (type == MIX_VARINT) bytes = varint_part<true>(L, v0, v1);
+                else bytes = interpolative_part(L, L.v[part], sz, sum);
+                if (lane == 0) *dst = (uint8_t)type;
+                ++dst;
             }
             if (WRITE) {
                 copy_out(L, dst, bytes);
                 dst += bytes;
                 wave_sync();
-            } else if (lane == 0) {
-                a.psize[2ull * blk + part] = bytes;
             }
+            // (the block_mixed write pass reports what it wrote: the host holds it against the hull's size)
+            if ((!WRITE || MODE == ENC_MIXED) && lane == 0) a.psize[2ull * blk + part] = bytes + (MODE == ENC_MIXED && sz == 128);
         }
         if (!WRITE) {
             if (lane == 0) a.bmax[blk] = last_doc;
@@ -360,14 +525,81 @@ __global__ void __launch_bounds__(64) k_encode(EncArgs a) {
     }
 }
 
+// The optimiser's plan pass: one HybRec per part. Candidates as hybrid_part_measure (host_hybrid.hpp): OptPFor at every
+// b of ENC_LOGS except those past the first b >= max_b and those the exception coder cannot serve (max_b - b > 28) --
+// no early stop, unlike findBestB --, VarInt-G8IU, interpolative where the sum allows it.
+__global__ void __launch_bounds__(64) k_hybrid_plan(EncArgs a) {
+    __shared__ EncLds L;
+    __shared__ InterpTree T;
+    const uint32_t lane = lane_id();
+    enc_tables_init(L);
+    interp_tree_init(T);
+    for (uint32_t blk = blockIdx.x; blk < a.nblocks; blk += gridDim.x) {
+        const BlockIn B = load_block(a, L, blk);
+        const uint32_t sz = B.sz;
+        for (int part = 0; part < 2; ++part) {
+            HybRec* rec = (HybRec*)a.rec + (2ull * blk + part);
+            const uint32_t v0 = part ? B.f0 : B.g0, v1 = part ? B.f1 : B.g1;
+            uint32_t my_words = 0xFFFFu, my_nexc = 0, ok = 0, varint = 0, interp = 0, live = 0;
+            if (sz != 128) {
+                interp = interpolative_part(L, L.v[part], sz, part ? 0xFFFFFFFFu : B.last_doc - B.block_base - (sz - 1));
+            } else {
+                const uint32_t orv = wave_or_all(v0 | v1);
+                const uint32_t max_b = orv ? 32u - (uint32_t)__builtin_clz(orv) : 0u;
+                for (uint32_t i = 0; i < 17; ++i) {
+                    const uint32_t b = ENC_LOGS[i];
+                    if (b > max_b && i > 0 && ENC_LOGS[i - 1] >= max_b) continue;
+                    if (max_b > b && max_b - b > 28) continue;
+                    uint32_t words = 128, nexc = 0;
+                    if (b != 32) {
+                        nexc = optpfor_exceptions(L, v0, v1, b);
+                        words = 4 * b;
+                        if (nexc) words += simple16_words<false>(L, 2 * nexc, nullptr);
+                        wave_sync();
+                    }
+                    if (lane == i) { my_words = words; my_nexc = nexc; }
+                }
+                varint = varint_part<false>(L, v0, v1);
+                ok = part_sum_fits(v0, v1);
+                if (ok) interp = interp_size128(L, T, v0, v1, part != 0, live);
+            }
+            if (lane < 17) {
+                rec->pfor_words[lane] = (uint16_t)my_words;
+                rec->nexc[lane] = (uint8_t)my_nexc;
+            }
+            if (lane == 0) {
+                rec->interp_ok = (uint8_t)ok;
+                rec->varint_bytes = (uint16_t)varint;
+                rec->interp_bytes = (uint16_t)interp;
+                rec->live = (uint16_t)live;
+            }
+        }
+        wave_sync();
+    }
+}
+
 } // namespace
 
 extern "C" {
 size_t ds2i_sizeof_enc_args() { return sizeof(EncArgs); }
-hipError_t ds2i_launch_encode(int write, const void* args, unsigned grid, hipStream_t s) {
+size_t ds2i_sizeof_hyb_rec() { return sizeof(HybRec); }
+// mode: the codec_kind of the image (block_optpfor, block_varint, block_interpolative; block_mixed has a write pass only)
+hipError_t ds2i_launch_encode(int mode, int write, const void* args, unsigned grid, hipStream_t s) {
     const EncArgs& a = *(const EncArgs*)args;
-    if (write) hipLaunchKernelGGL(k_encode<true>, dim3(grid), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL(k_encode<false>, dim3(grid), dim3(64), 0, s, a);
+    const dim3 g(grid), b(64);
+    if (mode == ENC_OPTPFOR && write) hipLaunchKernelGGL((k_encode<true, ENC_OPTPFOR>), g, b, 0, s, a);
+    else if (mode == ENC_OPTPFOR) hipLaunchKernelGGL((k_encode<false, ENC_OPTPFOR>), g, b, 0, s, a);
+    else if (mode == ENC_VARINT && write) hipLaunchKernelGGL((k_encode<true, ENC_VARINT>), g, b, 0, s, a);
+    else if (mode == ENC_VARINT) hipLaunchKernelGGL((k_encode<false, ENC_VARINT>), g, b, 0, s, a);
+    else if (mode == ENC_INTERP && write) hipLaunchKernelGGL((k_encode<true, ENC_INTERP>), g, b, 0, s, a);
+    else if (mode == ENC_INTERP) hipLaunchKernelGGL((k_encode<false, ENC_INTERP>), g, b, 0, s, a);
+    else if (mode == ENC_MIXED && write) hipLaunchKernelGGL((k_encode<true, ENC_MIXED>), g, b, 0, s, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+hipError_t ds2i_launch_hybrid_plan(const void* args, unsigned grid, hipStream_t s) {
+    const EncArgs& a = *(const EncArgs*)args;
+    hipLaunchKernelGGL(k_hybrid_plan, dim3(grid), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 }

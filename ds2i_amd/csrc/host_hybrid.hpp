@@ -51,44 +51,76 @@ inline uint32_t interp_live_nodes(const uint32_t* pre, size_t n, uint32_t low, u
     return 1 + interp_live_nodes(pre, h, low, val) + interp_live_nodes(pre + h + 1, n - h - 1, val, high);
 }
 
-// all (space, time) candidates of one block, then its lower convex hull sorted by increasing space
-inline void hybrid_block_points(const uint32_t* in, uint32_t sum, size_t n, uint32_t access, hybrid_model const& m,
-                                std::vector<hybrid_point>& hull) {
-    hull.clear();
-    std::vector<hybrid_point> pts;
+// What the candidates of one part cost, as integers: the expensive half of the analysis (every encoder runs), and the
+// half the GPU plan kernel computes instead (encode_kernels.hip k_hybrid_plan fills the same record).
+struct hybrid_part_rec {
+    uint16_t pfor_words[17]; // payload words of OptPFor at OPTPFOR_LOGS[i] (packed values + Simple16 exceptions), 0xFFFF: not a candidate
+    uint8_t nexc[17];        // exceptions at that b
+    uint8_t interp_ok;       // the values sum to less than 2^32 - 1 (interpolative codes u32 prefix sums)
+    uint16_t varint_bytes;
+    uint16_t interp_bytes;   // full blocks: valid if interp_ok; partial blocks: the only field that is read
+    uint16_t live;           // interp_live_nodes
+    uint16_t pad[3];
+};
+static_assert(sizeof(hybrid_part_rec) == 64, "hybrid_part_rec layout");
+
+inline void hybrid_part_measure(const uint32_t* in, uint32_t sum, size_t n, hybrid_part_rec& r) {
+    std::memset(&r, 0, sizeof r);
     bytes_t buf;
-    const float w = (float)access + 1.f;
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; ++i) total += in[i];
-    const bool interp_ok = total < 0xFFFFFFFFull;
-    if (n < BLOCK) { // partial blocks: interpolative only, no time prediction (mixed_block.hpp:69-71,143)
+    if (n < BLOCK) { // partial blocks: interpolative only (mixed_block.hpp:69-71,143)
         interpolative_encode(in, sum, n, buf);
-        hull.push_back(hybrid_point{0.f, (uint16_t)buf.size(), (uint8_t)MIXED_INTERP, -1});
+        r.interp_bytes = (uint16_t)buf.size();
         return;
     }
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; ++i) total += in[i];
+    r.interp_ok = total < 0xFFFFFFFFull;
     const uint32_t max_b = maxbits128(in);
     for (int i = 0; i < 17; ++i) {
         const uint32_t b = OPTPFOR_LOGS[i];
+        r.pfor_words[i] = 0xFFFF;
         if (b > max_b && i > 0 && OPTPFOR_LOGS[i - 1] >= max_b) continue; // useless
         if (max_b > b && max_b - b > 28) continue;                         // exception coder cannot hold it
         uint32_t nexc = 0;
         if (b < 32) for (size_t k = 0; k < BLOCK; ++k) nexc += (in[k] >> b) != 0;
-        const uint32_t words = optpfor_try_b(b, in);            // payload words: packed values + Simple16 exceptions
+        r.nexc[i] = (uint8_t)nexc;
+        r.pfor_words[i] = (uint16_t)optpfor_try_b(b, in);       // payload words: packed values + Simple16 exceptions
+    }
+    varint_g8iu_encode(in, sum, n, buf);
+    r.varint_bytes = (uint16_t)buf.size();
+    if (r.interp_ok) {
+        buf.clear();
+        interpolative_encode(in, sum, n, buf);
+        r.interp_bytes = (uint16_t)buf.size();
+        uint32_t pre[BLOCK];
+        pre[0] = in[0];
+        for (size_t i = 1; i < n; ++i) pre[i] = pre[i - 1] + in[i];
+        r.live = (uint16_t)interp_live_nodes(pre, n - 1, 0, pre[n - 1]);
+    }
+}
+
+// record -> (space, time) candidates -> lower convex hull sorted by increasing space. Every float of the optimiser is
+// computed here, by these expressions, whichever side measured the record.
+inline void hybrid_hull_of(hybrid_part_rec const& r, size_t n, uint32_t access, hybrid_model const& m,
+                           std::vector<hybrid_point>& hull) {
+    hull.clear();
+    if (n < BLOCK) { // no time prediction (mixed_block.hpp:143)
+        hull.push_back(hybrid_point{0.f, r.interp_bytes, (uint8_t)MIXED_INTERP, -1});
+        return;
+    }
+    std::vector<hybrid_point> pts;
+    const float w = (float)access + 1.f;
+    for (int i = 0; i < 17; ++i) {
+        if (r.pfor_words[i] == 0xFFFF) continue;
+        const uint32_t b = OPTPFOR_LOGS[i], nexc = r.nexc[i], words = r.pfor_words[i];
         const uint32_t space = 1 + 4 * (1 + words);             // type byte + header word + payload
         const float t = m.pfor_base + (nexc == 0 ? 0.f : nexc <= 32 ? m.pfor_exc : m.pfor_exc_many);
         pts.push_back(hybrid_point{t * w, (uint16_t)space, (uint8_t)MIXED_PFOR, (int8_t)b});
     }
-    buf.clear();
-    varint_g8iu_encode(in, sum, n, buf);
-    pts.push_back(hybrid_point{m.varint * w, (uint16_t)(1 + buf.size()), (uint8_t)MIXED_VARINT, -1});
-    if (interp_ok) {
-        buf.clear();
-        interpolative_encode(in, sum, n, buf);
-        uint32_t pre[BLOCK];
-        pre[0] = in[0];
-        for (size_t i = 1; i < n; ++i) pre[i] = pre[i - 1] + in[i];
-        const uint32_t live = interp_live_nodes(pre, n - 1, 0, pre[n - 1]);
-        pts.push_back(hybrid_point{(m.interp_base + m.interp_node * live) * w, (uint16_t)(1 + buf.size()), (uint8_t)MIXED_INTERP, -1});
+    pts.push_back(hybrid_point{m.varint * w, (uint16_t)(1 + r.varint_bytes), (uint8_t)MIXED_VARINT, -1});
+    if (r.interp_ok) {
+        const uint32_t live = r.live;
+        pts.push_back(hybrid_point{(m.interp_base + m.interp_node * live) * w, (uint16_t)(1 + r.interp_bytes), (uint8_t)MIXED_INTERP, -1});
     }
     // lower convex hull (optimal_hybrid_index.cpp:92-113): sort by (space, time); keep points that are faster than
     // every smaller one and whose exchange rate d(space)/d(time) keeps increasing
@@ -109,6 +141,14 @@ inline void hybrid_block_points(const uint32_t* in, uint32_t sum, size_t n, uint
             break;
         }
     }
+}
+
+// all (space, time) candidates of one block, then its lower convex hull sorted by increasing space
+inline void hybrid_block_points(const uint32_t* in, uint32_t sum, size_t n, uint32_t access, hybrid_model const& m,
+                                std::vector<hybrid_point>& hull) {
+    hybrid_part_rec r;
+    hybrid_part_measure(in, sum, n, r);
+    hybrid_hull_of(r, n, access, m, hull);
 }
 
 // argmin over the hull of time + space / rate  (rate = bytes one is willing to pay per unit of time saved)
@@ -280,6 +320,61 @@ public:
 
     uint64_t lists() const { return m_lists.size(); }
     bool analysed() const { return m_analysed; }
+
+    // ---- the doors of the GPU path (capi_encode.cpp: ds2i_hip_hybrid_analyse / ds2i_hip_hybrid_freeze)
+    bool has_virtual() const {
+        for (auto const& L : m_lists) if (L.is_virtual) return true;
+        return false;
+    }
+    uint64_t num_docs() const { return m_num_docs; }
+    uint64_t list_size(size_t t) const { return m_lists[t].docs.size(); }
+    const uint32_t* list_docs(size_t t) const { return m_lists[t].docs.data(); }
+    const uint32_t* list_freqs(size_t t) const { return m_lists[t].freqs.data(); }
+    // the analysis from measured records: 2 per block (docs part, freqs part), blocks numbered list by list
+    void analyse_from_records(const hybrid_part_rec* recs, int threads) {
+        const size_t V = m_lists.size();
+        std::vector<uint64_t> blk0(V + 1, 0);
+        for (size_t t = 0; t < V; ++t) blk0[t + 1] = blk0[t] + ceil_div((uint64_t)m_lists[t].docs.size(), (uint64_t)BLOCK);
+        std::atomic<size_t> next(0);
+        auto worker = [&]() {
+            std::vector<hybrid_point> hull;
+            for (;;) {
+                const size_t t = next.fetch_add(1);
+                if (t >= V) break;
+                list_t& L = m_lists[t];
+                const uint64_t n = L.docs.size(), blocks = blk0[t + 1] - blk0[t];
+                L.hull_off.assign(2 * blocks + 1, 0);
+                L.hull.clear();
+                for (uint64_t b = 0; b < blocks; ++b) {
+                    const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (uint32_t)(n % BLOCK);
+                    for (int side = 0; side < 2; ++side) {
+                        hybrid_hull_of(recs[2 * (blk0[t] + b) + side], cur, L.access.empty() ? 0 : L.access[2 * b + side], m_model, hull);
+                        L.hull.insert(L.hull.end(), hull.begin(), hull.end());
+                        L.hull_off[2 * b + side + 1] = (uint32_t)L.hull.size();
+                    }
+                }
+            }
+        };
+        run_threads(threads, worker);
+        m_analysed = true;
+    }
+    // hull of one part (analysed builders): null if there is no such part
+    const hybrid_point* hull(uint64_t list, uint64_t block, int side, uint32_t& n) const {
+        if (!m_analysed || list >= m_lists.size() || side < 0 || side > 1) return nullptr;
+        list_t const& L = m_lists[list];
+        if (2 * block + side + 1 >= L.hull_off.size()) return nullptr;
+        n = L.hull_off[2 * block + side + 1] - L.hull_off[2 * block + side];
+        return L.hull.data() + L.hull_off[2 * block + side];
+    }
+    // the point every part takes at that rate, in index order (what freeze encodes)
+    template <class F>
+    void for_each_choice(double rate, F f) const {
+        for (auto const& L : m_lists)
+            for (size_t j = 0; j + 1 < L.hull_off.size(); ++j) {
+                const hybrid_point* h = L.hull.data() + L.hull_off[j];
+                f(h[hybrid_choose(h, L.hull_off[j + 1] - L.hull_off[j], rate)]);
+            }
+    }
 
 private:
     struct list_t {

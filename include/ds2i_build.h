@@ -4,7 +4,8 @@
  * compiled here (create_freq_index.cpp:45-110, create_wand_data.cpp:8-29,
  * block_freq_index::builder block_freq_index.hpp:18-70). They produce the reference's on-disk
  * images (block_freq_index / wand_data) that ds2i_hip_index_open consumes. Nothing here is on
- * the timed query path and nothing here touches the GPU.
+ * the timed query path and nothing here touches the GPU: the GPU forms of the encoder and of the
+ * block_mixed optimiser (ds2i_hip_encode_index, ds2i_hip_hybrid_analyse / _freeze) are in ds2i_hip.h.
  */
 #ifndef DS2I_BUILD_H
 #define DS2I_BUILD_H
@@ -108,6 +109,10 @@ int ds2i_hybrid_analyse(ds2i_hybrid* h, int threads, uint64_t* min_space, uint64
  * {docs pfor, docs varint, docs interpolative, freqs pfor, freqs varint, freqs interpolative} */
 int ds2i_hybrid_freeze(ds2i_hybrid* h, uint64_t budget_bytes, int threads, ds2i_blob** image, double* rate,
                        uint64_t* space, double* model_time, uint64_t type_counts[6]);
+/* hull of one part after analyse (either path: this one or ds2i_hip_hybrid_analyse, ds2i_hip.h): side 0 = docs,
+ * 1 = freqs; points as {float time; uint16 space; uint8 type; int8 b}, by increasing space and decreasing time.
+ * n receives the hull's size, at most `capacity` points are written. */
+int ds2i_hybrid_hull(const ds2i_hybrid* h, uint64_t list, uint64_t block, int side, void* points, uint32_t capacity, uint32_t* n);
 void ds2i_hybrid_free(ds2i_hybrid* h);
 
 /* synthetic collection */

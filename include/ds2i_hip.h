@@ -250,12 +250,28 @@ void ds2i_hip_pipeline_destroy(ds2i_hip_pipeline* p);
 /* GPU index encoder (build side): block_posting_list::write (block_posting_list.hpp:13-53) with
  * optpfor_block::encode + ds2i's findBestB (block_codecs.hpp:156-208) as HIP kernels, one wavefront per 128-posting
  * block. Input: nlists posting lists in CSR form (list t = docs / freqs [list_offsets[t], list_offsets[t+1])), sorted
- * doc-ids < num_docs, freqs >= 1. Output: the frozen block_freq_index<optpfor_block> image (ds2i_blob_* of
- * ds2i_build.h release it), byte-identical to the host builder's (ds2i_builder_*). index_kind must be
- * DS2I_BLOCK_OPTPFOR. device_ms (may be NULL) receives the hipEvent time of the two kernel passes. */
+ * doc-ids < num_docs, freqs >= 1. Output: the frozen block_freq_index image of that kind (ds2i_blob_* of
+ * ds2i_build.h release it), byte-identical to the host builder's (ds2i_builder_*). index_kind is DS2I_BLOCK_OPTPFOR,
+ * DS2I_BLOCK_VARINT (every full block VarInt-G8IU) or DS2I_BLOCK_INTERPOLATIVE; DS2I_BLOCK_QMX has no GPU encoder and
+ * DS2I_BLOCK_MIXED images come from ds2i_hip_hybrid_freeze below: both are DS2I_EINVAL here. device_ms (may be NULL)
+ * receives the hipEvent time of the two kernel passes. */
 typedef struct ds2i_blob ds2i_blob;
 int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                           const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms);
+
+/* The block_mixed optimiser of ds2i_build.h (ds2i_hybrid_*) with its build side on the GPU. They
+ * live here because nothing in ds2i_build.h touches the GPU; the handle is the one ds2i_hybrid_create returns, filled
+ * with ds2i_hybrid_add_posting_list. A builder that holds virtual lists (ds2i_synth_build_hybrid) is DS2I_EINVAL.
+ * analyse: a plan kernel measures every candidate of every 128-value part (OptPFor at each usable b, VarInt-G8IU,
+ * interpolative: sizes and counts, integers only); the host turns them into the same (space, time) hulls as
+ * ds2i_hybrid_analyse, bit for bit, so either analysis serves either freeze, ds2i_hybrid_hull included.
+ * freeze: solves the budget on the host as ds2i_hybrid_freeze does (analysing on the device first if need be) and
+ * writes the chosen encodings in one kernel pass; image, rate, space, model_time and type_counts equal the host's.
+ * device_ms (may be NULL) receives the hipEvent time of the kernels this call ran. */
+struct ds2i_hybrid;
+int ds2i_hip_hybrid_analyse(struct ds2i_hybrid* h, int device, uint64_t* min_space, uint64_t* max_space, double* device_ms);
+int ds2i_hip_hybrid_freeze(struct ds2i_hybrid* h, int device, uint64_t budget_bytes, ds2i_blob** image, double* rate,
+                           uint64_t* space, double* model_time, uint64_t type_counts[6], double* device_ms);
 
 /* The synthetic collection of ds2i_build.h generated on `threads` host threads (<= 0: all) and encoded on the GPU;
  * the same two images as ds2i_synth_build(p, DS2I_BLOCK_OPTPFOR, ...), byte for byte. wand_image, total_postings,
