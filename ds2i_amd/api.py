@@ -136,6 +136,9 @@ def lib():
         L.ds2i_hip_synth_encode.argtypes = [C.c_int, C.POINTER(SynthParams), C.c_int, C.POINTER(vp), C.POINTER(vp), u64p,
                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.ds2i_hip_encode_index.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_build_wand.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_build_collection.argtypes = [C.c_int, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(vp),
+                                                C.POINTER(C.c_double)]
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -253,19 +256,49 @@ def build_index(codec, num_docs, lists):
         L.ds2i_builder_free(b)
 
 
-def gpu_encode_index(num_docs, lists, device=0, codec="block_optpfor"):
-    """The index image of `lists` (iterable of (docs, freqs)) encoded ON THE GPU (ds2i_hip_encode_index): byte-identical
-    to build_index(codec, num_docs, lists). Returns (image bytes, device milliseconds of the two kernel passes)."""
+def _csr(lists):
+    """(number of lists, offsets uint64[n + 1], docs, freqs) -- the form posting lists cross the C ABI in"""
     lists = [(_u32(dd), _u32(ff)) for dd, ff in lists]
     offs = np.zeros(len(lists) + 1, dtype=np.uint64)
     for i, (dd, _) in enumerate(lists):
         offs[i + 1] = offs[i] + len(dd)
     docs = np.concatenate([dd for dd, _ in lists]) if lists else np.zeros(1, np.uint32)
     freqs = np.concatenate([ff for _, ff in lists]) if lists else np.zeros(1, np.uint32)
+    return len(lists), offs, docs, freqs
+
+
+def gpu_encode_index(num_docs, lists, device=0, codec="block_optpfor"):
+    """The index image of `lists` (iterable of (docs, freqs)) encoded ON THE GPU (ds2i_hip_encode_index): byte-identical
+    to build_index(codec, num_docs, lists). Returns (image bytes, device milliseconds of the two kernel passes)."""
+    n, offs, docs, freqs = _csr(lists)
     h, ms = C.c_void_p(), C.c_double()
-    _check(lib().ds2i_hip_encode_index(device, _codec(codec), num_docs, len(lists), _ptr(offs), _ptr(docs), _ptr(freqs),
+    _check(lib().ds2i_hip_encode_index(device, _codec(codec), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
                                        C.byref(h), C.byref(ms)))
     return _take_blob(h), ms.value
+
+
+def gpu_build_wand(doc_sizes, lists, device=0):
+    """The wand_data image of `lists` over documents of `doc_sizes` built ON THE GPU (ds2i_hip_build_wand): byte-identical
+    to build_wand(doc_sizes, lists). Returns (image bytes, dict(device_ms))."""
+    s = _u32(doc_sizes)
+    n, offs, docs, freqs = _csr(lists)
+    h, ms = C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_build_wand(device, _ptr(s), len(s), n, _ptr(offs), _ptr(docs), _ptr(freqs), C.byref(h), C.byref(ms)))
+    return _take_blob(h), {"device_ms": ms.value}
+
+
+def gpu_build_collection(num_docs, doc_sizes, lists, codec="block_optpfor", device=0):
+    """Index image and wand_data image of one collection from ONE staging on the GPU (ds2i_hip_build_collection): what
+    gpu_encode_index and gpu_build_wand return, everything Index(codec, index, wand) needs.
+    Returns (index image, wand image, dict(device_ms))."""
+    s = _u32(doc_sizes)
+    if len(s) != num_docs:
+        raise ValueError("doc_sizes holds %d lengths for %d documents" % (len(s), num_docs))
+    n, offs, docs, freqs = _csr(lists)
+    hi, hw, ms = C.c_void_p(), C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_build_collection(device, _codec(codec), _ptr(s), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
+                                           C.byref(hi), C.byref(hw), C.byref(ms)))
+    return _take_blob(hi), _take_blob(hw), {"device_ms": ms.value}
 
 
 def synth_build_gpu(p, device=0, threads=0):

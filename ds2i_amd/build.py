@@ -13,8 +13,8 @@ ARCH = "gfx950"
 
 # ranked_stream.hip holds the pipelined ranked_and kernels of the benchmark configuration;
 # kernels.hip is compiled six times: once per list-count class (-DDS2I_TU_TMAX=n: the query kernels of that class; 0 = the
-# long class) and once for everything else; encode_kernels.hip holds the index encoder; all units are built in parallel
-DEVICE_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [("kernels.hip", "kernels.hip", []), ("ranked_stream.hip", "ranked_stream.hip", []), ("ranked_stream.hip", "ranked_stream_bigk.hip", ["-DDS2I_RS_BIGK_TU"]), ("ranked_stream_mixed.hip", "ranked_stream_mixed.hip", []), ("freq_stream.hip", "freq_stream.hip", []), ("union_stream.hip", "union_stream.hip", []), ("union_stream.hip", "union_stream_bigk.hip", ["-DDS2I_US_BIGK_TU"]), ("encode_kernels.hip", "encode_kernels.hip", [])]
+# long class) and once for everything else; encode_kernels.hip holds the index encoder, wand_kernels.hip the wand_data builder; all units are built in parallel
+DEVICE_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [("kernels.hip", "kernels.hip", []), ("ranked_stream.hip", "ranked_stream.hip", []), ("ranked_stream.hip", "ranked_stream_bigk.hip", ["-DDS2I_RS_BIGK_TU"]), ("ranked_stream_mixed.hip", "ranked_stream_mixed.hip", []), ("freq_stream.hip", "freq_stream.hip", []), ("union_stream.hip", "union_stream.hip", []), ("union_stream.hip", "union_stream_bigk.hip", ["-DDS2I_US_BIGK_TU"]), ("encode_kernels.hip", "encode_kernels.hip", []), ("wand_kernels.hip", "wand_kernels.hip", [])]
 # DS2I_OP_TOPK_DOCS: the same sources once more with -DDS2I_DOCS_TU -- the ranked kernels with (score, doc-id) heaps, named *_docs
 # (device_enum.hpp); each docs unit mirrors a scores-only unit above, so the build stays as parallel as before
 DOCS_UNITS = [("kernels.hip", "kernels_t%d_docs.hip" % t, ["-DDS2I_DOCS_TU", "-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [

@@ -5,6 +5,9 @@
 // The block_mixed optimiser's device half lives here too (ds2i_hip_hybrid_analyse / ds2i_hip_hybrid_freeze; §8(f) item
 // 3): the plan kernel measures every candidate of every part, the host builds hulls and solves the budget
 // (host_hybrid.hpp, shared with the host path), and one write pass lays the chosen encodings down.
+// The wand_data image is built over the same staging (ds2i_hip_build_wand; ds2i_hip_build_collection returns it together
+// with the index image from ONE upload): norm_lens on the host as compute_norm_lens writes them, every list's maximum
+// term weight by wand_kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -22,6 +25,9 @@ size_t ds2i_sizeof_enc_args();
 size_t ds2i_sizeof_hyb_rec();
 hipError_t ds2i_launch_encode(int mode, int write, const void* args, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_hybrid_plan(const void* args, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_wand_list_max(const uint32_t* docs, const uint32_t* freqs, const uint64_t* list_in, const uint32_t* blk_list,
+                                     const uint32_t* list_blk0, uint32_t nblocks, const float* norm_lens, uint64_t num_docs,
+                                     unsigned int* list_max, unsigned max_groups, hipStream_t s);
 }
 
 namespace {
@@ -183,17 +189,9 @@ struct EncStage {
         const int rc_ = (call);        \
         if (rc_ != DS2I_OK) return rc_; \
     } while (0)
-} // namespace
 
-extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
-                                     const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms) {
-    if (!list_offsets || !docs || !freqs || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: null argument");
-    if (index_kind != DS2I_BLOCK_OPTPFOR && index_kind != DS2I_BLOCK_VARINT && index_kind != DS2I_BLOCK_INTERPOLATIVE)
-        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: the GPU encoder writes block_optpfor, block_varint and block_interpolative indexes");
-    const int codec = index_kind == DS2I_BLOCK_OPTPFOR ? ds2i_host::CODEC_OPTPFOR
-                      : index_kind == DS2I_BLOCK_VARINT ? ds2i_host::CODEC_VARINT : ds2i_host::CODEC_INTERPOLATIVE;
-    EncStage st;
-    STAGE_OK(st.upload("ds2i_hip_encode_index", device, nlists, list_offsets, docs, freqs));
+// plan pass, layout, write pass of one codec over a staged collection; ms accumulates the hipEvent time of the two passes
+int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image, double& ms) {
     const uint64_t nblocks = st.nblocks;
     Events evs;
     for (auto& x : evs.e) HIP_OK(hipEventCreate(&x));
@@ -215,8 +213,122 @@ extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_do
     float ms_plan = 0.f, ms_write = 0.f;
     HIP_OK(hipEventElapsedTime(&ms_plan, e0, e1));
     HIP_OK(hipEventElapsedTime(&ms_write, e2, e3));
-    if (device_ms) *device_ms = (double)ms_plan + ms_write;
+    ms += (double)ms_plan + ms_write;
     return st.wrap(codec, num_docs, bytes, list_end, image);
+}
+
+// max_term_weight of every list of a staged collection (wand_kernels.hip); ms accumulates the kernel's hipEvent time
+int wand_max_staged(EncStage& st, const std::vector<float>& norm_lens, std::vector<float>& max_w, double& ms) {
+    static_assert(sizeof(float) == sizeof(unsigned int), "the list maxima travel as the bits of a float");
+    float* d_norm = nullptr;
+    unsigned int* d_max = nullptr;
+    HIP_OK(st.dev.alloc(&d_norm, 4 * norm_lens.size()));
+    HIP_OK(st.dev.alloc(&d_max, 4 * st.nlists));
+    HIP_OK(hipMemcpy(d_norm, norm_lens.data(), 4 * norm_lens.size(), hipMemcpyHostToDevice));
+    HIP_OK(hipMemset(d_max, 0, 4 * st.nlists));
+    Events evs;
+    HIP_OK(hipEventCreate(&evs.e[0]));
+    HIP_OK(hipEventCreate(&evs.e[1]));
+    HIP_OK(hipEventRecord(evs.e[0], nullptr));
+    if (st.nblocks)
+        HIP_OK(ds2i_launch_wand_list_max(st.a.docs, st.a.freqs, st.a.list_in, st.a.blk_list, st.a.list_blk0, st.a.nblocks, d_norm,
+                                         norm_lens.size(), d_max, st.grid, nullptr));
+    HIP_OK(hipEventRecord(evs.e[1], nullptr));
+    HIP_OK(hipEventSynchronize(evs.e[1]));
+    float t = 0.f;
+    HIP_OK(hipEventElapsedTime(&t, evs.e[0], evs.e[1]));
+    ms += t;
+    max_w.resize(st.nlists);
+    HIP_OK(hipMemcpy(max_w.data(), d_max, 4 * st.nlists, hipMemcpyDeviceToHost));
+    return DS2I_OK;
+}
+
+// The images of one staged collection: the index of `codec` (index_image non-null) and / or the wand_data image over
+// `norm_lens` (wand_image non-null), from ONE upload. Neither output is touched unless both succeed.
+int build_images(const char* who, int device, int codec, uint64_t num_docs, const std::vector<float>* norm_lens, uint64_t nlists,
+                 const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs, ds2i_blob** index_image,
+                 ds2i_blob** wand_image, double* device_ms) {
+    EncStage st;
+    STAGE_OK(st.upload(who, device, nlists, list_offsets, docs, freqs));
+    double ms = 0.0;
+    ds2i_blob* ib = nullptr;
+    if (index_image) STAGE_OK(encode_staged(st, codec, num_docs, &ib, ms));
+    std::unique_ptr<ds2i_blob> index_blob(ib), wand_blob;
+    if (wand_image) {
+        std::vector<float> max_w;
+        STAGE_OK(wand_max_staged(st, *norm_lens, max_w, ms));
+        wand_blob.reset(new ds2i_blob);
+        ds2i_host::wand_freeze(*norm_lens, max_w, wand_blob->data);
+    }
+    if (index_image) *index_image = index_blob.release();
+    if (wand_image) *wand_image = wand_blob.release();
+    if (device_ms) *device_ms = ms;
+    return DS2I_OK;
+}
+
+int block_codec_of(const char* who, int index_kind, int& codec) {
+    if (index_kind != DS2I_BLOCK_OPTPFOR && index_kind != DS2I_BLOCK_VARINT && index_kind != DS2I_BLOCK_INTERPOLATIVE)
+        return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": the GPU encoder writes block_optpfor, block_varint and block_interpolative indexes").c_str());
+    codec = index_kind == DS2I_BLOCK_OPTPFOR ? ds2i_host::CODEC_OPTPFOR
+            : index_kind == DS2I_BLOCK_VARINT ? ds2i_host::CODEC_VARINT : ds2i_host::CODEC_INTERPOLATIVE;
+    return DS2I_OK;
+}
+
+// what the wand kernel's gather relies on, checked before anything is staged: no empty list (the host builder's "List
+// must be nonempty", block_freq_index.hpp:31) and no doc-id past norm_lens
+int check_postings(const char* who, uint64_t num_docs, uint64_t nlists, const uint64_t* offs, const uint32_t* docs) {
+    for (uint64_t t = 0; t < nlists; ++t) {
+        if (offs[t + 1] <= offs[t]) return ds2i_set_error(DS2I_EINVAL, "List must be nonempty");
+        uint32_t top = 0;
+        for (uint64_t i = offs[t]; i < offs[t + 1]; ++i) top = std::max(top, docs[i]);
+        if (top >= num_docs) return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": doc id out of range").c_str());
+    }
+    return DS2I_OK;
+}
+} // namespace
+
+extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                                     const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms) {
+    if (!list_offsets || !docs || !freqs || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: null argument");
+    int codec = 0;
+    STAGE_OK(block_codec_of("ds2i_hip_encode_index", index_kind, codec));
+    try {
+        return build_images("ds2i_hip_encode_index", device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    }
+}
+
+extern "C" int ds2i_hip_build_wand(int device, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                                   const uint32_t* docs, const uint32_t* freqs, ds2i_blob** wand_image, double* device_ms) {
+    if (!doc_sizes || !num_docs || !list_offsets || !docs || !freqs || !wand_image)
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_build_wand: bad argument");
+    STAGE_OK(check_postings("ds2i_hip_build_wand", num_docs, nlists, list_offsets, docs));
+    try {
+        std::vector<float> norm_lens;
+        ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
+        return build_images("ds2i_hip_build_wand", device, 0, num_docs, &norm_lens, nlists, list_offsets, docs, freqs, nullptr, wand_image, device_ms);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    }
+}
+
+extern "C" int ds2i_hip_build_collection(int device, int index_kind, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists,
+                                         const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                                         ds2i_blob** index_image, ds2i_blob** wand_image, double* device_ms) {
+    if (!list_offsets || !docs || !freqs || !index_image || (wand_image && (!doc_sizes || !num_docs)))
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_build_collection: bad argument");
+    int codec = 0;
+    STAGE_OK(block_codec_of("ds2i_hip_build_collection", index_kind, codec));
+    STAGE_OK(check_postings("ds2i_hip_build_collection", num_docs, nlists, list_offsets, docs));
+    try {
+        std::vector<float> norm_lens;
+        if (wand_image) ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
+        return build_images("ds2i_hip_build_collection", device, codec, num_docs, &norm_lens, nlists, list_offsets, docs, freqs, index_image,
+                            wand_image, device_ms);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    }
 }
 
 // ---------------------------------------------------------------- block_mixed optimiser on the device
@@ -387,7 +499,6 @@ extern "C" int ds2i_hip_synth_encode(int device, const ds2i_synth_params* pp, in
         std::vector<uint32_t>().swap(sizes);
         const uint32_t V = p.num_terms;
         std::vector<std::vector<uint32_t>> ld(V), lf(V);
-        std::vector<float> max_w(V);
         std::atomic<uint32_t> next(0);
         std::string err;
         std::mutex err_mu;
@@ -406,7 +517,6 @@ extern "C" int ds2i_hip_synth_encode(int device, const ds2i_synth_params* pp, in
                     lf[t].resize(n);
                     ld[t].shrink_to_fit();
                     lf[t].shrink_to_fit();
-                    max_w[t] = list_max_weight(norm_lens.data(), n, ld[t].data(), lf[t].data());
                 }
             } catch (std::exception const& e) {
                 std::lock_guard<std::mutex> g(err_mu);
@@ -430,13 +540,9 @@ extern "C" int ds2i_hip_synth_encode(int device, const ds2i_synth_params* pp, in
         });
         if (generate_s) *generate_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         if (total_postings) *total_postings = offs[V];
-        int rc = ds2i_hip_encode_index(device, DS2I_BLOCK_OPTPFOR, p.num_docs, V, offs.data(), docs.data(), freqs.data(), index_image, device_ms);
-        if (rc) return rc;
-        if (wand_image) {
-            std::unique_ptr<ds2i_blob> wb(new ds2i_blob);
-            wand_freeze(norm_lens, max_w, wb->data);
-            *wand_image = wb.release();
-        }
+        // one staging for both images; max_term_weight comes from the wand kernel (the generator's doc-ids are < num_docs)
+        STAGE_OK(build_images("ds2i_hip_synth_encode", device, CODEC_OPTPFOR, p.num_docs, &norm_lens, V, offs.data(), docs.data(), freqs.data(),
+                              index_image, wand_image, device_ms));
     } catch (std::bad_alloc const&) {
         return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
     } catch (std::exception const& e) {

@@ -4,8 +4,9 @@
  * compiled here (create_freq_index.cpp:45-110, create_wand_data.cpp:8-29,
  * block_freq_index::builder block_freq_index.hpp:18-70). They produce the reference's on-disk
  * images (block_freq_index / wand_data) that ds2i_hip_index_open consumes. Nothing here is on
- * the timed query path and nothing here touches the GPU: the GPU forms of the encoder and of the
- * block_mixed optimiser (ds2i_hip_encode_index, ds2i_hip_hybrid_analyse / _freeze) are in ds2i_hip.h.
+ * the timed query path and nothing here touches the GPU: the GPU forms of the encoder, of the
+ * block_mixed optimiser and of the wand_data builder (ds2i_hip_encode_index, ds2i_hip_hybrid_analyse /
+ * _freeze, ds2i_hip_build_wand, ds2i_hip_build_collection) are in ds2i_hip.h.
  */
 #ifndef DS2I_BUILD_H
 #define DS2I_BUILD_H

@@ -259,6 +259,24 @@ typedef struct ds2i_blob ds2i_blob;
 int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                           const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms);
 
+/* wand_data on the GPU (build side; create_wand_data.cpp:8-29, wand_data.hpp:20-52): the image ds2i_wand_create(doc_sizes,
+ * num_docs) / ds2i_wand_add_list x nlists / ds2i_wand_freeze of ds2i_build.h return for the same input, byte for byte.
+ * They live here because nothing in ds2i_build.h touches the GPU. Lists in the CSR form of ds2i_hip_encode_index;
+ * doc_sizes holds num_docs (> 0) document lengths. norm_lens are computed on the host exactly as the host builder
+ * computes them; max_term_weight[t] = max over list t's postings of bm25::doc_term_weight(freq, norm_len[doc]) comes from
+ * a HIP kernel, one wavefront per 128-posting block, with the query kernels' own scoring function.
+ * An empty list ("List must be nonempty") and a doc-id >= num_docs (checked on the host, before anything is launched)
+ * are DS2I_EINVAL. device_ms (may be NULL) receives the hipEvent time of the kernel. */
+int ds2i_hip_build_wand(int device, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                        const uint32_t* docs, const uint32_t* freqs, ds2i_blob** wand_image, double* device_ms);
+/* Both images of a collection from ONE staging of its postings: everything ds2i_hip_index_open needs. index_image is what
+ * ds2i_hip_encode_index(index_kind, ...) returns (same kinds; DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL),
+ * wand_image what ds2i_hip_build_wand returns. wand_image may be NULL (doc_sizes may then be NULL too); on an error
+ * neither output is written. device_ms (may be NULL): the hipEvent time of the encoder's two passes plus the wand kernel. */
+int ds2i_hip_build_collection(int device, int index_kind, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists,
+                              const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                              ds2i_blob** index_image, ds2i_blob** wand_image, double* device_ms);
+
 /* The block_mixed optimiser of ds2i_build.h (ds2i_hybrid_*) with its build side on the GPU. They
  * live here because nothing in ds2i_build.h touches the GPU; the handle is the one ds2i_hybrid_create returns, filled
  * with ds2i_hybrid_add_posting_list. A builder that holds virtual lists (ds2i_synth_build_hybrid) is DS2I_EINVAL.
@@ -274,7 +292,8 @@ int ds2i_hip_hybrid_freeze(struct ds2i_hybrid* h, int device, uint64_t budget_by
                            uint64_t* space, double* model_time, uint64_t type_counts[6], double* device_ms);
 
 /* The synthetic collection of ds2i_build.h generated on `threads` host threads (<= 0: all) and encoded on the GPU;
- * the same two images as ds2i_synth_build(p, DS2I_BLOCK_OPTPFOR, ...), byte for byte. wand_image, total_postings,
+ * the same two images as ds2i_synth_build(p, DS2I_BLOCK_OPTPFOR, ...), byte for byte (one staging, as
+ * ds2i_hip_build_collection: the maximum term weights come from the wand kernel). wand_image, total_postings,
  * generate_s (host seconds spent generating the lists) and device_ms may be NULL. */
 struct ds2i_synth_params;
 int ds2i_hip_synth_encode(int device, const struct ds2i_synth_params* p, int threads, ds2i_blob** index_image,
