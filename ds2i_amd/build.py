@@ -11,19 +11,22 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libds2i_hip.so")
 ARCH = "gfx950"
 
-# ranked_stream.hip holds the pipelined ranked_and kernels of the benchmark configuration;
-# kernels.hip is compiled six times: once per list-count class (-DDS2I_TU_TMAX=n: the query kernels of that class; 0 = the
-# long class) and once for everything else; encode_kernels.hip holds the index encoder, wand_kernels.hip the wand_data builder; all units are built in parallel
-DEVICE_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [("kernels.hip", "kernels.hip", []), ("ranked_stream.hip", "ranked_stream.hip", []), ("ranked_stream.hip", "ranked_stream_bigk.hip", ["-DDS2I_RS_BIGK_TU"]), ("ranked_stream_mixed.hip", "ranked_stream_mixed.hip", []), ("freq_stream.hip", "freq_stream.hip", []), ("union_stream.hip", "union_stream.hip", []), ("union_stream.hip", "union_stream_bigk.hip", ["-DDS2I_US_BIGK_TU"]), ("encode_kernels.hip", "encode_kernels.hip", []), ("wand_kernels.hip", "wand_kernels.hip", [])]
-# DS2I_OP_TOPK_DOCS: the same sources once more with -DDS2I_DOCS_TU -- the ranked kernels with (score, doc-id) heaps, named *_docs
-# (device_enum.hpp); each docs unit mirrors a scores-only unit above, so the build stays as parallel as before
-DOCS_UNITS = [("kernels.hip", "kernels_t%d_docs.hip" % t, ["-DDS2I_DOCS_TU", "-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [
-    ("ranked_stream.hip", "ranked_stream_docs.hip", ["-DDS2I_DOCS_TU"]),
-    ("ranked_stream.hip", "ranked_stream_bigk_docs.hip", ["-DDS2I_DOCS_TU", "-DDS2I_RS_BIGK_TU"]),
-    ("ranked_stream_mixed.hip", "ranked_stream_mixed_docs.hip", ["-DDS2I_DOCS_TU"]),
-    ("union_stream.hip", "union_stream_docs.hip", ["-DDS2I_DOCS_TU"]),
-    ("union_stream.hip", "union_stream_bigk_docs.hip", ["-DDS2I_DOCS_TU", "-DDS2I_US_BIGK_TU"])]
-DEVICE_UNITS += DOCS_UNITS
+# (source, object name, defines) of every device unit; all are built in parallel.
+# kernels.hip is compiled six times: once per list-count class (-DDS2I_TU_TMAX=n: the query kernels of that class; 0 = the long
+# class) and once for everything else; ranked_stream.hip holds the pipelined ranked_and kernels of the benchmark configuration,
+# union_stream.hip those of wand / maxscore / ranked_or (each once more for k > 64: _bigk); encode_kernels.hip holds the index
+# encoder, wand_kernels.hip the wand_data builder.
+RANKED_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [
+    ("ranked_stream.hip", "ranked_stream.hip", []),
+    ("ranked_stream.hip", "ranked_stream_bigk.hip", ["-DDS2I_RS_BIGK_TU"]),
+    ("ranked_stream_mixed.hip", "ranked_stream_mixed.hip", []),
+    ("union_stream.hip", "union_stream.hip", []),
+    ("union_stream.hip", "union_stream_bigk.hip", ["-DDS2I_US_BIGK_TU"])]
+# DS2I_OP_TOPK_DOCS: every unit that holds ranked kernels once more with -DDS2I_DOCS_TU -- the same sources with (score, doc-id)
+# heaps, kernels and launchers named *_docs (device_enum.hpp, DS2I_KN); the build stays as parallel as before
+DOCS_UNITS = [(src, name.replace(".hip", "_docs.hip"), ["-DDS2I_DOCS_TU"] + defs) for src, name, defs in RANKED_UNITS]
+DEVICE_UNITS = RANKED_UNITS + [("kernels.hip", "kernels.hip", []), ("freq_stream.hip", "freq_stream.hip", []),
+                               ("encode_kernels.hip", "encode_kernels.hip", []), ("wand_kernels.hip", "wand_kernels.hip", [])] + DOCS_UNITS
 HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "capi_build.cpp", "capi_encode.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
@@ -78,7 +81,9 @@ def build(verbose=False, force=False):
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.check_call(cmd)
 
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 4)) as pool:
+        # (os.cpu_count() is the whole machine, which a shared host does not give one build)
+        workers = min(len(jobs), os.cpu_count() or 4, int(os.environ.get("MAX_JOBS") or 16))
+        with ThreadPoolExecutor(max_workers=workers) as pool:
             list(pool.map(run, jobs))
     if force or _newer(lib, objs):
         cmd = [hipcc, "--offload-arch=" + ARCH, "-shared", "-fPIC", "-o", lib] + objs + ["-lpthread"]

@@ -1,4 +1,5 @@
-// Plain structs shared by the HIP kernels (kernels.hip) and the host C-ABI (capi.cpp).
+// Plain structs shared by the HIP kernels (*.hip) and the host C-ABI (capi*.cpp): every struct that crosses that boundary is
+// defined here, once. The launchers that take them are declared in launchers.hpp.
 #pragma once
 #include <stdint.h>
 
@@ -280,5 +281,54 @@ struct DecodeArgs {
     const uint32_t* xovf;
     const uint32_t* tails;
 };
+
+// wand / maxscore / ranked_or of a ONE-term query are exactly its ranked_and result: copied from the seed pass (k_copy_seed)
+struct CopySeedArgs {
+    const uint32_t* queries;
+    uint32_t n, k;
+    const float* seed_topk;
+    const uint32_t* seed_len;
+    const unsigned long long* seed_count;
+    float* out_topk;
+    uint32_t* out_len;
+    unsigned long long* out_count;
+};
+// ... with the doc-ids (DS2I_OP_TOPK_DOCS, k_copy_seed_docs: the seed batch ran the docs kernels too)
+struct CopySeedDocsArgs {
+    CopySeedArgs s;
+    const uint32_t* seed_docs;
+    uint32_t* out_docs;
+};
+
+// the index encoder and the block_mixed optimiser's plan pass (encode_kernels.hip) over a collection staged in CSR form
+struct EncArgs {
+    const uint32_t* docs;      // postings of all lists, concatenated
+    const uint32_t* freqs;
+    const uint64_t* list_in;   // nlists + 1 posting offsets
+    const uint32_t* blk_list;  // per block: its list
+    const uint32_t* list_blk0; // per list: its first block (global numbering)
+    uint32_t nblocks;
+    uint8_t* bsel;             // 2 per block: chosen b of the docs / freqs part (full blocks)
+    uint32_t* psize;           // 2 per block: bytes of the docs / freqs part
+    uint32_t* bmax;            // per block: last doc-id
+    const uint64_t* blk_out;   // write pass: byte offset of the block's bytes in `out` (nblocks + 1 entries)
+    const uint64_t* list_out;  // write pass: byte offset of the list (its vbyte(n)) in `out`
+    uint8_t* out;
+    const uint8_t* choice;     // block_mixed write pass: 2 per part (4 per block): mixed type, OptPFor b
+    void* rec;                 // optimiser plan: 2 HybRec per block (docs part, freqs part)
+};
+
+// What the candidates of one 128-value part cost, as integers -- sizes and counts only: the record k_hybrid_plan fills and the
+// optimiser reads (host_hybrid.hpp, where hybrid_part_measure fills the same record on the host)
+struct HybRec {
+    uint16_t pfor_words[17]; // payload words of OptPFor at OPTPFOR_LOGS[i] (packed values + Simple16 exceptions), 0xFFFF: not a candidate
+    uint8_t nexc[17];        // exceptions at that b
+    uint8_t interp_ok;       // the values sum to less than 2^32 - 1 (interpolative codes u32 prefix sums)
+    uint16_t varint_bytes;
+    uint16_t interp_bytes;   // full blocks: valid if interp_ok; partial blocks: the only field that is read
+    uint16_t live;           // interpolative tree nodes whose range is not degenerate (interp_live_nodes)
+    uint16_t pad[3];
+};
+static_assert(sizeof(HybRec) == 64, "HybRec is a 64-byte device record");
 
 } // namespace ds2i_dev

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "capi_internal.hpp"
+#include "launchers.hpp"
 #include "knobs.hpp"
 #include "../../include/ds2i_build.h"
 #include "host_index.hpp"
@@ -28,17 +29,6 @@ using ds2i_dev::MergeArgs;
 using ds2i_dev::Unit;
 using ds2i_dev::QTerm;
 using ds2i_dev::Stats;
-
-extern "C" {
-hipError_t ds2i_launch_decode_list(const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_decode_list_side(const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_block_max_weights(const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_list_top_bmw(const float* bmw, const void* lists, uint32_t nlists, float* out, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_build_side_tables(const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_calib_read(const uint32_t* base, unsigned long long ndw, uint32_t* out, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_selftest(const uint32_t* in, uint32_t* out, unsigned blocks, hipStream_t s);
-hipError_t ds2i_launch_selftest_bm25(const uint32_t* freqs, const float* norm_lens, float* out, uint32_t n, hipStream_t s);
-}
 
 // ------------------------------------------------------------------ errors
 namespace {
@@ -144,7 +134,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
     a.list_bmw = d_lmax;
     a.rmw = nullptr;
     const unsigned grid = (unsigned)std::min<size_t>(items.size(), (size_t)x->num_cus * 64);
-    HIP_OK(ds2i_launch_block_max_weights(&a, grid, x->stream[0]));
+    HIP_OK(ds2i_launch_block_max_weights(a, grid, x->stream[0]));
     HIP_OK(hipStreamSynchronize(x->stream[0]));
     x->list_bmw.assign(V, 0.f);
     HIP_OK(hipMemcpy(x->list_bmw.data(), d_lmax, 4 * V, hipMemcpyDeviceToHost));
@@ -235,7 +225,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
     a.rmw_level = 0;
     a.bitmaps = x->knobs.no_bitmaps ? 0u : 1u;
     x->has_bitmaps = a.bitmaps != 0;
-    HIP_OK(ds2i_launch_block_max_weights(&a, grid, x->stream[0]));
+    HIP_OK(ds2i_launch_block_max_weights(a, grid, x->stream[0]));
     for (uint32_t lvl = 1; lvl <= 2; ++lvl) { // level lvl + 1 = maxima of 64 entries of level lvl, 4096 entries per item
         items.clear();
         for (uint64_t t = 0; t < V; ++t) {
@@ -249,7 +239,7 @@ int build_block_max_weights(ds2i_hip_index* x) {
         a.items = d_it;
         a.nitems = (uint32_t)items.size();
         a.rmw_level = lvl;
-        HIP_OK(ds2i_launch_block_max_weights(&a, (unsigned)std::min<size_t>(items.size(), (size_t)x->num_cus * 64), x->stream[0]));
+        HIP_OK(ds2i_launch_block_max_weights(a, (unsigned)std::min<size_t>(items.size(), (size_t)x->num_cus * 64), x->stream[0]));
     }
     HIP_OK(hipStreamSynchronize(x->stream[0]));
     x->extra_bytes += bytes + (x->d_rmh ? bytes : 0);
@@ -401,7 +391,7 @@ int build_side_tables(ds2i_hip_index* x) {
         a.xovf_cursor = d_cursor;
         a.tails = x->d_tails;
         a.bad = (unsigned int*)(d_cursor + 1);
-        HIP_OK(ds2i_launch_build_side_tables(&a, (unsigned)std::min<size_t>(items.size(), (size_t)x->num_cus * 64), x->stream[0]));
+        HIP_OK(ds2i_launch_build_side_tables(a, (unsigned)std::min<size_t>(items.size(), (size_t)x->num_cus * 64), x->stream[0]));
         HIP_OK(hipStreamSynchronize(x->stream[0]));
         unsigned long long res[2] = {0, 0};
         HIP_OK(hipMemcpy(res, d_cursor, 16, hipMemcpyDeviceToHost));
@@ -554,7 +544,7 @@ static int index_open_transcoded(int device, int kind, const void* index_image, 
                 a.num_docs = (uint32_t)raw->num_docs;
                 a.out_docs = d_docs + fill;
                 a.out_freqs = d_freqs + fill;
-                HIP_OK(ds2i_launch_decode_list(&a, (unsigned)std::min<uint64_t>(raw->list_nb[t1], uint64_t(raw->num_cus) * 16), raw->stream[0]));
+                HIP_OK(ds2i_launch_decode_list(a, (unsigned)std::min<uint64_t>(raw->list_nb[t1], uint64_t(raw->num_cus) * 16), raw->stream[0]));
                 fill += raw->list_n[t1];
                 ++t1;
             }
@@ -868,7 +858,7 @@ int ds2i_hip_decode_list(ds2i_hip_index* idx, uint32_t term, uint32_t* docs, uin
     unsigned grid = (unsigned)std::min<uint64_t>(nb, uint64_t(idx->num_cus) * 16);
     // block_optpfor with side tables: through the stream kernels' decoder (DS2I_DECODE_GENERAL=1: the general decoders)
     const bool side = idx->side_tables() && !idx->knobs.decode_general;
-    hipError_t e = side ? ds2i_launch_decode_list_side(&a, grid, idx->stream[0]) : ds2i_launch_decode_list(&a, grid, idx->stream[0]);
+    hipError_t e = side ? ds2i_launch_decode_list_side(a, grid, idx->stream[0]) : ds2i_launch_decode_list(a, grid, idx->stream[0]);
     if (e == hipSuccess) e = hipStreamSynchronize(idx->stream[0]);
     if (e == hipSuccess) e = hipMemcpy(docs, d_docs, 4 * len, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(freqs, d_freqs, 4 * len, hipMemcpyDeviceToHost);

@@ -27,40 +27,13 @@
 #include "capi_internal.hpp"
 #include "knobs.hpp"
 #include "host_index.hpp"
+#include "launchers.hpp"
 
 using ds2i_dev::BatchArgs;
 using ds2i_dev::MergeArgs;
 using ds2i_dev::QTerm;
 using ds2i_dev::Stats;
 using ds2i_dev::Unit;
-
-extern "C" {
-hipError_t ds2i_launch_batch(int op, int tmax_class, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_ranked_stream(int nt, const void* args, unsigned grid, hipStream_t s); // ranked_stream.hip
-hipError_t ds2i_launch_ranked_stream_bigk(int cap, const void* args, unsigned grid, hipStream_t s); // ranked_stream.hip compiled with -DDS2I_RS_BIGK_TU (k > 64)
-hipError_t ds2i_launch_freq_stream(const void* args, unsigned longest, unsigned nqterms, hipStream_t s); // freq_stream.hip
-hipError_t ds2i_launch_and_stream(const void* args, int with_freqs, unsigned longest, unsigned nterms, hipStream_t s); // freq_stream.hip
-hipError_t ds2i_launch_and_rstream(int cap, int with_freqs, const void* args, unsigned grid, hipStream_t s);       // ranked_stream.hip (AND = true)
-hipError_t ds2i_launch_union_stream(int nt, const void* args, unsigned grid, hipStream_t s);     // union_stream.hip (wand / maxscore / ranked_or)
-hipError_t ds2i_launch_union_stream_bigk(int cap, const void* args, unsigned grid, hipStream_t s); // union_stream.hip compiled with -DDS2I_US_BIGK_TU (k > 64)
-hipError_t ds2i_launch_ranked_stream_mixed(int nt, const void* args, unsigned grid, hipStream_t s); // ranked_stream_mixed.hip
-hipError_t ds2i_launch_merge(const void* args, unsigned grid, hipStream_t s);
-// DS2I_OP_TOPK_DOCS: the *_docs instantiations (the *_docs units of build.py; same arguments, BatchArgs / MergeArgs docs fields set)
-hipError_t ds2i_launch_batch_docs(int op, int tmax_class, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_ranked_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_ranked_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_ranked_stream_mixed_docs(int nt, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_union_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_union_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_merge_docs(const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_copy_seed_docs(const uint32_t* queries, uint32_t n, uint32_t k, const float* seed_topk, const uint32_t* seed_docs,
-                                      const uint32_t* seed_len, const unsigned long long* seed_count, float* out_topk, uint32_t* out_docs,
-                                      uint32_t* out_len, unsigned long long* out_count, hipStream_t s);
-hipError_t ds2i_launch_copy_seed(const uint32_t* queries, uint32_t n, uint32_t k, const float* seed_topk, const uint32_t* seed_len,
-                                 const unsigned long long* seed_count, float* out_topk, uint32_t* out_len,
-                                 unsigned long long* out_count, hipStream_t s);
-uint32_t ds2i_meta_words(void); // kernels.hip: dwords of enumerator state per list slot (M_WORDS)
-}
 
 // one contiguous range of a batch's queries, planned by one thread (plan_queries)
 struct PlanChunk {
@@ -155,7 +128,7 @@ void ds2i_plan_pool_run(unsigned n, const std::function<void(unsigned)>& f) {
 } // namespace
 
 // The kernel a launch group runs (ds2i_hip_batch::SubLaunch), chosen when the plan forms the group (form_groups): the class kernel of the
-// operator (ds2i_launch_batch) or one of the stream kernels declared above (_bigk: their TopKBig instantiations, k > 64)
+// operator (ds2i_launch_batch) or one of the stream kernels (launchers.hpp; _bigk: their TopKBig instantiations, k > 64)
 enum class GroupKernel : uint8_t { cls, ranked_stream, ranked_stream_bigk, ranked_stream_mixed, and_rstream, union_stream, union_stream_bigk };
 
 // Which kernel families answer a batch: decided once per plan (plan_route), before any query is planned, from the index (its tables
@@ -1086,28 +1059,20 @@ GroupKernel launched_kernel(const ds2i_hip_batch* b, const ds2i_hip_batch::SubLa
 // one launch group's kernel (a.order / a.urec / a.nslice / a.dyn_lists already point at the group)
 hipError_t launch_group(const ds2i_hip_batch* b, GroupKernel kernel, int c, const BatchArgs& a, hipStream_t s) {
     const int lists = (int)a.dyn_lists;
-    if (b->route.docs) {
-        switch (kernel) {
-        case GroupKernel::ranked_stream: return ds2i_launch_ranked_stream_docs(lists, &a, a.nslice, s);
-        case GroupKernel::ranked_stream_bigk: return ds2i_launch_ranked_stream_bigk_docs(lists, &a, a.nslice, s);
-        case GroupKernel::ranked_stream_mixed: return ds2i_launch_ranked_stream_mixed_docs(lists, &a, a.nslice, s);
-        case GroupKernel::union_stream: return ds2i_launch_union_stream_docs(lists, &a, a.nslice, s);
-        case GroupKernel::union_stream_bigk: return ds2i_launch_union_stream_bigk_docs(lists, &a, a.nslice, s);
-        case GroupKernel::and_rstream: return hipErrorInvalidValue; // (plan_route: the flag is for ranked operators)
-        case GroupKernel::cls: break;
-        }
-        return ds2i_launch_batch_docs(b->op & (0xFF | DS2I_OP_REFERENCE_ORDER), c, &a, a.nslice, s);
-    }
+    const bool docs = b->route.docs; // DS2I_OP_TOPK_DOCS: the *_docs build of the same launcher
     switch (kernel) {
-    case GroupKernel::ranked_stream: return ds2i_launch_ranked_stream(lists, &a, a.nslice, s);
-    case GroupKernel::ranked_stream_bigk: return ds2i_launch_ranked_stream_bigk(lists, &a, a.nslice, s);
-    case GroupKernel::ranked_stream_mixed: return ds2i_launch_ranked_stream_mixed(lists, &a, a.nslice, s);
-    case GroupKernel::and_rstream: return ds2i_launch_and_rstream(lists, (b->op & 0xFF) == DS2I_OP_AND_FREQ ? 1 : 0, &a, a.nslice, s);
-    case GroupKernel::union_stream: return ds2i_launch_union_stream(lists, &a, a.nslice, s);
-    case GroupKernel::union_stream_bigk: return ds2i_launch_union_stream_bigk(lists, &a, a.nslice, s);
+    case GroupKernel::ranked_stream: return (docs ? ds2i_launch_ranked_stream_docs : ds2i_launch_ranked_stream)(lists, a, a.nslice, s);
+    case GroupKernel::ranked_stream_bigk: return (docs ? ds2i_launch_ranked_stream_bigk_docs : ds2i_launch_ranked_stream_bigk)(lists, a, a.nslice, s);
+    case GroupKernel::ranked_stream_mixed: return (docs ? ds2i_launch_ranked_stream_mixed_docs : ds2i_launch_ranked_stream_mixed)(lists, a, a.nslice, s);
+    case GroupKernel::union_stream: return (docs ? ds2i_launch_union_stream_docs : ds2i_launch_union_stream)(lists, a, a.nslice, s);
+    case GroupKernel::union_stream_bigk: return (docs ? ds2i_launch_union_stream_bigk_docs : ds2i_launch_union_stream_bigk)(lists, a, a.nslice, s);
+    case GroupKernel::and_rstream:
+        if (docs) return hipErrorInvalidValue; // (plan_route: the flag is for ranked operators)
+        return ds2i_launch_and_rstream(lists, (b->op & 0xFF) == DS2I_OP_AND_FREQ ? 1 : 0, a, a.nslice, s);
     case GroupKernel::cls: break;
     }
-    return ds2i_launch_batch(b->route.freq_stream ? (int)DS2I_OP_OR : (b->op & (0xFF | DS2I_OP_REFERENCE_ORDER)), c, &a, a.nslice, s);
+    const int op = !docs && b->route.freq_stream ? (int)DS2I_OP_OR : (b->op & (0xFF | DS2I_OP_REFERENCE_ORDER));
+    return (docs ? ds2i_launch_batch_docs : ds2i_launch_batch)(op, c, a, a.nslice, s);
 }
 
 // and / and_freq of the all-dense queries: list streams beside the class kernels (nobody else writes these queries' results);
@@ -1131,7 +1096,7 @@ int launch_list_streams(ds2i_hip_batch* b, hipStream_t* cstreams, hipStream_t sm
         g.out_freq_sum = with_freqs ? b->d_out.at<unsigned long long>(b->o_freq_sum) : nullptr;
         for (size_t t0 = 0; t0 < b->sterms.size(); t0 += 32768) { // (grid.y is limited to 65535)
             g.terms = b->d_up.at<ds2i_dev::StreamTerm>(b->o_sterms) + t0;
-            HIP_OK(ds2i_launch_and_stream(&g, with_freqs ? 1 : 0, b->sterm_longest, (unsigned)std::min<size_t>(32768, b->sterms.size() - t0), sf));
+            HIP_OK(ds2i_launch_and_stream(g, with_freqs ? 1 : 0, b->sterm_longest, (unsigned)std::min<size_t>(32768, b->sterms.size() - t0), sf));
         }
     } else {
         ds2i_dev::FreqArgs f{};
@@ -1149,7 +1114,7 @@ int launch_list_streams(ds2i_hip_batch* b, hipStream_t* cstreams, hipStream_t sm
             ds2i_dev::FreqArgs g = f;
             g.qterms += t0;
             g.qterm_q += t0;
-            HIP_OK(ds2i_launch_freq_stream(&g, longest, (unsigned)std::min<size_t>(32768, b->qterms.size() - t0), sf));
+            HIP_OK(ds2i_launch_freq_stream(g, longest, (unsigned)std::min<size_t>(32768, b->qterms.size() - t0), sf));
         }
     }
     if (own) {
@@ -1348,22 +1313,18 @@ int launch_batch(ds2i_hip_batch* b) {
         if (b->route.docs) {
             m.unit_topk_docs = b->d_scr.at<uint32_t>(b->o_unit_topk_docs);
             m.out_topk_docs = b->d_out.at<uint32_t>(b->o_topk_docs);
-            HIP_OK(ds2i_launch_merge_docs(&m, std::min<unsigned>(b->nsplit, 4096u), sm));
-        } else {
-            HIP_OK(ds2i_launch_merge(&m, std::min<unsigned>(b->nsplit, 4096u), sm));
         }
+        HIP_OK((b->route.docs ? ds2i_launch_merge_docs : ds2i_launch_merge)(m, std::min<unsigned>(b->nsplit, 4096u), sm));
     }
-    if (b->use_seed && b->nsingle && b->route.docs)
-        HIP_OK(ds2i_launch_copy_seed_docs(b->d_up.at<uint32_t>(b->o_single), b->nsingle, b->k, b->seed->d_out.at<float>(b->seed->o_topk),
-                                          b->seed->d_out.at<uint32_t>(b->seed->o_topk_docs), b->seed->d_out.at<uint32_t>(b->seed->o_topk_len),
-                                          b->seed->d_out.at<unsigned long long>(b->seed->o_count), b->d_out.at<float>(b->o_topk),
-                                          b->d_out.at<uint32_t>(b->o_topk_docs), b->d_out.at<uint32_t>(b->o_topk_len),
-                                          b->d_out.at<unsigned long long>(b->o_count), sm));
-    else if (b->use_seed && b->nsingle)
-        HIP_OK(ds2i_launch_copy_seed(b->d_up.at<uint32_t>(b->o_single), b->nsingle, b->k, b->seed->d_out.at<float>(b->seed->o_topk),
-                                     b->seed->d_out.at<uint32_t>(b->seed->o_topk_len),
-                                     b->seed->d_out.at<unsigned long long>(b->seed->o_count), b->d_out.at<float>(b->o_topk),
-                                     b->d_out.at<uint32_t>(b->o_topk_len), b->d_out.at<unsigned long long>(b->o_count), sm));
+    if (b->use_seed && b->nsingle) {
+        const ds2i_dev::CopySeedArgs cs{b->d_up.at<uint32_t>(b->o_single), b->nsingle, b->k, b->seed->d_out.at<float>(b->seed->o_topk),
+                                        b->seed->d_out.at<uint32_t>(b->seed->o_topk_len), b->seed->d_out.at<unsigned long long>(b->seed->o_count),
+                                        b->d_out.at<float>(b->o_topk), b->d_out.at<uint32_t>(b->o_topk_len), b->d_out.at<unsigned long long>(b->o_count)};
+        if (b->route.docs)
+            HIP_OK(ds2i_launch_copy_seed_docs(ds2i_dev::CopySeedDocsArgs{cs, b->seed->d_out.at<uint32_t>(b->seed->o_topk_docs), b->d_out.at<uint32_t>(b->o_topk_docs)}, sm));
+        else
+            HIP_OK(ds2i_launch_copy_seed(cs, sm));
+    }
     HIP_OK(hipMemcpyAsync(b->h_out.p, b->d_out.p, b->out_bytes, hipMemcpyDeviceToHost, sm));
     HIP_OK(hipEventRecord(b->ev_done, sm));
     b->launched = true;

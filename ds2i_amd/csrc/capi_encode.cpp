@@ -19,34 +19,9 @@
 #include "capi_hybrid.hpp"
 #include "capi_internal.hpp"
 #include "host_index.hpp"
-
-extern "C" {
-size_t ds2i_sizeof_enc_args();
-size_t ds2i_sizeof_hyb_rec();
-hipError_t ds2i_launch_encode(int mode, int write, const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_hybrid_plan(const void* args, unsigned grid, hipStream_t s);
-hipError_t ds2i_launch_wand_list_max(const uint32_t* docs, const uint32_t* freqs, const uint64_t* list_in, const uint32_t* blk_list,
-                                     const uint32_t* list_blk0, uint32_t nblocks, const float* norm_lens, uint64_t num_docs,
-                                     unsigned int* list_max, unsigned max_groups, hipStream_t s);
-}
+#include "launchers.hpp"
 
 namespace {
-struct EncArgsHost { // mirrors EncArgs in encode_kernels.hip
-    const uint32_t* docs;
-    const uint32_t* freqs;
-    const uint64_t* list_in;
-    const uint32_t* blk_list;
-    const uint32_t* list_blk0;
-    uint32_t nblocks;
-    uint8_t* bsel;
-    uint32_t* psize;
-    uint32_t* bmax;
-    const uint64_t* blk_out;
-    const uint64_t* list_out;
-    uint8_t* out;
-    const uint8_t* choice;
-    void* rec;
-};
 struct DevFree {
     std::vector<void*> p;
     ~DevFree() { for (void* x : p) if (x) (void)hipFree(x); }
@@ -73,7 +48,7 @@ int check_device(const char* who, int device) {
 // A collection in CSR form staged on the device, with the block tables both kernels walk
 struct EncStage {
     DevFree dev;
-    EncArgsHost a{};
+    ds2i_dev::EncArgs a{};
     uint64_t nlists = 0, nblocks = 0;
     const uint64_t* list_offsets = nullptr;
     std::vector<uint32_t> list_blk0;
@@ -82,8 +57,6 @@ struct EncStage {
     uint64_t* d_list_out = nullptr;
 
     int upload(const char* who, int device, uint64_t nl, const uint64_t* offs, const uint32_t* docs, const uint32_t* freqs) {
-        if (sizeof(EncArgsHost) != ds2i_sizeof_enc_args() || sizeof(ds2i_host::hybrid_part_rec) != ds2i_sizeof_hyb_rec())
-            return ds2i_set_error(DS2I_EINVAL, "EncArgs layout mismatch");
         const int rc = check_device(who, device);
         if (rc != DS2I_OK) return rc;
         nlists = nl;
@@ -198,7 +171,7 @@ int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image,
     const hipEvent_t e0 = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
     // ---- plan pass
     HIP_OK(hipEventRecord(e0, nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 0, &st.a, st.grid, nullptr));
+    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 0, st.a, st.grid, nullptr));
     HIP_OK(hipEventRecord(e1, nullptr));
     std::vector<uint32_t> psize(2 * nblocks);
     HIP_OK(hipMemcpy(psize.data(), st.a.psize, 8 * nblocks, hipMemcpyDeviceToHost));
@@ -207,7 +180,7 @@ int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image,
     STAGE_OK(st.lay_out(psize, list_end, bytes));
     // ---- write pass
     HIP_OK(hipEventRecord(e2, nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 1, &st.a, st.grid, nullptr));
+    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 1, st.a, st.grid, nullptr));
     HIP_OK(hipEventRecord(e3, nullptr));
     HIP_OK(hipEventSynchronize(e3));
     float ms_plan = 0.f, ms_write = 0.f;
@@ -357,7 +330,7 @@ int hybrid_analyse_on(EncStage& st, ds2i_host::hybrid_index_builder& hb, double&
     HIP_OK(hipEventCreate(&evs.e[0]));
     HIP_OK(hipEventCreate(&evs.e[1]));
     HIP_OK(hipEventRecord(evs.e[0], nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_hybrid_plan(&st.a, st.grid, nullptr));
+    if (nblocks) HIP_OK(ds2i_launch_hybrid_plan(st.a, st.grid, nullptr));
     HIP_OK(hipEventRecord(evs.e[1], nullptr));
     HIP_OK(hipEventSynchronize(evs.e[1]));
     float t = 0.f;
@@ -446,7 +419,7 @@ extern "C" int ds2i_hip_hybrid_freeze(ds2i_hybrid* h, int device, uint64_t budge
         HIP_OK(hipEventCreate(&evs.e[0]));
         HIP_OK(hipEventCreate(&evs.e[1]));
         HIP_OK(hipEventRecord(evs.e[0], nullptr));
-        if (nblocks) HIP_OK(ds2i_launch_encode(ds2i_host::CODEC_MIXED, 1, &st.a, st.grid, nullptr));
+        if (nblocks) HIP_OK(ds2i_launch_encode(ds2i_host::CODEC_MIXED, 1, st.a, st.grid, nullptr));
         HIP_OK(hipEventRecord(evs.e[1], nullptr));
         HIP_OK(hipEventSynchronize(evs.e[1]));
         float tw = 0.f;

@@ -16,43 +16,16 @@
 #include <hip/hip_runtime.h>
 
 #include "device_codecs.hpp"
+#include "dispatch.hpp"
+#include "launchers.hpp"
 
 using namespace ds2i_dev;
 
 namespace {
 
-struct EncArgs {
-    const uint32_t* docs;      // postings of all lists, concatenated
-    const uint32_t* freqs;
-    const uint64_t* list_in;   // nlists + 1 posting offsets
-    const uint32_t* blk_list;  // per block: its list
-    const uint32_t* list_blk0; // per list: its first block (global numbering)
-    uint32_t nblocks;
-    uint8_t* bsel;             // 2 per block: chosen b of the docs / freqs part (full blocks)
-    uint32_t* psize;           // 2 per block: bytes of the docs / freqs part
-    uint32_t* bmax;            // per block: last doc-id
-    const uint64_t* blk_out;   // write pass: byte offset of the block's bytes in `out` (nblocks + 1 entries)
-    const uint64_t* list_out;  // write pass: byte offset of the list (its vbyte(n)) in `out`
-    uint8_t* out;
-    const uint8_t* choice;     // block_mixed write pass: 2 per part (4 per block): mixed type, OptPFor b
-    void* rec;                 // optimiser plan: 2 HybRec per block (docs part, freqs part)
-};
-
 // which encoder the full blocks of k_encode take (host_encode.hpp codec_kind; QMX has no encoder here)
 enum : int { ENC_OPTPFOR = 0, ENC_VARINT = 1, ENC_INTERP = 2, ENC_MIXED = 4 };
 enum : uint32_t { MIX_PFOR = 0, MIX_VARINT = 1, MIX_INTERP = 2 };
-
-// One part as the optimiser sees it (mirrors hybrid_part_rec in host_hybrid.hpp): sizes and counts only
-struct HybRec {
-    uint16_t pfor_words[17]; // payload words of OptPFor at ENC_LOGS[i] (packed values + Simple16 exceptions), 0xFFFF: not a candidate
-    uint8_t nexc[17];        // exceptions at that b
-    uint8_t interp_ok;       // the values sum to less than 2^32 - 1: interpolative can code the part
-    uint16_t varint_bytes;
-    uint16_t interp_bytes;   // full blocks: valid if interp_ok; partial blocks: the only field that is read
-    uint16_t live;           // interpolative tree nodes whose range is not degenerate
-    uint16_t pad[3];
-};
-static_assert(sizeof(HybRec) == 64, "HybRec layout");
 
 // Shape of write_interpolative(pre, 127, 0, sum) for a full block: the node that codes pre[p] has the range
 // (lo[p] ? pre[lo[p] - 1] : 0) .. pre[hi[p]]. It depends on the block size alone.
@@ -580,26 +553,16 @@ __global__ void __launch_bounds__(64) k_hybrid_plan(EncArgs a) {
 
 } // namespace
 
+using namespace ds2i_launch;
 extern "C" {
-size_t ds2i_sizeof_enc_args() { return sizeof(EncArgs); }
-size_t ds2i_sizeof_hyb_rec() { return sizeof(HybRec); }
 // mode: the codec_kind of the image (block_optpfor, block_varint, block_interpolative; block_mixed has a write pass only)
-hipError_t ds2i_launch_encode(int mode, int write, const void* args, unsigned grid, hipStream_t s) {
-    const EncArgs& a = *(const EncArgs*)args;
-    const dim3 g(grid), b(64);
-    if (mode == ENC_OPTPFOR && write) hipLaunchKernelGGL((k_encode<true, ENC_OPTPFOR>), g, b, 0, s, a);
-    else if (mode == ENC_OPTPFOR) hipLaunchKernelGGL((k_encode<false, ENC_OPTPFOR>), g, b, 0, s, a);
-    else if (mode == ENC_VARINT && write) hipLaunchKernelGGL((k_encode<true, ENC_VARINT>), g, b, 0, s, a);
-    else if (mode == ENC_VARINT) hipLaunchKernelGGL((k_encode<false, ENC_VARINT>), g, b, 0, s, a);
-    else if (mode == ENC_INTERP && write) hipLaunchKernelGGL((k_encode<true, ENC_INTERP>), g, b, 0, s, a);
-    else if (mode == ENC_INTERP) hipLaunchKernelGGL((k_encode<false, ENC_INTERP>), g, b, 0, s, a);
-    else if (mode == ENC_MIXED && write) hipLaunchKernelGGL((k_encode<true, ENC_MIXED>), g, b, 0, s, a);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
+hipError_t ds2i_launch_encode(int mode, int write, const EncArgs& a, unsigned grid, hipStream_t s) {
+    return pick<ENC_OPTPFOR, ENC_VARINT, ENC_INTERP, ENC_MIXED>(mode, [&](auto m) { return with_bool(write != 0, [&](auto w) {
+        constexpr int MODE = decltype(m)::value;
+        constexpr bool WRITE = decltype(w)::value;
+        if constexpr (MODE == ENC_MIXED && !WRITE) return hipErrorInvalidValue;
+        else return launch(k_encode<WRITE, MODE>, dim3(grid), dim3(64), 0, s, a);
+    }); });
 }
-hipError_t ds2i_launch_hybrid_plan(const void* args, unsigned grid, hipStream_t s) {
-    const EncArgs& a = *(const EncArgs*)args;
-    hipLaunchKernelGGL(k_hybrid_plan, dim3(grid), dim3(64), 0, s, a);
-    return hipGetLastError();
-}
+hipError_t ds2i_launch_hybrid_plan(const EncArgs& a, unsigned grid, hipStream_t s) { return launch(k_hybrid_plan, dim3(grid), dim3(64), 0, s, a); }
 }

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 
 #include "device_enum.hpp"
+#include "dispatch.hpp"
+#include "launchers.hpp"
 
 using namespace ds2i_dev;
 
@@ -286,20 +288,15 @@ __global__ void __launch_bounds__(64, 8) k_and_stream(AndStreamArgs a) {
 
 } // namespace
 
+using namespace ds2i_launch;
 // longest = blocks of the longest list among the terms
-extern "C" hipError_t ds2i_launch_freq_stream(const void* args, unsigned longest, unsigned nqterms, hipStream_t s) {
-    const FreqArgs& a = *(const FreqArgs*)args;
+extern "C" hipError_t ds2i_launch_freq_stream(const FreqArgs& a, unsigned longest, unsigned nqterms, hipStream_t s) {
     if (!nqterms) return hipSuccess;
-    hipLaunchKernelGGL(k_freq_stream, dim3((longest + FS_RUN - 1) / FS_RUN, nqterms), dim3(64), 0, s, a);
-    return hipGetLastError();
+    return launch(k_freq_stream, dim3((longest + FS_RUN - 1) / FS_RUN, nqterms), dim3(64), 0, s, a);
 }
 
 // and / and_freq of the all-dense queries: nterms records of AndStreamArgs::terms, longest = blocks of the longest of their lists
-extern "C" hipError_t ds2i_launch_and_stream(const void* args, int with_freqs, unsigned longest, unsigned nterms, hipStream_t s) {
-    const AndStreamArgs& a = *(const AndStreamArgs*)args;
+extern "C" hipError_t ds2i_launch_and_stream(const AndStreamArgs& a, int with_freqs, unsigned longest, unsigned nterms, hipStream_t s) {
     if (!nterms) return hipSuccess;
-    const dim3 g((longest + FS_RUN - 1) / FS_RUN, nterms), b(64);
-    if (with_freqs) hipLaunchKernelGGL((k_and_stream<true>), g, b, 0, s, a);
-    else hipLaunchKernelGGL((k_and_stream<false>), g, b, 0, s, a);
-    return hipGetLastError();
+    return with_bool(with_freqs != 0, [&](auto f) { return launch(k_and_stream<decltype(f)::value>, dim3((longest + FS_RUN - 1) / FS_RUN, nterms), dim3(64), 0, s, a); });
 }

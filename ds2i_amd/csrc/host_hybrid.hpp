@@ -22,6 +22,7 @@
 #include <functional>
 #include <thread>
 
+#include "abi_structs.hpp"
 #include "host_encode.hpp"
 #include "host_index.hpp"
 
@@ -53,16 +54,7 @@ inline uint32_t interp_live_nodes(const uint32_t* pre, size_t n, uint32_t low, u
 
 // What the candidates of one part cost, as integers: the expensive half of the analysis (every encoder runs), and the
 // half the GPU plan kernel computes instead (encode_kernels.hip k_hybrid_plan fills the same record).
-struct hybrid_part_rec {
-    uint16_t pfor_words[17]; // payload words of OptPFor at OPTPFOR_LOGS[i] (packed values + Simple16 exceptions), 0xFFFF: not a candidate
-    uint8_t nexc[17];        // exceptions at that b
-    uint8_t interp_ok;       // the values sum to less than 2^32 - 1 (interpolative codes u32 prefix sums)
-    uint16_t varint_bytes;
-    uint16_t interp_bytes;   // full blocks: valid if interp_ok; partial blocks: the only field that is read
-    uint16_t live;           // interp_live_nodes
-    uint16_t pad[3];
-};
-static_assert(sizeof(hybrid_part_rec) == 64, "hybrid_part_rec layout");
+using hybrid_part_rec = ds2i_dev::HybRec; // abi_structs.hpp
 
 inline void hybrid_part_measure(const uint32_t* in, uint32_t sum, size_t n, hybrid_part_rec& r) {
     std::memset(&r, 0, sizeof r);

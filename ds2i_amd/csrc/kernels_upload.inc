@@ -330,16 +330,6 @@ __global__ void __launch_bounds__(64) k_selftest_bm25(const uint32_t* freqs, con
 }
 
 // wand / maxscore / ranked_or of a ONE-term query are exactly its ranked_and result: copy it from the seed pass
-struct CopySeedArgs {
-    const uint32_t* queries;
-    uint32_t n, k;
-    const float* seed_topk;
-    const uint32_t* seed_len;
-    const unsigned long long* seed_count;
-    float* out_topk;
-    uint32_t* out_len;
-    unsigned long long* out_count;
-};
 __global__ void __launch_bounds__(64) k_copy_seed(CopySeedArgs a) {
     const uint32_t lane = lane_id();
     for (uint32_t w = blockIdx.x; w < a.n; w += gridDim.x) {
@@ -351,11 +341,6 @@ __global__ void __launch_bounds__(64) k_copy_seed(CopySeedArgs a) {
 
 #ifdef DS2I_DOCS_TU
 // ... with the doc-ids (DS2I_OP_TOPK_DOCS: the seed batch ran the docs kernels too)
-struct CopySeedDocsArgs {
-    CopySeedArgs s;
-    const uint32_t* seed_docs;
-    uint32_t* out_docs;
-};
 __global__ void __launch_bounds__(64) k_copy_seed_docs(CopySeedDocsArgs a) {
     const uint32_t lane = lane_id();
     for (uint32_t w = blockIdx.x; w < a.s.n; w += gridDim.x) {

@@ -1,0 +1,58 @@
+// The one declaration of every launcher: the functions through which the host translation units (capi*.cpp) start the kernels of
+// the device ones (*.hip). Both sides include this header, so a definition whose signature drifts from its caller's fails to
+// compile (C linkage: a second signature under the same name is an error, not an overload). Argument blocks: abi_structs.hpp.
+// A name ending in _docs is the DS2I_OP_TOPK_DOCS build of the launcher before it (the -DDS2I_DOCS_TU units of build.py: the same
+// body over the (score, doc-id) heaps, defined under DS2I_KN(name), device_enum.hpp); same arguments, the docs fields of
+// BatchArgs / MergeArgs set; ranked operators only, no counters.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "abi_structs.hpp"
+
+extern "C" {
+// ---- kernels.hip
+// tmax_class: 0 -> TMAX 2, 1 -> TMAX 4, 2 -> TMAX 8, 3 -> TMAX 16 (LDS footprint per wave grows with TMAX), 4 -> more than 16 terms
+// (state in global scratch); op: a ds2i_dev::OP_* value, | OP_REFERENCE_ORDER for the one-document-per-step traversal
+hipError_t ds2i_launch_batch(int op, int tmax_class, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_batch_docs(int op, int tmax_class, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_merge(const ds2i_dev::MergeArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_merge_docs(const ds2i_dev::MergeArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_copy_seed(const ds2i_dev::CopySeedArgs& a, hipStream_t s);
+hipError_t ds2i_launch_copy_seed_docs(const ds2i_dev::CopySeedDocsArgs& a, hipStream_t s);
+uint32_t ds2i_meta_words(void); // dwords of enumerator state per list slot (M_WORDS)
+hipError_t ds2i_launch_block_max_weights(const ds2i_dev::BmwArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_build_side_tables(const ds2i_dev::SideArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_list_top_bmw(const float* bmw, const ds2i_dev::QTerm* lists, uint32_t nlists, float* out, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_decode_list(const ds2i_dev::DecodeArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_decode_list_side(const ds2i_dev::DecodeArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_selftest(const uint32_t* in, uint32_t* out, unsigned blocks, hipStream_t s);
+hipError_t ds2i_launch_selftest_bm25(const uint32_t* freqs, const float* norm_lens, float* out, uint32_t n, hipStream_t s);
+hipError_t ds2i_launch_calib_read(const uint32_t* base, unsigned long long ndw, uint32_t* out, unsigned grid, hipStream_t s);
+
+// ---- ranked_stream.hip (ranked_and; and / and_freq through the same pipeline), union_stream.hip (wand / maxscore / ranked_or).
+// cap = list capacity of the launch (2, 4, 6, 8, 16); _bigk: 64 < k <= 1024, the units compiled with -DDS2I_RS_BIGK_TU / -DDS2I_US_BIGK_TU
+hipError_t ds2i_launch_ranked_stream(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_docs(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_bigk(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_bigk_docs(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_and_rstream(int cap, int with_freqs, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_union_stream(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_union_stream_docs(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_union_stream_bigk(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_union_stream_bigk_docs(int cap, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+// ---- ranked_stream_mixed.hip: nt = exact number of distinct terms of every query of the launch (2..4)
+hipError_t ds2i_launch_ranked_stream_mixed(int nt, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_ranked_stream_mixed_docs(int nt, const ds2i_dev::BatchArgs& a, unsigned grid, hipStream_t s);
+
+// ---- freq_stream.hip: longest = blocks of the longest list among the terms
+hipError_t ds2i_launch_freq_stream(const ds2i_dev::FreqArgs& a, unsigned longest, unsigned nqterms, hipStream_t s);
+hipError_t ds2i_launch_and_stream(const ds2i_dev::AndStreamArgs& a, int with_freqs, unsigned longest, unsigned nterms, hipStream_t s);
+
+// ---- encode_kernels.hip, wand_kernels.hip
+// mode: the codec_kind of the image (block_optpfor, block_varint, block_interpolative; block_mixed has a write pass only)
+hipError_t ds2i_launch_encode(int mode, int write, const ds2i_dev::EncArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_hybrid_plan(const ds2i_dev::EncArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_wand_list_max(const uint32_t* docs, const uint32_t* freqs, const uint64_t* list_in, const uint32_t* blk_list,
+                                     const uint32_t* list_blk0, uint32_t nblocks, const float* norm_lens, uint64_t num_docs,
+                                     unsigned int* list_max, unsigned max_groups, hipStream_t s);
+}

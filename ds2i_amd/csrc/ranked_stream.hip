@@ -36,6 +36,8 @@
 #include "device_enum.hpp"
 #include "device_score.hpp"
 #include "stream_common.hpp"
+#include "dispatch.hpp"
+#include "launchers.hpp"
 
 using namespace ds2i_dev;
 using namespace ds2i_dev::stream;
@@ -811,91 +813,35 @@ __global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) DS2I_KN(k_ranked_strea
 
 } // namespace
 
+using namespace ds2i_launch;
 extern "C" {
-#ifdef DS2I_DOCS_TU
-// DS2I_OP_TOPK_DOCS: k_ranked_stream_docs, the (score, doc-id) heaps, uninstrumented only (a docs batch runs without counters);
-// the same caps and k split as the launchers below
-#ifdef DS2I_RS_BIGK_TU
-hipError_t ds2i_launch_ranked_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-#define DS2I_RSK_CASE(N) case N: \
-        if (a.k <= 256) hipLaunchKernelGGL((k_ranked_stream_docs<N, false, false, false, 4>), g, b, 0, s, a); \
-        else hipLaunchKernelGGL((k_ranked_stream_docs<N, false, false, false, 16>), g, b, 0, s, a); \
-        break;
-    switch (cap) {
-    DS2I_RSK_CASE(2) DS2I_RSK_CASE(4) DS2I_RSK_CASE(6) DS2I_RSK_CASE(8) DS2I_RSK_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_RSK_CASE
-    return hipGetLastError();
-}
-#else
-hipError_t ds2i_launch_ranked_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-#define DS2I_RS_CASE(N) case N: hipLaunchKernelGGL((k_ranked_stream_docs<N, false>), g, b, 0, s, a); break;
-    switch (cap) {
-    DS2I_RS_CASE(2) DS2I_RS_CASE(4) DS2I_RS_CASE(6) DS2I_RS_CASE(8) DS2I_RS_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_RS_CASE
-    return hipGetLastError();
-}
-#endif
-#else // !DS2I_DOCS_TU
-#ifdef DS2I_RS_BIGK_TU
-// ranked_and with 64 < k <= 1024 (compiled as a translation unit of its own: -DDS2I_RS_BIGK_TU, ds2i_amd/build.py): k <= 256 keeps four
-// scores per lane, beyond that sixteen; cap as below, one-term queries ride in the capacity-4 launch
-hipError_t ds2i_launch_ranked_stream_bigk(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    const bool st = a.stats != nullptr;
-#define DS2I_RSK_CASE(N) case N: \
-        if (a.k <= 256) { if (st) hipLaunchKernelGGL((k_ranked_stream<N, true, false, false, 4>), g, b, 0, s, a); else hipLaunchKernelGGL((k_ranked_stream<N, false, false, false, 4>), g, b, 0, s, a); } \
-        else { if (st) hipLaunchKernelGGL((k_ranked_stream<N, true, false, false, 16>), g, b, 0, s, a); else hipLaunchKernelGGL((k_ranked_stream<N, false, false, false, 16>), g, b, 0, s, a); } \
-        break;
-    switch (cap) {
-    DS2I_RSK_CASE(2) DS2I_RSK_CASE(4) DS2I_RSK_CASE(6) DS2I_RSK_CASE(8) DS2I_RSK_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_RSK_CASE
-    return hipGetLastError();
-}
-#else
 // cap = list capacity of the launch (2, 4, 6, 8, 16): every query of it has cap - 1 or cap (16: 9 .. 16) distinct terms (UnitRec::pad = the count; the
-// planner's DS2I_STREAM_NT_MAX caps it); the caller has checked that the index is block_optpfor with skip table, block weights, range
-// tables and side slots, and that k <= 64
-hipError_t ds2i_launch_ranked_stream(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    const bool st = a.stats != nullptr;
-#define DS2I_RS_CASE(N) case N: if (st) hipLaunchKernelGGL((k_ranked_stream<N, true>), g, b, 0, s, a); else hipLaunchKernelGGL((k_ranked_stream<N, false>), g, b, 0, s, a); break;
-    switch (cap) {
-    DS2I_RS_CASE(2) DS2I_RS_CASE(4) DS2I_RS_CASE(6) DS2I_RS_CASE(8) DS2I_RS_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_RS_CASE
-    return hipGetLastError();
+// planner's DS2I_STREAM_NT_MAX caps it), one-term queries ride in the capacity-4 launch; the caller has checked that the index is
+// block_optpfor with skip table, block weights, range tables and side slots
+#ifdef DS2I_RS_BIGK_TU
+// 64 < k <= 1024, a translation unit of its own (ds2i_amd/build.py): k <= 256 keeps four scores per lane, beyond that sixteen
+hipError_t DS2I_KN(ds2i_launch_ranked_stream_bigk)(int cap, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    return with_cap(cap, [&](auto n) { return with_big_heap(a.k, [&](auto nk) { return with_bool(a.stats != nullptr, [&](auto counters) {
+        constexpr bool ST = instrumented(K_STREAM, CODEC_OPTPFOR, decltype(counters)::value);
+        return launch(DS2I_KN(k_ranked_stream)<decltype(n)::value, ST, false, false, decltype(nk)::value>, dim3(grid), dim3(64), 0, s, a);
+    }); }); });
 }
-#endif
-#ifndef DS2I_RS_BIGK_TU
+#else
+// k <= 64
+hipError_t DS2I_KN(ds2i_launch_ranked_stream)(int cap, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    return with_cap(cap, [&](auto n) { return with_bool(a.stats != nullptr, [&](auto counters) {
+        constexpr bool ST = instrumented(K_STREAM, CODEC_OPTPFOR, decltype(counters)::value);
+        return launch(DS2I_KN(k_ranked_stream)<decltype(n)::value, ST>, dim3(grid), dim3(64), 0, s, a);
+    }); });
+}
+#ifndef DS2I_DOCS_TU
 // and_query (counts; with_freqs: counts + the freq checksum) through the same pipeline (k_ranked_stream<cap, ., AND = true, FREQS>); same preconditions
-hipError_t ds2i_launch_and_rstream(int cap, int with_freqs, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    const bool st = a.stats != nullptr;
-#define DS2I_AND_CASE(N) case N: \
-        if (with_freqs) { if (st) hipLaunchKernelGGL((k_ranked_stream<N, true, true, true>), g, b, 0, s, a); else hipLaunchKernelGGL((k_ranked_stream<N, false, true, true>), g, b, 0, s, a); } \
-        else { if (st) hipLaunchKernelGGL((k_ranked_stream<N, true, true>), g, b, 0, s, a); else hipLaunchKernelGGL((k_ranked_stream<N, false, true>), g, b, 0, s, a); } \
-        break;
-    switch (cap) {
-    DS2I_AND_CASE(2) DS2I_AND_CASE(4) DS2I_AND_CASE(6) DS2I_AND_CASE(8) DS2I_AND_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_AND_CASE
-    return hipGetLastError();
+hipError_t ds2i_launch_and_rstream(int cap, int with_freqs, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    return with_cap(cap, [&](auto n) { return with_bool(with_freqs != 0, [&](auto f) { return with_bool(a.stats != nullptr, [&](auto counters) {
+        constexpr bool ST = instrumented(K_STREAM, CODEC_OPTPFOR, decltype(counters)::value);
+        return launch(k_ranked_stream<decltype(n)::value, ST, true, decltype(f)::value>, dim3(grid), dim3(64), 0, s, a);
+    }); }); });
 }
 #endif
-#endif // DS2I_DOCS_TU
+#endif
 }

@@ -31,6 +31,8 @@
 
 #include "device_enum.hpp"
 #include "device_score.hpp"
+#include "dispatch.hpp"
+#include "launchers.hpp"
 
 using namespace ds2i_dev;
 
@@ -774,33 +776,12 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) DS2I_KN(k_ranked_stream_mixe
 
 } // namespace
 
-extern "C" {
-#ifdef DS2I_DOCS_TU
-// DS2I_OP_TOPK_DOCS: k_ranked_stream_mixed_docs, uninstrumented (a docs batch passes no counters)
-hipError_t ds2i_launch_ranked_stream_mixed_docs(int nt, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    switch (nt) {
-    case 2: hipLaunchKernelGGL((k_ranked_stream_mixed_docs<2, false, CODEC_MIXED>), g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((k_ranked_stream_mixed_docs<3, false, CODEC_MIXED>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((k_ranked_stream_mixed_docs<4, false, CODEC_MIXED>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#else
+using namespace ds2i_launch;
 // nt = exact number of distinct terms of every query of the launch (2..4); block_mixed index with skip table, block weights
-// and range tables, k <= 64 (instrumented and uninstrumented runs share the instantiation with counters)
-hipError_t ds2i_launch_ranked_stream_mixed(int nt, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    switch (nt) {
-    case 2: hipLaunchKernelGGL((k_ranked_stream_mixed<2, true, CODEC_MIXED>), g, b, 0, s, a); break;
-    case 3: hipLaunchKernelGGL((k_ranked_stream_mixed<3, true, CODEC_MIXED>), g, b, 0, s, a); break;
-    case 4: hipLaunchKernelGGL((k_ranked_stream_mixed<4, true, CODEC_MIXED>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-#endif // DS2I_DOCS_TU
+// and range tables, k <= 64
+extern "C" hipError_t DS2I_KN(ds2i_launch_ranked_stream_mixed)(int nt, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    return with_lists(nt, [&](auto n) { return with_bool(a.stats != nullptr, [&](auto counters) {
+        constexpr bool ST = instrumented(K_STREAM, CODEC_MIXED, decltype(counters)::value);
+        return launch(DS2I_KN(k_ranked_stream_mixed)<decltype(n)::value, ST, CODEC_MIXED>, dim3(grid), dim3(64), 0, s, a);
+    }); });
 }

@@ -38,6 +38,8 @@
 #include "device_enum.hpp"
 #include "device_score.hpp"
 #include "stream_common.hpp"
+#include "dispatch.hpp"
+#include "launchers.hpp"
 
 using namespace ds2i_dev;
 using namespace ds2i_dev::stream;
@@ -702,72 +704,26 @@ __global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) DS2I_KN(k_union_stream
 
 } // namespace
 
+using namespace ds2i_launch;
 extern "C" {
-#ifdef DS2I_DOCS_TU
-// DS2I_OP_TOPK_DOCS: k_union_stream_docs (uninstrumented; same caps and k split as below)
-#ifdef DS2I_US_BIGK_TU
-hipError_t ds2i_launch_union_stream_bigk_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-#define DS2I_USK_CASE(N) case N: \
-        if (a.k <= 256) hipLaunchKernelGGL((k_union_stream_docs<N, false, 4>), g, b, 0, s, a); \
-        else hipLaunchKernelGGL((k_union_stream_docs<N, false, 16>), g, b, 0, s, a); \
-        break;
-    switch (cap) {
-    DS2I_USK_CASE(2) DS2I_USK_CASE(4) DS2I_USK_CASE(6) DS2I_USK_CASE(8) DS2I_USK_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_USK_CASE
-    return hipGetLastError();
-}
-#else
-hipError_t ds2i_launch_union_stream_docs(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-#define DS2I_US_CASE(N) case N: hipLaunchKernelGGL((k_union_stream_docs<N, false>), g, b, 0, s, a); break;
-    switch (cap) {
-    DS2I_US_CASE(2) DS2I_US_CASE(4) DS2I_US_CASE(6) DS2I_US_CASE(8) DS2I_US_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_US_CASE
-    return hipGetLastError();
-}
-#endif
-#else // !DS2I_DOCS_TU
-#ifdef DS2I_US_BIGK_TU
-// wand / maxscore / ranked_or with 64 < k <= 1024 (a translation unit of its own: -DDS2I_US_BIGK_TU, ds2i_amd/build.py): k <= 256 keeps
-// four scores per lane, beyond that sixteen; cap as below
-hipError_t ds2i_launch_union_stream_bigk(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    const bool st = a.stats != nullptr;
-#define DS2I_USK_CASE(N) case N: \
-        if (a.k <= 256) { if (st) hipLaunchKernelGGL((k_union_stream<N, true, 4>), g, b, 0, s, a); else hipLaunchKernelGGL((k_union_stream<N, false, 4>), g, b, 0, s, a); } \
-        else { if (st) hipLaunchKernelGGL((k_union_stream<N, true, 16>), g, b, 0, s, a); else hipLaunchKernelGGL((k_union_stream<N, false, 16>), g, b, 0, s, a); } \
-        break;
-    switch (cap) {
-    DS2I_USK_CASE(2) DS2I_USK_CASE(4) DS2I_USK_CASE(6) DS2I_USK_CASE(8) DS2I_USK_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_USK_CASE
-    return hipGetLastError();
-}
-#else
 // cap = list capacity of the launch (2, 4, 6, 8, 16): every virtual query of it has cap - 1 or cap (16: 9 .. 16) lists (driver + exclusions + optional
 // lists; UnitRec::pad = exclusion lists | lists << 8); the caller has checked that the index is block_optpfor with skip table, block
-// weights, range tables and side slots, that k <= 64, and has filled BatchArgs::urec and BatchArgs::q_floor
-hipError_t ds2i_launch_union_stream(int cap, const void* args, unsigned grid, hipStream_t s) {
-    const BatchArgs& a = *(const BatchArgs*)args;
-    const dim3 g(grid), b(64);
-    const bool st = a.stats != nullptr;
-#define DS2I_US_CASE(N) case N: if (st) hipLaunchKernelGGL((k_union_stream<N, true>), g, b, 0, s, a); else hipLaunchKernelGGL((k_union_stream<N, false>), g, b, 0, s, a); break;
-    switch (cap) {
-    DS2I_US_CASE(2) DS2I_US_CASE(4) DS2I_US_CASE(6) DS2I_US_CASE(8) DS2I_US_CASE(16)
-    default: return hipErrorInvalidValue;
-    }
-#undef DS2I_US_CASE
-    return hipGetLastError();
+// weights, range tables and side slots, and has filled BatchArgs::urec and BatchArgs::q_floor
+#ifdef DS2I_US_BIGK_TU
+// 64 < k <= 1024, a translation unit of its own (ds2i_amd/build.py): k <= 256 keeps four scores per lane, beyond that sixteen
+hipError_t DS2I_KN(ds2i_launch_union_stream_bigk)(int cap, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    return with_cap(cap, [&](auto n) { return with_big_heap(a.k, [&](auto nk) { return with_bool(a.stats != nullptr, [&](auto counters) {
+        constexpr bool ST = instrumented(K_STREAM, CODEC_OPTPFOR, decltype(counters)::value);
+        return launch(DS2I_KN(k_union_stream)<decltype(n)::value, ST, decltype(nk)::value>, dim3(grid), dim3(64), 0, s, a);
+    }); }); });
+}
+#else
+// k <= 64
+hipError_t DS2I_KN(ds2i_launch_union_stream)(int cap, const BatchArgs& a, unsigned grid, hipStream_t s) {
+    return with_cap(cap, [&](auto n) { return with_bool(a.stats != nullptr, [&](auto counters) {
+        constexpr bool ST = instrumented(K_STREAM, CODEC_OPTPFOR, decltype(counters)::value);
+        return launch(DS2I_KN(k_union_stream)<decltype(n)::value, ST>, dim3(grid), dim3(64), 0, s, a);
+    }); });
 }
 #endif
-#endif // DS2I_DOCS_TU
 }

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device_score.hpp"
+#include "launchers.hpp"
 
 using namespace ds2i_dev;
 
