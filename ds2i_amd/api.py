@@ -136,6 +136,8 @@ def lib():
         L.ds2i_hip_synth_encode.argtypes = [C.c_int, C.POINTER(SynthParams), C.c_int, C.POINTER(vp), C.POINTER(vp), u64p,
                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]
         L.ds2i_hip_encode_index.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_encode_host_seconds.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_encode_host_seconds.restype = None
         L.ds2i_hip_build_wand.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_build_collection.argtypes = [C.c_int, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(vp),
                                                 C.POINTER(C.c_double)]
@@ -269,7 +271,9 @@ def _csr(lists):
 
 def gpu_encode_index(num_docs, lists, device=0, codec="block_optpfor"):
     """The index image of `lists` (iterable of (docs, freqs)) encoded ON THE GPU (ds2i_hip_encode_index): byte-identical
-    to build_index(codec, num_docs, lists). Returns (image bytes, device milliseconds of the two kernel passes)."""
+    to build_index(codec, num_docs, lists). codec: "block_optpfor", "block_varint", "block_interpolative", or one of the
+    Elias-Fano layouts "opt", "ef", "single", "uniform" (default global_parameters; doc-ids strictly increasing and
+    < num_docs, freqs >= 1, checked on the host). Returns (image bytes, device milliseconds of the kernels)."""
     n, offs, docs, freqs = _csr(lists)
     h, ms = C.c_void_p(), C.c_double()
     _check(lib().ds2i_hip_encode_index(device, _codec(codec), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
@@ -289,7 +293,8 @@ def gpu_build_wand(doc_sizes, lists, device=0):
 
 def gpu_build_collection(num_docs, doc_sizes, lists, codec="block_optpfor", device=0):
     """Index image and wand_data image of one collection from ONE staging on the GPU (ds2i_hip_build_collection): what
-    gpu_encode_index and gpu_build_wand return, everything Index(codec, index, wand) needs.
+    gpu_encode_index and gpu_build_wand return, everything Index(codec, index, wand) needs. codec: as gpu_encode_index
+    (the block codecs and "opt", "ef", "single", "uniform").
     Returns (index image, wand image, dict(device_ms))."""
     s = _u32(doc_sizes)
     if len(s) != num_docs:

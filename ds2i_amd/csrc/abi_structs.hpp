@@ -331,4 +331,40 @@ struct HybRec {
 };
 static_assert(sizeof(HybRec) == 64, "HybRec is a 64-byte device record");
 
+// The Elias-Fano layouts' encoder (freq_encode_kernels.hip). One FreqJob = one base sequence of one side (docs, or the freqs'
+// prefix sums) of one list: a partition of an opt / uniform list, or the whole of an ef / single list -- what seq_write / ef_write
+// (host_pef.hpp, host_index.hpp) emit for it. The host sizes and places it (ef_offsets / rb_offsets: closed forms of universe and
+// n) and the kernel writes its bits. Offsets are absolute bit positions in the side's bit vector. The jobs of a side are in
+// posting order and tile [0, postings): job j holds the postings [src, src + n).
+enum : uint32_t { FREQ_SEQ_EF = 0, FREQ_SEQ_RB = 1, FREQ_SEQ_ALL_ONES = 2 }; // host_pef.hpp seq_type
+struct FreqJob {
+    uint64_t src;      // global index of its first posting
+    uint64_t n;
+    uint64_t origin;   // stored value of element i: value - origin, and - i more when `shift` (strict Elias-Fano)
+    uint64_t type_off; // where the type bit goes (typed: indexed_sequence / strict_sequence)
+    uint64_t a_off;    // EF: pointers0        RB: rank1_samples
+    uint64_t b_off;    // EF: pointers1        RB: pointers1
+    uint64_t hi_off;   // EF: high bits        RB: the characteristic vector
+    uint64_t lo_off;   // EF: low bits
+    uint64_t hi_len;   // EF: higher_bits_length   RB: universe
+    uint64_t na, nb;   // entries of the two sampled arrays
+    uint8_t type;      // FREQ_SEQ_*
+    uint8_t typed;     // a type bit precedes the sequence
+    uint8_t shift;
+    uint8_t l;         // EF: lower_bits
+    uint8_t wa, wb;    // bits per entry of the two arrays (RB: rank1_sample_size, pointer_size; EF: pointer_size twice)
+    uint8_t lsa, lsb;  // log2 of their sampling steps (EF: log_sampling0, log_sampling1; RB: log_rank1_sampling, log_sampling1)
+};
+static_assert(sizeof(FreqJob) == 96, "FreqJob is a 96-byte device record");
+
+struct FreqEncArgs {
+    const uint32_t* docs;     // the side's values: docs (docs side) or cum (freqs side)
+    const uint64_t* cum;
+    const FreqJob* jobs;
+    uint64_t njobs;
+    uint64_t postings;
+    unsigned long long* out;  // zero-filled, (nbits + 63) / 64 words and two words of padding
+    uint64_t nbits;
+};
+
 } // namespace ds2i_dev

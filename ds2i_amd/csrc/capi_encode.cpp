@@ -8,16 +8,22 @@
 // The wand_data image is built over the same staging (ds2i_hip_build_wand; ds2i_hip_build_collection returns it together
 // with the index image from ONE upload): norm_lens on the host as compute_norm_lens writes them, every list's maximum
 // term weight by wand_kernels.hip.
+// The Elias-Fano layouts (opt, ef, single, uniform) go through the same entry points and the same staging: the host plans every
+// list (host_freq_plan.hpp: headers, and the place of every base sequence), freq_encode_kernels.hip writes the base sequences.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <memory>
+#include <mutex>
+#include <thread>
 #include <vector>
 
 #include "capi_blob.hpp"
 #include "capi_hybrid.hpp"
 #include "capi_internal.hpp"
+#include "host_freq_plan.hpp"
 #include "host_index.hpp"
 #include "launchers.hpp"
 
@@ -190,6 +196,136 @@ int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image,
     return st.wrap(codec, num_docs, bytes, list_end, image);
 }
 
+// ---- the Elias-Fano layouts (freq_index: opt, ef, single, uniform) over a staged collection
+constexpr int FREQ_PLAN_THREADS = 16; // the planning pool's cap: never the whole machine's CPU count
+
+// `fn(t)` for every list on the host pool ds2i_synth_build uses (threads drawing list numbers), at most FREQ_PLAN_THREADS wide
+template <class Fn>
+void for_each_list(uint64_t nlists, Fn fn) {
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const unsigned threads = (unsigned)std::min<uint64_t>(std::min<unsigned>(hw, FREQ_PLAN_THREADS), std::max<uint64_t>(nlists, 1));
+    std::atomic<uint64_t> next(0);
+    std::string err;
+    std::mutex err_mu;
+    auto worker = [&]() {
+        try {
+            for (;;) {
+                const uint64_t t = next.fetch_add(1);
+                if (t >= nlists) break;
+                fn(t);
+            }
+        } catch (std::exception const& e) {
+            std::lock_guard<std::mutex> g(err_mu);
+            err = e.what();
+        }
+    };
+    std::vector<std::thread> pool;
+    for (unsigned i = 1; i < threads; ++i) pool.emplace_back(worker);
+    worker();
+    for (auto& th : pool) th.join();
+    if (!err.empty()) throw std::runtime_error(err);
+}
+
+// Plan on the host (for opt: optimal_partition, list-parallel), prefix sums and base sequences on the device, headers ORed into
+// the downloaded vectors, opt_index_builder::freeze around them. ms accumulates the hipEvent time of the kernels; the host's two
+// phases are left in freq_host_s for ds2i_hip_encode_host_seconds.
+thread_local double freq_host_s[2] = {0.0, 0.0}; // seconds of {planning, download + headers + freeze} of this thread's last call
+int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image,
+                       double& ms) {
+    using namespace ds2i_host;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t nlists = st.nlists;
+    const uint64_t* offs = st.list_offsets;
+    const uint64_t postings = offs[nlists];
+    const global_parameters params;
+    std::vector<freq_list_plan> plans(nlists);
+    for_each_list(nlists, [&](uint64_t t) {
+        plan_list(layout, num_docs, params, offs[t], offs[t + 1] - offs[t], docs + offs[t], freqs + offs[t], plans[t]);
+    });
+    // where every list starts in the two bit vectors; the jobs move to their final offsets
+    std::vector<uint64_t> ends[2], head_at[2];
+    std::vector<ds2i_dev::FreqJob> jobs[2];
+    for (int side = 0; side < 2; ++side) {
+        uint64_t njobs = 0;
+        for (auto const& pl : plans) njobs += pl.jobs[side].size();
+        jobs[side].reserve(njobs);
+        ends[side].assign(1, 0);
+        ends[side].reserve(nlists + 1);
+        uint64_t cursor = 0;
+        for (auto& pl : plans) {
+            const uint64_t body_at = cursor + pl.head[side].size();
+            for (auto j : pl.jobs[side]) {
+                place(j, body_at);
+                jobs[side].push_back(j);
+            }
+            std::vector<ds2i_dev::FreqJob>().swap(pl.jobs[side]);
+            cursor = body_at + pl.body_bits[side];
+            ends[side].push_back(cursor);
+        }
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- device: prefix sums of the freqs, then the base sequences of both sides
+    uint64_t *d_blk_base = nullptr, *d_cum = nullptr;
+    HIP_OK(st.dev.alloc(&d_blk_base, 8 * st.nblocks));
+    HIP_OK(st.dev.alloc(&d_cum, 8 * postings));
+    ds2i_dev::FreqEncArgs fa[2];
+    uint64_t words[2];
+    for (int side = 0; side < 2; ++side) {
+        ds2i_dev::FreqJob* d_jobs = nullptr;
+        unsigned long long* d_out = nullptr;
+        words[side] = (ends[side].back() + 63) / 64;
+        HIP_OK(st.dev.alloc(&d_jobs, sizeof(ds2i_dev::FreqJob) * jobs[side].size()));
+        HIP_OK(st.dev.alloc(&d_out, 8 * (words[side] + 2)));
+        HIP_OK(hipMemcpy(d_jobs, jobs[side].data(), sizeof(ds2i_dev::FreqJob) * jobs[side].size(), hipMemcpyHostToDevice));
+        HIP_OK(hipMemset(d_out, 0, 8 * (words[side] + 2)));
+        fa[side].docs = st.a.docs;
+        fa[side].cum = d_cum;
+        fa[side].jobs = d_jobs;
+        fa[side].njobs = jobs[side].size();
+        fa[side].postings = postings;
+        fa[side].out = d_out;
+        fa[side].nbits = ends[side].back();
+        std::vector<ds2i_dev::FreqJob>().swap(jobs[side]);
+    }
+    Events evs;
+    HIP_OK(hipEventCreate(&evs.e[0]));
+    HIP_OK(hipEventCreate(&evs.e[1]));
+    HIP_OK(hipEventRecord(evs.e[0], nullptr));
+    if (st.nblocks) {
+        HIP_OK(ds2i_launch_freq_prefix_sums(st.a, nlists, d_blk_base, d_cum, st.grid, nullptr));
+        HIP_OK(ds2i_launch_freq_write(0, fa[0], st.grid, nullptr));
+        HIP_OK(ds2i_launch_freq_write(1, fa[1], st.grid, nullptr));
+    }
+    HIP_OK(hipEventRecord(evs.e[1], nullptr));
+    HIP_OK(hipEventSynchronize(evs.e[1]));
+    float t = 0.f;
+    HIP_OK(hipEventElapsedTime(&t, evs.e[0], evs.e[1]));
+    ms += t;
+    // ---- host: the headers join the device's words; the container is the host builder's
+    const auto t2 = std::chrono::steady_clock::now();
+    try {
+        bitvec_builder bits[2];
+        for (int side = 0; side < 2; ++side) {
+            bits[side].zero_extend(ends[side].back());
+            HIP_OK(hipMemcpy(bits[side].words().data(), fa[side].out, 8 * words[side], hipMemcpyDeviceToHost));
+            for (uint64_t l = 0; l < nlists; ++l) or_bits_at(bits[side].words(), ends[side][l], plans[l].head[side]);
+        }
+        std::vector<freq_list_plan>().swap(plans);
+        opt_index_builder builder(num_docs, params, layout);
+        builder.set_encoded(std::move(bits[0]), std::move(ends[0]), std::move(bits[1]), std::move(ends[1]));
+        std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
+        builder.freeze(blob->data);
+        *image = blob.release();
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    }
+    freq_host_s[0] = std::chrono::duration<double>(t1 - t0).count();
+    freq_host_s[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count();
+    return DS2I_OK;
+}
+
 // max_term_weight of every list of a staged collection (wand_kernels.hip); ms accumulates the kernel's hipEvent time
 int wand_max_staged(EncStage& st, const std::vector<float>& norm_lens, std::vector<float>& max_w, double& ms) {
     static_assert(sizeof(float) == sizeof(unsigned int), "the list maxima travel as the bits of a float");
@@ -216,7 +352,7 @@ int wand_max_staged(EncStage& st, const std::vector<float>& norm_lens, std::vect
     return DS2I_OK;
 }
 
-// The images of one staged collection: the index of `codec` (index_image non-null) and / or the wand_data image over
+// The images of one staged collection: the index of `codec` (a block codec_kind or a freq_layout; index_image non-null) and / or the wand_data image over
 // `norm_lens` (wand_image non-null), from ONE upload. Neither output is touched unless both succeed.
 int build_images(const char* who, int device, int codec, uint64_t num_docs, const std::vector<float>* norm_lens, uint64_t nlists,
                  const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs, ds2i_blob** index_image,
@@ -225,7 +361,9 @@ int build_images(const char* who, int device, int codec, uint64_t num_docs, cons
     STAGE_OK(st.upload(who, device, nlists, list_offsets, docs, freqs));
     double ms = 0.0;
     ds2i_blob* ib = nullptr;
-    if (index_image) STAGE_OK(encode_staged(st, codec, num_docs, &ib, ms));
+    if (index_image)
+        STAGE_OK(ds2i_host::is_freq_layout(codec) ? freq_encode_staged(st, codec, num_docs, docs, freqs, &ib, ms)
+                                                  : encode_staged(st, codec, num_docs, &ib, ms));
     std::unique_ptr<ds2i_blob> index_blob(ib), wand_blob;
     if (wand_image) {
         std::vector<float> max_w;
@@ -239,9 +377,17 @@ int build_images(const char* who, int device, int codec, uint64_t num_docs, cons
     return DS2I_OK;
 }
 
-int block_codec_of(const char* who, int index_kind, int& codec) {
+// the encoder's name for an index kind: the block codec_kind (host_encode.hpp) or the freq_layout (host_pef.hpp)
+int encoder_kind_of(const char* who, int index_kind, int& codec) {
+    if (ds2i_host::is_freq_layout(index_kind)) {
+        static_assert(DS2I_OPT == ds2i_host::LAYOUT_OPT && DS2I_EF == ds2i_host::LAYOUT_EF && DS2I_SINGLE == ds2i_host::LAYOUT_SINGLE &&
+                          DS2I_UNIFORM == ds2i_host::LAYOUT_UNIFORM, "freq_layout is numbered like ds2i_hip_index_kind");
+        codec = index_kind;
+        return DS2I_OK;
+    }
     if (index_kind != DS2I_BLOCK_OPTPFOR && index_kind != DS2I_BLOCK_VARINT && index_kind != DS2I_BLOCK_INTERPOLATIVE)
-        return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": the GPU encoder writes block_optpfor, block_varint and block_interpolative indexes").c_str());
+        return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": the GPU encoder writes block_optpfor, block_varint, block_interpolative, opt, ef, "
+                                                               "single and uniform indexes").c_str());
     codec = index_kind == DS2I_BLOCK_OPTPFOR ? ds2i_host::CODEC_OPTPFOR
             : index_kind == DS2I_BLOCK_VARINT ? ds2i_host::CODEC_VARINT : ds2i_host::CODEC_INTERPOLATIVE;
     return DS2I_OK;
@@ -258,18 +404,41 @@ int check_postings(const char* who, uint64_t num_docs, uint64_t nlists, const ui
     }
     return DS2I_OK;
 }
+// what the Elias-Fano layouts rely on, checked before anything is staged: no empty list, doc-ids strictly increasing and below
+// num_docs (the sequences are sorted sets over that universe), every freq >= 1 (a zero makes the prefix sums non-strict)
+int check_freq_postings(const char* who, uint64_t num_docs, uint64_t nlists, const uint64_t* offs, const uint32_t* docs,
+                        const uint32_t* freqs) {
+    const std::string w(who);
+    for (uint64_t t = 0; t < nlists; ++t) {
+        if (offs[t + 1] <= offs[t]) return ds2i_set_error(DS2I_EINVAL, "List must be nonempty");
+        if (offs[t + 1] - offs[t] > 0xFFFFFFFFull) return ds2i_set_error(DS2I_EINVAL, "posting list longer than 2^32");
+        for (uint64_t i = offs[t]; i < offs[t + 1]; ++i) {
+            if (i > offs[t] && docs[i] <= docs[i - 1]) return ds2i_set_error(DS2I_EINVAL, (w + ": doc ids not strictly increasing").c_str());
+            if (docs[i] >= num_docs) return ds2i_set_error(DS2I_EINVAL, (w + ": doc id out of range").c_str());
+            if (!freqs[i]) return ds2i_set_error(DS2I_EINVAL, (w + ": zero freq").c_str());
+        }
+    }
+    return DS2I_OK;
+}
 } // namespace
 
 extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                                      const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms) {
     if (!list_offsets || !docs || !freqs || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: null argument");
     int codec = 0;
-    STAGE_OK(block_codec_of("ds2i_hip_encode_index", index_kind, codec));
+    STAGE_OK(encoder_kind_of("ds2i_hip_encode_index", index_kind, codec));
+    if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings("ds2i_hip_encode_index", num_docs, nlists, list_offsets, docs, freqs));
     try {
         return build_images("ds2i_hip_encode_index", device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms);
     } catch (std::bad_alloc const&) {
         return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    } catch (std::exception const& e) { // the planner of the Elias-Fano layouts
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
     }
+}
+
+extern "C" void ds2i_hip_encode_host_seconds(double seconds[2]) {
+    if (seconds) seconds[0] = freq_host_s[0], seconds[1] = freq_host_s[1];
 }
 
 extern "C" int ds2i_hip_build_wand(int device, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
@@ -292,8 +461,9 @@ extern "C" int ds2i_hip_build_collection(int device, int index_kind, const uint3
     if (!list_offsets || !docs || !freqs || !index_image || (wand_image && (!doc_sizes || !num_docs)))
         return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_build_collection: bad argument");
     int codec = 0;
-    STAGE_OK(block_codec_of("ds2i_hip_build_collection", index_kind, codec));
+    STAGE_OK(encoder_kind_of("ds2i_hip_build_collection", index_kind, codec));
     STAGE_OK(check_postings("ds2i_hip_build_collection", num_docs, nlists, list_offsets, docs));
+    if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings("ds2i_hip_build_collection", num_docs, nlists, list_offsets, docs, freqs));
     try {
         std::vector<float> norm_lens;
         if (wand_image) ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
@@ -301,6 +471,8 @@ extern "C" int ds2i_hip_build_collection(int device, int index_kind, const uint3
                             wand_image, device_ms);
     } catch (std::bad_alloc const&) {
         return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
     }
 }
 

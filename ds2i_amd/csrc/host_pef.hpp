@@ -148,6 +148,45 @@ inline void seq_write(bitvec_builder& bvb, const uint64_t* v, uint64_t universe,
     }
 }
 
+// ---------------------------------------------------------------- where the base sequences of a list go
+// The sequence writers below write a list's HEADERS themselves and hand every base sequence -- a partition of a partitioned
+// layout, or the whole sequence of an ef / single list -- to a `Bodies` object:
+//   partition(from, to, origin)  seq[from, to) - origin as one base sequence (seq_write) over its last value + 1
+//   whole(universe, n)           seq[0, n) as one base sequence over `universe`              (single)
+//   whole_ef(universe, n)        seq[0, n) as a bare compact_elias_fano / strict_elias_fano   (ef)
+//   size()                       bits of the base sequences so far
+//   append_to(out)               the base sequences go behind `out`
+// written_bodies encodes the values: the host builder. The GPU encoder plans with a Bodies that only sizes them
+// (host_freq_plan.hpp), so the header layout is stated once, here.
+template <bool STRICT>
+struct written_bodies {
+    const uint64_t* seq = nullptr;
+    global_parameters params;
+    bitvec_builder bits;
+    std::vector<uint64_t> rel;
+    explicit written_bodies(global_parameters const& p) : params(p) {}
+    uint64_t size() const { return bits.size(); }
+    void partition(uint64_t from, uint64_t to, uint64_t origin) {
+        rel.resize(to - from);
+        for (uint64_t i = from; i < to; ++i) rel[i - from] = seq[i] - origin;
+        seq_write<STRICT>(bits, rel.data(), rel.back() + 1, to - from, params);
+    }
+    void whole(uint64_t universe, uint64_t n) { seq_write<STRICT>(bits, seq, universe, n, params); }
+    void whole_ef(uint64_t universe, uint64_t n) {
+        if (STRICT) { // strict_elias_fano.hpp:21-36: v_i - i over universe - n + 1, the index's own parameters
+            rel.resize(n);
+            for (uint64_t i = 0; i < n; ++i) rel[i] = seq[i] - i;
+            ef_write(bits, rel.begin(), universe - n + 1, n, params);
+        } else {
+            ef_write(bits, seq, universe, n, params);
+        }
+    }
+    void append_to(bitvec_builder& out) {
+        bv_append(out, bits);
+        bits = bitvec_builder();
+    }
+};
+
 // ---------------------------------------------------------------- optimal partition (approximate DP)
 struct partition_config { double eps1 = 0.03, eps2 = 0.3; uint64_t fix_cost = 64; };
 
@@ -216,59 +255,68 @@ inline std::vector<uint32_t> optimal_partition(const uint64_t* seq, uint64_t uni
 //            partition p-1) - 1 (partition 0: v - first value) over (its last stored value + 1)
 //
 // `ends` = the exclusive end index of every partition (ends.back() == n).
-template <bool STRICT>
+template <bool STRICT, class Bodies>
 inline void write_partition_table(bitvec_builder& out, const uint64_t* seq, uint64_t universe, uint64_t n,
-                                  std::vector<uint32_t> const& ends, bool with_sizes, global_parameters const& params) {
+                                  std::vector<uint32_t> const& ends, bool with_sizes, global_parameters const& params,
+                                  Bodies& bodies) {
     const uint64_t P = ends.size();
     write_gamma_nonzero(out, P);
-    std::vector<uint64_t> rel;
-    // stores seq[from, to) relative to `origin` as one base sequence appended to `dst`
-    auto emit_partition = [&](bitvec_builder& dst, uint64_t from, uint64_t to, uint64_t origin) {
-        rel.resize(to - from);
-        for (uint64_t i = from; i < to; ++i) rel[i - from] = seq[i] - origin;
-        seq_write<STRICT>(dst, rel.data(), rel.back() + 1, to - from, params);
-    };
     if (P == 1) {
         const uint64_t first = seq[0], span = seq[n - 1] - first;
         out.append_bits(first, (unsigned)ceil_log2(universe));
         if (n > 1) write_delta(out, seq[n - 1] + 1 == universe ? 0 : span);
-        emit_partition(out, 0, n, first);
+        bodies.partition(0, n, first);
+        bodies.append_to(out);
         return;
     }
-    bitvec_builder body;
     std::vector<uint64_t> bounds(1, seq[0]), offsets_after, inner_ends(ends.begin(), ends.end());
     for (uint64_t p = 0, from = 0; p < P; from = ends[p++]) {
-        emit_partition(body, from, ends[p], p ? seq[from - 1] + 1 : seq[0]);
-        offsets_after.push_back(body.size());
+        bodies.partition(from, ends[p], p ? seq[from - 1] + 1 : seq[0]);
+        offsets_after.push_back(bodies.size());
         bounds.push_back(seq[ends[p] - 1]);
     }
-    const unsigned endpoint_bits = (unsigned)ceil_log2(body.size() + 1);
+    const unsigned endpoint_bits = (unsigned)ceil_log2(bodies.size() + 1);
     write_gamma(out, endpoint_bits);
     bitvec_builder table;
     if (with_sizes) ef_write(table, inner_ends.begin(), n, P - 1, params);
     ef_write(table, bounds.begin(), universe, P + 1, params);
     bv_append(out, table);
     for (uint64_t p = 0; p + 1 < P; ++p) out.append_bits(offsets_after[p], endpoint_bits);
-    bv_append(out, body);
+    bodies.append_to(out);
 }
 
 // partitioned_sequence: end points from the (1+eps)-approximate shortest path (optimal_partition above)
-template <bool STRICT>
+template <bool STRICT, class Bodies>
 inline void partitioned_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n,
-                              global_parameters const& params, partition_config const& conf = partition_config()) {
+                              global_parameters const& params, Bodies& bodies, partition_config const& conf = partition_config()) {
     auto cost_fun = [&](uint64_t u, uint64_t m) { return seq_bitsize<STRICT>(params, u, m) + conf.fix_cost; };
     write_partition_table<STRICT>(bvb, seq, universe, n, optimal_partition(seq, universe, n, cost_fun, conf.eps1, conf.eps2),
-                                  true, params);
+                                  true, params, bodies);
 }
 
 // uniform_partitioned_sequence: fixed partitions of 2^log_partition_size elements
-template <bool STRICT>
-inline void uniform_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n, global_parameters const& params) {
+template <bool STRICT, class Bodies>
+inline void uniform_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n, global_parameters const& params,
+                          Bodies& bodies) {
     const uint64_t psize = uint64_t(1) << params.log_partition_size;
     std::vector<uint32_t> ends;
     for (uint64_t e = psize; e < n; e += psize) ends.push_back((uint32_t)e);
     ends.push_back((uint32_t)n);
-    write_partition_table<STRICT>(bvb, seq, universe, n, ends, false, params);
+    write_partition_table<STRICT>(bvb, seq, universe, n, ends, false, params, bodies);
+}
+
+// the same two with the values encoded in place (written_bodies)
+template <bool STRICT>
+inline void partitioned_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n, global_parameters const& params) {
+    written_bodies<STRICT> bodies(params);
+    bodies.seq = seq;
+    partitioned_write<STRICT>(bvb, seq, universe, n, params, bodies);
+}
+template <bool STRICT>
+inline void uniform_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n, global_parameters const& params) {
+    written_bodies<STRICT> bodies(params);
+    bodies.seq = seq;
+    uniform_write<STRICT>(bvb, seq, universe, n, params, bodies);
 }
 
 // The four freq_index instantiations of index_types.hpp:18-32; numbered like enum ds2i_hip_index_kind.
@@ -279,26 +327,24 @@ inline void uniform_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t uni
 enum freq_layout : int { LAYOUT_OPT = 5, LAYOUT_EF = 6, LAYOUT_SINGLE = 7, LAYOUT_UNIFORM = 8 };
 inline bool is_freq_layout(int kind) { return kind >= LAYOUT_OPT && kind <= LAYOUT_UNIFORM; }
 
-template <bool STRICT>
+// `bodies` holds the sequence (bodies.seq == seq) and receives its base sequences
+template <bool STRICT, class Bodies>
 inline void layout_write(int layout, bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n,
-                         global_parameters const& params) {
+                         global_parameters const& params, Bodies& bodies) {
     switch (layout) {
-    case LAYOUT_OPT: partitioned_write<STRICT>(bvb, seq, universe, n, params); break;
-    case LAYOUT_UNIFORM: uniform_write<STRICT>(bvb, seq, universe, n, params); break;
-    case LAYOUT_SINGLE: seq_write<STRICT>(bvb, seq, universe, n, params); break;
+    case LAYOUT_OPT: partitioned_write<STRICT>(bvb, seq, universe, n, params, bodies); break;
+    case LAYOUT_UNIFORM: uniform_write<STRICT>(bvb, seq, universe, n, params, bodies); break;
+    case LAYOUT_SINGLE:
+        bodies.whole(universe, n);
+        bodies.append_to(bvb);
+        break;
     case LAYOUT_EF:
-        if (STRICT) { // strict_elias_fano.hpp:21-36: v_i - i over universe - n + 1, the index's own parameters
-            std::vector<uint64_t> shifted(n);
-            for (uint64_t i = 0; i < n; ++i) shifted[i] = seq[i] - i;
-            ef_write(bvb, shifted.begin(), universe - n + 1, n, params);
-        } else {
-            ef_write(bvb, seq, universe, n, params);
-        }
+        bodies.whole_ef(universe, n);
+        bodies.append_to(bvb);
         break;
     default: throw std::invalid_argument("unknown freq_index layout");
     }
 }
-
 // ---------------------------------------------------------------- freq_index<DocsSequence, positive_sequence<...>>
 class opt_index_builder {
 public:
@@ -311,6 +357,16 @@ public:
     static void encode_list(uint64_t num_docs, global_parameters const& params, uint64_t n, const uint32_t* docs,
                             const uint32_t* freqs, bitvec_builder& docs_bits, bitvec_builder& freqs_bits,
                             int layout = LAYOUT_OPT) {
+        written_bodies<false> db(params);
+        written_bodies<true> fb(params);
+        encode_list(num_docs, params, n, docs, freqs, docs_bits, freqs_bits, layout, db, fb);
+    }
+    // ... with the base sequences handed to db (docs) / fb (freqs): docs_bits / freqs_bits receive the headers and what
+    // append_to puts behind them
+    template <class DocsBodies, class FreqsBodies>
+    static void encode_list(uint64_t num_docs, global_parameters const& params, uint64_t n, const uint32_t* docs,
+                            const uint32_t* freqs, bitvec_builder& docs_bits, bitvec_builder& freqs_bits, int layout,
+                            DocsBodies& db, FreqsBodies& fb) {
         if (!n) throw std::invalid_argument("List must be nonempty");
         uint64_t occurrences = 0;
         std::vector<uint64_t> d(n), cum(n);
@@ -319,10 +375,12 @@ public:
             occurrences += freqs[i];
             cum[i] = occurrences; // positive_sequence: strictly increasing prefix sums
         }
+        db.seq = d.data();
+        fb.seq = cum.data();
         write_gamma_nonzero(docs_bits, occurrences);
         if (occurrences > 1) docs_bits.append_bits(n, (unsigned)ceil_log2(occurrences + 1));
-        layout_write<false>(layout, docs_bits, d.data(), num_docs, n, params);
-        layout_write<true>(layout, freqs_bits, cum.data(), occurrences + 1, n, params);
+        layout_write<false>(layout, docs_bits, d.data(), num_docs, n, params, db);
+        layout_write<true>(layout, freqs_bits, cum.data(), occurrences + 1, n, params, fb);
     }
     void add_posting_list(uint64_t n, const uint32_t* docs, const uint32_t* freqs) {
         bitvec_builder db, fb;
@@ -334,6 +392,15 @@ public:
         m_docs_endpoints.push_back(m_docs.size());
         bv_append(m_freqs, fb);
         m_freqs_endpoints.push_back(m_freqs.size());
+    }
+    // all lists at once, already laid out (the GPU encoder): the two bit vectors and, for each, the bit offset at which every
+    // list starts followed by the total (nlists + 1 entries, the first 0)
+    void set_encoded(bitvec_builder&& docs, std::vector<uint64_t>&& docs_endpoints, bitvec_builder&& freqs,
+                     std::vector<uint64_t>&& freqs_endpoints) {
+        m_docs = std::move(docs);
+        m_docs_endpoints = std::move(docs_endpoints);
+        m_freqs = std::move(freqs);
+        m_freqs_endpoints = std::move(freqs_endpoints);
     }
     // image = 5 B params | u64 num_docs | collection(docs) | collection(freqs)
     // collection = u64 m_size | bit_vector m_endpoints | bit_vector m_bitvectors ; bit_vector = u64 bits | u64 nwords | words

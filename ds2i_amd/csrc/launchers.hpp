@@ -55,4 +55,10 @@ hipError_t ds2i_launch_hybrid_plan(const ds2i_dev::EncArgs& a, unsigned grid, hi
 hipError_t ds2i_launch_wand_list_max(const uint32_t* docs, const uint32_t* freqs, const uint64_t* list_in, const uint32_t* blk_list,
                                      const uint32_t* list_blk0, uint32_t nblocks, const float* norm_lens, uint64_t num_docs,
                                      unsigned int* list_max, unsigned max_groups, hipStream_t s);
+// ---- freq_encode_kernels.hip: the Elias-Fano layouts (opt, ef, single, uniform) over the same staging (EncArgs: freqs, list_in and the
+// block tables). prefix_sums: cum[k] = sum of the freqs of k's list up to and including k (blk_base: nblocks words of scratch);
+// write: the base sequences of one side (freqs_side: values from a.cum, else a.docs) ORed into the zero-filled a.out
+hipError_t ds2i_launch_freq_prefix_sums(const ds2i_dev::EncArgs& st, uint64_t nlists, uint64_t* blk_base, uint64_t* cum, unsigned max_groups,
+                                        hipStream_t s);
+hipError_t ds2i_launch_freq_write(int freqs_side, const ds2i_dev::FreqEncArgs& a, unsigned max_groups, hipStream_t s);
 }

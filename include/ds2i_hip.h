@@ -254,10 +254,22 @@ void ds2i_hip_pipeline_destroy(ds2i_hip_pipeline* p);
  * ds2i_build.h release it), byte-identical to the host builder's (ds2i_builder_*). index_kind is DS2I_BLOCK_OPTPFOR,
  * DS2I_BLOCK_VARINT (every full block VarInt-G8IU) or DS2I_BLOCK_INTERPOLATIVE; DS2I_BLOCK_QMX has no GPU encoder and
  * DS2I_BLOCK_MIXED images come from ds2i_hip_hybrid_freeze below: both are DS2I_EINVAL here. device_ms (may be NULL)
- * receives the hipEvent time of the two kernel passes. */
+ * receives the hipEvent time of the kernels the call ran.
+ * The Elias-Fano layouts -- DS2I_OPT, DS2I_EF, DS2I_SINGLE, DS2I_UNIFORM -- are encoded too: the image is the one
+ * ds2i_builder_create(kind, num_docs) / ds2i_builder_add_posting_list x nlists / ds2i_builder_freeze return, byte for
+ * byte, with the default global_parameters (sampling 9 / 8 / 9 / 8, log_partition_size 7). Every size of these layouts
+ * is an integer in closed form of (universe, n), so the host plans -- type, length and final bit offset of every base
+ * sequence, the headers, for DS2I_OPT the partition end points (optimal_partition, list-parallel on at most 16 host
+ * threads) -- and HIP kernels form the prefix sums of the freqs and write every base sequence (Elias-Fano, ranked
+ * bitvector, their sampled arrays) into the two bit vectors, one thread per posting. For these kinds the input is
+ * checked on the host before anything is staged: an empty list ("List must be nonempty"), doc-ids not strictly
+ * increasing or >= num_docs, and a zero freq are DS2I_EINVAL; no output is written on an error. */
 typedef struct ds2i_blob ds2i_blob;
 int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                           const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms);
+/* Diagnostic: the host seconds of this thread's last ds2i_hip_encode_index / ds2i_hip_build_collection of an Elias-Fano kind:
+ * seconds[0] planning (DS2I_OPT: the partition DP), seconds[1] download, headers and freeze. */
+void ds2i_hip_encode_host_seconds(double seconds[2]);
 
 /* wand_data on the GPU (build side; create_wand_data.cpp:8-29, wand_data.hpp:20-52): the image ds2i_wand_create(doc_sizes,
  * num_docs) / ds2i_wand_add_list x nlists / ds2i_wand_freeze of ds2i_build.h return for the same input, byte for byte.
@@ -270,9 +282,10 @@ int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_
 int ds2i_hip_build_wand(int device, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                         const uint32_t* docs, const uint32_t* freqs, ds2i_blob** wand_image, double* device_ms);
 /* Both images of a collection from ONE staging of its postings: everything ds2i_hip_index_open needs. index_image is what
- * ds2i_hip_encode_index(index_kind, ...) returns (same kinds; DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL),
- * wand_image what ds2i_hip_build_wand returns. wand_image may be NULL (doc_sizes may then be NULL too); on an error
- * neither output is written. device_ms (may be NULL): the hipEvent time of the encoder's two passes plus the wand kernel. */
+ * ds2i_hip_encode_index(index_kind, ...) returns (same kinds, the Elias-Fano layouts among them, and the same input
+ * checks; DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL), wand_image what ds2i_hip_build_wand returns. wand_image
+ * may be NULL (doc_sizes may then be NULL too); on an error neither output is written. device_ms (may be NULL): the
+ * hipEvent time of the encoder's kernels plus the wand kernel. */
 int ds2i_hip_build_collection(int device, int index_kind, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists,
                               const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
                               ds2i_blob** index_image, ds2i_blob** wand_image, double* device_ms);
