@@ -60,6 +60,15 @@ class SynthParams(C.Structure):
                 ("topics", C.c_uint32), ("topic_boost", C.c_uint32)]  # correlated terms (0, 0: independent lists)
 
 
+class VerifyReport(C.Structure):
+    """ds2i_hip_verify_report (include/ds2i_hip.h)"""
+    _fields_ = [("what", C.c_int), ("list", C.c_uint64), ("position", C.c_uint64), ("got", C.c_uint64), ("expected", C.c_uint64),
+                ("postings_checked", C.c_uint64)]
+
+
+VERIFY_WHAT = ("ok", "num_docs", "lists", "length", "docid", "freq")
+
+
 def library_path():
     # DS2I_LIB_VARIANT=name loads a diagnostic / A-B build of the same library (ds2i_amd/build.py, DS2I_BUILD_VARIANT)
     variant = os.environ.get("DS2I_LIB_VARIANT", "")
@@ -141,6 +150,11 @@ def lib():
         L.ds2i_hip_build_wand.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_build_collection.argtypes = [C.c_int, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(vp),
                                                 C.POINTER(C.c_double)]
+        L.ds2i_hip_index_verify.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(VerifyReport), C.POINTER(C.c_double)]
+        L.ds2i_hip_verify_collection.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, C.c_uint64, C.c_uint64, vp, vp, vp,
+                                                 C.POINTER(VerifyReport), C.POINTER(C.c_double)]
+        L.ds2i_hip_verify_host_seconds.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_verify_host_seconds.restype = None
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -304,6 +318,23 @@ def gpu_build_collection(num_docs, doc_sizes, lists, codec="block_optpfor", devi
     _check(lib().ds2i_hip_build_collection(device, _codec(codec), _ptr(s), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
                                            C.byref(hi), C.byref(hw), C.byref(ms)))
     return _take_blob(hi), _take_blob(hw), {"device_ms": ms.value}
+
+
+def _verify_result(r, ms):
+    return dict(ok=r.what == 0, what=VERIFY_WHAT[r.what], list=r.list, position=r.position, got=r.got, expected=r.expected,
+                postings_checked=r.postings_checked, device_ms=ms.value)
+
+
+def gpu_verify_collection(kind, image, num_docs, lists, device=0):
+    """An index image checked against the collection it was built from, ON THE GPU (ds2i_hip_verify_collection): every list
+    decoded by the on-disk decoders of `kind` in one launch and compared with `lists` (iterable of (docs, freqs)).
+    Returns dict(ok, what, list, position, got, expected, postings_checked, device_ms); what is "ok" or names the first
+    difference: "num_docs", "lists", "length" (these three are found on the host), "docid", "freq"."""
+    n, offs, docs, freqs = _csr(lists)
+    r, ms = VerifyReport(), C.c_double()
+    _check(lib().ds2i_hip_verify_collection(device, _codec(kind), image, len(image), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
+                                            C.byref(r), C.byref(ms)))
+    return _verify_result(r, ms)
 
 
 def synth_build_gpu(p, device=0, threads=0):
@@ -706,6 +737,14 @@ class Index:
         got = C.c_uint64()
         _check(lib().ds2i_hip_decode_list(self._h, term, _ptr(d), _ptr(f), n, C.byref(got)))
         return d, f
+
+    def verify(self, lists):
+        """This index, as queries read it, against `lists` (iterable of (docs, freqs)) in one launch (ds2i_hip_index_verify);
+        the dict of gpu_verify_collection."""
+        n, offs, docs, freqs = _csr(lists)
+        r, ms = VerifyReport(), C.c_double()
+        _check(lib().ds2i_hip_index_verify(self._h, self.num_docs(), n, _ptr(offs), _ptr(docs), _ptr(freqs), C.byref(r), C.byref(ms)))
+        return _verify_result(r, ms)
 
     def calibration_read(self):
         n = C.c_uint64()

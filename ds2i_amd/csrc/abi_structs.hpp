@@ -282,6 +282,32 @@ struct DecodeArgs {
     const uint32_t* tails;
 };
 
+// Whole-index decode-and-compare (k_verify_index / k_verify_index_side): every block (chunk) of every list of the index against a
+// collection staged in CSR form. Block g of the index belongs to the list l with lists[l].blk_base <= g < lists[l].blk_base +
+// lists[l].nblocks; its posting i is compared with exp_docs / exp_freqs [list_first[l] + (position of the block in its list) + i].
+// The host has compared the list lengths before the launch: list_first[l + 1] - list_first[l] == lists[l].n for every list.
+// first_bad receives (atomicMin; preset to VERIFY_NONE) the smallest key (global posting index << 1) | (1: the doc-id matched and
+// the freq differs) over all differences -- the first one in (list, position) order, doc-id before freq, whatever the scheduling.
+static constexpr unsigned long long VERIFY_NONE = ~0ull;
+struct VerifyArgs {
+    const uint8_t* arena;
+    const uint8_t* bits0;
+    const uint8_t* bits1;
+    const QTerm* lists;        // one per list of the index (ds2i_make_qterm)
+    uint32_t nlists;
+    uint32_t total_blocks;
+    int codec;
+    uint32_t num_docs;
+    const uint32_t* exp_docs;
+    const uint32_t* exp_freqs;
+    const uint64_t* list_first; // nlists + 1 posting offsets of the collection
+    unsigned long long* first_bad;
+    const void* skip;          // k_verify_index_side: as DecodeArgs
+    const uint32_t* xslots;
+    const uint32_t* xovf;
+    const uint32_t* tails;
+};
+
 // wand / maxscore / ranked_or of a ONE-term query are exactly its ranked_and result: copied from the seed pass (k_copy_seed)
 struct CopySeedArgs {
     const uint32_t* queries;

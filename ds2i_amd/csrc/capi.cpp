@@ -45,17 +45,6 @@ namespace {
 
 const float kNegInf = -std::numeric_limits<float>::infinity();
 
-uint32_t host_vbyte(const uint8_t* p, size_t avail, uint32_t& val) {
-    uint32_t v = 0, shift = 0, i = 0;
-    while (i < avail && i < 5) {
-        uint8_t c = p[i++];
-        v += uint32_t(c & 127) << shift;
-        if (c & 128) { val = v; return i; }
-        shift += 7;
-    }
-    return 0;
-}
-
 void free_index(ds2i_hip_index* x) {
     if (!x) return;
     (void)hipSetDevice(x->device);
@@ -674,7 +663,7 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
         const uint8_t* lp = view.lists + view.list_offsets[t];
         const uint64_t len = view.list_offsets[t + 1] - view.list_offsets[t];
         uint32_t n = 0;
-        uint32_t vl = host_vbyte(lp, len, n);
+        uint32_t vl = ds2i_host_vbyte(lp, len, n);
         if (!vl || !n) return ds2i_set_error(DS2I_EFORMAT, "posting list header is corrupt");
         const uint64_t nb = (uint64_t(n) + 127) / 128;
         if (len < vl + 8 * nb - 4) return ds2i_set_error(DS2I_EFORMAT, "posting list shorter than its block tables");
@@ -721,7 +710,7 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
             const uint8_t* lp = view.lists + view.list_offsets[t];
             const uint64_t len = view.list_offsets[t + 1] - view.list_offsets[t];
             uint32_t n = 0;
-            const uint32_t vl = host_vbyte(lp, len, n);
+            const uint32_t vl = ds2i_host_vbyte(lp, len, n);
             const uint64_t nb = x->list_nb[t];
             const uint8_t* maxs = lp + vl;
             const uint8_t* eps = maxs + 4 * nb;
@@ -966,3 +955,7 @@ int ds2i_hip_selftest_scan(int device, const uint32_t* in, uint32_t* out, uint32
 }
 
 } // extern "C"
+
+int ds2i_index_open_bare(int device, int kind, const void* index_image, size_t index_bytes, ds2i_hip_index** out) {
+    return index_open_impl(device, kind, index_image, index_bytes, nullptr, 0, true, ds2i_knobs(), out);
+}

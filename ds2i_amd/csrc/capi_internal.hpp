@@ -150,6 +150,20 @@ struct ds2i_hip_index {
 
 void ds2i_batch_destroy(ds2i_hip_batch* b); // capi_batch.cpp
 
+// vbyte(n) at the head of a block posting list (block_posting_list.hpp:86-90): bytes consumed, 0 = malformed
+static inline uint32_t ds2i_host_vbyte(const uint8_t* p, size_t avail, uint32_t& val) {
+    uint32_t v = 0, shift = 0, i = 0;
+    while (i < avail && i < 5) {
+        uint8_t c = p[i++];
+        v += uint32_t(c & 127) << shift;
+        if (c & 128) { val = v; return i; }
+        shift += 7;
+    }
+    return 0;
+}
+// capi.cpp: the image uploaded as it is -- no tables, no transcoding -- whatever the knobs say (ds2i_hip_index_close releases it)
+int ds2i_index_open_bare(int device, int kind, const void* index_image, size_t index_bytes, ds2i_hip_index** out);
+
 // index[term] as the kernels see it (weights left at 0: they depend on the query)
 static inline ds2i_dev::QTerm ds2i_make_qterm(const ds2i_hip_index* idx, uint32_t term) {
     ds2i_dev::QTerm qt;

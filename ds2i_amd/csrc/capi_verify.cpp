@@ -1,0 +1,242 @@
+// Host side of the index verification (include/ds2i_hip.h: ds2i_hip_index_verify, ds2i_hip_verify_collection): the argument
+// checks, the structure comparison (number of documents, number of lists, list lengths -- on the host, before any device is
+// touched), the staging of the expected postings in CSR form, ONE launch of k_verify_index[_side] (kernels_upload.inc) over every
+// block of every list, and the report of the first difference. The kernel returns one word: the smallest (global posting index,
+// doc-id before freq) that differs; the value the index holds there comes from the single-list decode of that one list.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <vector>
+
+#include "capi_internal.hpp"
+#include "host_index.hpp"
+#include "host_pef.hpp"
+#include "launchers.hpp"
+
+using ds2i_dev::QTerm;
+
+namespace {
+
+struct DevFree { // device temporaries of one function: freed on every path out of it
+    std::vector<void*> p;
+    ~DevFree() { for (void* x : p) if (x) (void)hipFree(x); }
+    template <class T> hipError_t alloc(T** out, size_t bytes) {
+        void* q = nullptr;
+        hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
+        if (e == hipSuccess) p.push_back(q);
+        *out = (T*)q;
+        return e;
+    }
+};
+struct Events {
+    hipEvent_t e[2] = {};
+    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
+};
+
+// seconds of {image parse + structure comparison, bare upload of the image, staging of the expected postings} of this thread's last
+// call (ds2i_hip_verify_host_seconds)
+thread_local double verify_host_s[3] = {0.0, 0.0, 0.0};
+double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+int check_offsets(const char* who, uint64_t nlists, const uint64_t* offs) {
+    if (offs[0] != 0) return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": list_offsets must start at 0").c_str());
+    for (uint64_t t = 0; t < nlists; ++t)
+        if (offs[t + 1] < offs[t]) return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": list_offsets decrease").c_str());
+    return DS2I_OK;
+}
+
+// num_docs, the number of lists, then every list's length: true = a difference, and the report says which
+bool structure_differs(uint64_t idx_num_docs, uint64_t idx_lists, const uint32_t* idx_len, uint64_t num_docs, uint64_t nlists,
+                       const uint64_t* offs, ds2i_hip_verify_report* r) {
+    if (idx_num_docs != num_docs) {
+        r->what = DS2I_VERIFY_NUM_DOCS;
+        r->got = idx_num_docs;
+        r->expected = num_docs;
+        return true;
+    }
+    if (idx_lists != nlists) {
+        r->what = DS2I_VERIFY_LISTS;
+        r->got = idx_lists;
+        r->expected = nlists;
+        return true;
+    }
+    for (uint64_t t = 0; t < nlists; ++t) {
+        const uint64_t n = offs[t + 1] - offs[t];
+        if (idx_len[t] != n) {
+            r->what = DS2I_VERIFY_LENGTH;
+            r->list = t;
+            r->got = idx_len[t];
+            r->expected = n;
+            r->postings_checked = offs[t];
+            return true;
+        }
+    }
+    return false;
+}
+
+// the postings: the lengths agree list by list
+int verify_postings(ds2i_hip_index* idx, const uint64_t* offs, const uint32_t* docs, const uint32_t* freqs, ds2i_hip_verify_report* r,
+                    double* device_ms) {
+    const uint64_t V = idx->size, total = offs[V];
+    r->postings_checked = total;
+    if (!V || !total || !idx->total_blocks) return DS2I_OK;
+    if (idx->total_blocks >= (1ull << 32)) return ds2i_set_error(DS2I_EINVAL, "index verification: more than 2^32 blocks");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_OK(hipSetDevice(idx->device));
+    std::vector<QTerm> lists;
+    try {
+        lists.resize(V);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    }
+    for (uint64_t t = 0; t < V; ++t) lists[t] = ds2i_make_qterm(idx, (uint32_t)t);
+    DevFree dev;
+    Events ev;
+    QTerm* d_lists = nullptr;
+    uint32_t *d_docs = nullptr, *d_freqs = nullptr;
+    uint64_t* d_first = nullptr;
+    unsigned long long* d_bad = nullptr;
+    if (dev.alloc(&d_lists, sizeof(QTerm) * V) != hipSuccess || dev.alloc(&d_docs, 4 * total) != hipSuccess ||
+        dev.alloc(&d_freqs, 4 * total) != hipSuccess || dev.alloc(&d_first, 8 * (V + 1)) != hipSuccess || dev.alloc(&d_bad, 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return ds2i_set_error(DS2I_ENOMEM, "index verification: the collection does not fit beside the index (8 bytes per posting)");
+    }
+    unsigned long long key = ds2i_dev::VERIFY_NONE;
+    HIP_OK(hipMemcpy(d_lists, lists.data(), sizeof(QTerm) * V, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_docs, docs, 4 * total, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_freqs, freqs, 4 * total, hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_first, offs, 8 * (V + 1), hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(d_bad, &key, 8, hipMemcpyHostToDevice));
+    verify_host_s[2] = seconds_since(t0);
+    ds2i_dev::VerifyArgs a{};
+    a.arena = idx->d_arena;
+    a.bits0 = idx->d_bits0;
+    a.bits1 = idx->d_bits1;
+    a.lists = d_lists;
+    a.nlists = (uint32_t)V;
+    a.total_blocks = (uint32_t)idx->total_blocks;
+    a.codec = idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; // every freq_index layout decodes through the chunk directory
+    a.num_docs = (uint32_t)idx->num_docs;
+    a.exp_docs = d_docs;
+    a.exp_freqs = d_freqs;
+    a.list_first = d_first;
+    a.first_bad = d_bad;
+    a.skip = idx->d_skip;
+    a.xslots = idx->d_xslots;
+    a.xovf = idx->d_xovf;
+    a.tails = idx->d_tails;
+    const unsigned grid = (unsigned)std::min<uint64_t>(idx->total_blocks, uint64_t(idx->num_cus) * 16);
+    // block_optpfor with side tables: through the stream kernels' decoder (DS2I_DECODE_GENERAL=1: the general decoders)
+    const bool side = idx->side_tables() && !idx->knobs.decode_general;
+    for (auto& x : ev.e) HIP_OK(hipEventCreate(&x));
+    HIP_OK(hipEventRecord(ev.e[0], idx->stream[0]));
+    HIP_OK(side ? ds2i_launch_verify_index_side(a, grid, idx->stream[0]) : ds2i_launch_verify_index(a, grid, idx->stream[0]));
+    HIP_OK(hipEventRecord(ev.e[1], idx->stream[0]));
+    HIP_OK(hipEventSynchronize(ev.e[1]));
+    float ms = 0.f;
+    HIP_OK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    if (device_ms) *device_ms = ms;
+    HIP_OK(hipMemcpy(&key, d_bad, 8, hipMemcpyDeviceToHost));
+    if (key == ds2i_dev::VERIFY_NONE) return DS2I_OK;
+    const uint64_t at = key >> 1;
+    if (at >= total) return ds2i_set_error(DS2I_EDEVICE, "index verification: the kernel reported a posting outside the collection");
+    const uint64_t t = (uint64_t)(std::upper_bound(offs, offs + V + 1, at) - offs) - 1; // (no list is empty: the lengths agree with the index's)
+    r->what = (key & 1) ? DS2I_VERIFY_FREQ : DS2I_VERIFY_DOCID;
+    r->list = t;
+    r->position = at - offs[t];
+    r->expected = (key & 1) ? freqs[at] : docs[at];
+    r->postings_checked = at;
+    // what the index holds there: the single-list decode of that one list (the same choice of decoder)
+    std::vector<uint32_t> ld, lf;
+    try {
+        ld.resize(idx->list_n[t]);
+        lf.resize(idx->list_n[t]);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    }
+    uint64_t n = 0;
+    const int rc = ds2i_hip_decode_list(idx, (uint32_t)t, ld.data(), lf.data(), ld.size(), &n);
+    if (rc != DS2I_OK) return rc;
+    r->got = (key & 1) ? lf[r->position] : ld[r->position];
+    return DS2I_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ds2i_hip_index_verify(ds2i_hip_index* idx, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs,
+                          const uint32_t* freqs, ds2i_hip_verify_report* report, double* device_ms) {
+    if (!idx || !list_offsets || !docs || !freqs || !report) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_verify: null argument");
+    const int rc = check_offsets("ds2i_hip_index_verify", nlists, list_offsets);
+    if (rc != DS2I_OK) return rc;
+    std::memset(report, 0, sizeof *report);
+    if (device_ms) *device_ms = 0.0;
+    verify_host_s[0] = verify_host_s[1] = verify_host_s[2] = 0.0;
+    if (structure_differs(idx->num_docs, idx->size, idx->list_n.data(), num_docs, nlists, list_offsets, report)) return DS2I_OK;
+    return verify_postings(idx, list_offsets, docs, freqs, report, device_ms);
+}
+
+int ds2i_hip_verify_collection(int device, int index_kind, const void* image, size_t bytes, uint64_t num_docs, uint64_t nlists,
+                               const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs, ds2i_hip_verify_report* report,
+                               double* device_ms) {
+    if (!image || !list_offsets || !docs || !freqs || !report) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_verify_collection: null argument");
+    if (index_kind < DS2I_BLOCK_OPTPFOR || index_kind > DS2I_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_verify_collection: unknown index kind");
+    int rc = check_offsets("ds2i_hip_verify_collection", nlists, list_offsets);
+    if (rc != DS2I_OK) return rc;
+    // ---- the image on the host: its size, num_docs and every list's length
+    verify_host_s[0] = verify_host_s[1] = verify_host_s[2] = 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t img_docs = 0, img_lists = 0;
+    std::vector<uint32_t> img_len;
+    try {
+        if (ds2i_host::is_freq_layout(index_kind)) {
+            ds2i_host::opt_index_view v;
+            v.layout = index_kind;
+            v.parse(image, bytes);
+            img_docs = v.num_docs;
+            img_lists = v.size;
+            img_len.resize(v.size);
+            for (uint64_t t = 0; t < v.size; ++t) img_len[t] = (uint32_t)v.list_length(t);
+        } else {
+            ds2i_host::block_index_view v;
+            v.parse(image, bytes);
+            img_docs = v.num_docs;
+            img_lists = v.size;
+            img_len.resize(v.size);
+            for (uint64_t t = 0; t < v.size; ++t) {
+                uint32_t n = 0;
+                if (!ds2i_host_vbyte(v.lists + v.list_offsets[t], v.list_offsets[t + 1] - v.list_offsets[t], n) || !n)
+                    return ds2i_set_error(DS2I_EFORMAT, "posting list header is corrupt");
+                img_len[t] = n;
+            }
+        }
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    }
+    std::memset(report, 0, sizeof *report);
+    if (device_ms) *device_ms = 0.0;
+    const bool differs = structure_differs(img_docs, img_lists, img_len.data(), num_docs, nlists, list_offsets, report);
+    verify_host_s[0] = seconds_since(t0);
+    if (differs) return DS2I_OK;
+    // ---- the device: a bare upload (no tables, no transcoding), the kernel, close
+    if (device < 0 || device >= ds2i_hip_device_count()) return ds2i_set_error(DS2I_EDEVICE, "ds2i_hip_verify_collection: no such HIP device");
+    ds2i_hip_index* idx = nullptr;
+    const auto t1 = std::chrono::steady_clock::now();
+    rc = ds2i_index_open_bare(device, index_kind, image, bytes, &idx);
+    if (rc != DS2I_OK) return rc;
+    verify_host_s[1] = seconds_since(t1);
+    rc = verify_postings(idx, list_offsets, docs, freqs, report, device_ms);
+    ds2i_hip_index_close(idx);
+    return rc;
+}
+
+void ds2i_hip_verify_host_seconds(double seconds[3]) {
+    if (seconds) std::memcpy(seconds, verify_host_s, sizeof verify_host_s);
+}
+
+} // extern "C"

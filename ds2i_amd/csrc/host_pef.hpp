@@ -684,13 +684,26 @@ struct opt_index_view {
         }
     }
 
-    // flatten list t into its chunk directory
-    void build_dir(uint64_t t, pef_list_dir& dir) const {
-        bit_cursor it{&docs_bits, docs_off[t]};
-        const uint64_t occurrences = read_gamma(it) + 1;
+    // header of list t (freq_index.hpp:192-214): gamma(occurrences - 1), then n; `it` is left at the docs sequence
+    uint64_t list_header(uint64_t t, bit_cursor& it, uint64_t& occurrences) const {
+        it = bit_cursor{&docs_bits, docs_off[t]};
+        occurrences = read_gamma(it) + 1;
         uint64_t n = 1;
         if (occurrences > 1) n = it.take((unsigned)ceil_log2(occurrences + 1));
         if (!n || n > 0xFFFFFFFFull) throw std::runtime_error("corrupt opt posting list header");
+        return n;
+    }
+    uint64_t list_length(uint64_t t) const {
+        bit_cursor it{};
+        uint64_t occurrences = 0;
+        return list_header(t, it, occurrences);
+    }
+
+    // flatten list t into its chunk directory
+    void build_dir(uint64_t t, pef_list_dir& dir) const {
+        bit_cursor it{};
+        uint64_t occurrences = 0;
+        const uint64_t n = list_header(t, it, occurrences);
         std::vector<seq_partition> dp, fp;
         walk_layout<false>(layout, docs_bits, it.pos, num_docs, n, params, dp);
         walk_layout<true>(layout, freqs_bits, freqs_off[t], occurrences + 1, n, params, fp);

@@ -29,51 +29,141 @@ __global__ void __launch_bounds__(64) k_decode_list(DecodeArgs a) {
     cx.flush_stats(a.stats);
 }
 
-// The same through the exception side slots + tail table (block_optpfor with BatchArgs::xslots): the decoder of the stream
-// kernels (optpfor_decode_side), so that every list-decode test of a block_optpfor index exercises it and the tables.
+// Block b of list t of a block_optpfor index through the exception side slots + tail table (BatchArgs::xslots): the decoder of the
+// stream kernels (optpfor_decode_side). Value i of the block's sz postings in lane i & 63: d0 / f0 hold i = lane, d1 / f1
+// i = lane + 64 (absolute doc-ids, freqs). st / xs: STAGE_DW / XSLOT_DW dwords of LDS of the wave.
+struct SideBlock { uint32_t sz, d0, d1, f0, f1; };
+DS2I_DEV SideBlock side_decode_block(const uint8_t* arena, const void* skip, const uint32_t* xslots, const uint32_t* xovf, const uint32_t* tails,
+                                     const QTerm& t, uint32_t b, uint32_t* st, uint32_t* xs) {
+    const uint32_t lane = lane_id();
+    const uint32_t n = t.n, nb = (n + 127u) >> 7;
+    const uint32_t vl = 1u + (n >= (1u << 7)) + (n >= (1u << 14)) + (n >= (1u << 21)) + (n >= (1u << 28));
+    const uint8_t* const data = arena + t.list_off + vl + 4ull * nb + 4ull * (nb - 1);
+    const uint2* const tab = (const uint2*)skip + t.blk_base;
+    const uint32_t sz = ((b + 1) * 128u <= n) ? 128u : (n & 127u);
+    const uint32_t base = b ? tab[b - 1].x + 1u : 0u, ep = b ? tab[b - 1].y : 0u;
+    uint32_t v0, v1, f0, f1;
+    if (sz == 128u) {
+        const uint32_t* const g = (const uint32_t*)(data + ep);
+        const uint32_t* const gx = xslots + (size_t)XSLOT_DW * (t.blk_base + b);
+        st[lane] = g[lane];
+        st[lane + 64] = g[lane + 64];
+        xs[lane] = gx[lane];
+        wave_sync();
+        const SlotHead h = optpfor_slot_head(xs);
+        if (h.flag == 0u) {
+            uint32_t cd, cf;
+            optpfor_decode_pair(st, xs, h, v0, v1, f0, f1, cd, cf);
+        } else {
+            uint32_t nd = 0;
+            const uint32_t cons = optpfor_decode_side(st, STAGE_DW, xs, data + ep, xovf, 0u, 0u, v0, v1, &nd);
+            const uint32_t skip_dw = cons >> 2;
+            optpfor_decode_side(st + skip_dw, skip_dw < STAGE_DW ? STAGE_DW - skip_dw : 0u, xs, data + ep + cons, xovf, 1u, nd, f0, f1);
+        }
+    } else {
+        const uint32_t* const tl = tails + t.aux1;
+        v0 = lane < sz ? tl[lane] : 0u;
+        v1 = lane + 64 < sz ? tl[lane + 64] : 0u;
+        f0 = lane < sz ? tl[sz + lane] : 0u;
+        f1 = lane + 64 < sz ? tl[sz + lane + 64] : 0u;
+    }
+    const uint32_t g0 = (lane < sz) ? v0 + 1u : 0u, g1 = (lane + 64 < sz) ? v1 + 1u : 0u;
+    const uint32_t i0 = wave_incl_scan(g0);
+    const uint32_t i1 = wave_incl_scan(g1) + bcast(i0, 63);
+    return SideBlock{sz, base + i0 - 1u, base + i1 - 1u, f0 + 1u, f1 + 1u};
+}
+
+// k_decode_list through the side slots, so that every list-decode test of a block_optpfor index exercises that decoder and the tables
 __global__ void __launch_bounds__(64) k_decode_list_side(DecodeArgs a) {
     __shared__ uint32_t st[STAGE_DW];
     __shared__ uint32_t xs[XSLOT_DW];
     const uint32_t lane = lane_id();
-    const QTerm t = a.term;
-    const uint32_t n = t.n, nb = (n + 127u) >> 7;
-    const uint32_t vl = 1u + (n >= (1u << 7)) + (n >= (1u << 14)) + (n >= (1u << 21)) + (n >= (1u << 28));
-    const uint8_t* const data = a.arena + t.list_off + vl + 4ull * nb + 4ull * (nb - 1);
-    const uint2* const tab = (const uint2*)a.skip + t.blk_base;
+    const uint32_t nb = (a.term.n + 127u) >> 7;
     for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
-        const uint32_t sz = ((b + 1) * 128u <= n) ? 128u : (n & 127u);
-        const uint32_t base = b ? tab[b - 1].x + 1u : 0u, ep = b ? tab[b - 1].y : 0u;
-        uint32_t v0, v1, f0, f1;
-        if (sz == 128u) {
-            const uint32_t* const g = (const uint32_t*)(data + ep);
-            const uint32_t* const gx = a.xslots + (size_t)XSLOT_DW * (t.blk_base + b);
-            st[lane] = g[lane];
-            st[lane + 64] = g[lane + 64];
-            xs[lane] = gx[lane];
-            wave_sync();
-            const SlotHead h = optpfor_slot_head(xs);
-            if (h.flag == 0u) {
-                uint32_t cd, cf;
-                optpfor_decode_pair(st, xs, h, v0, v1, f0, f1, cd, cf);
-            } else {
-                uint32_t nd = 0;
-                const uint32_t cons = optpfor_decode_side(st, STAGE_DW, xs, data + ep, a.xovf, 0u, 0u, v0, v1, &nd);
-                const uint32_t skip_dw = cons >> 2;
-                optpfor_decode_side(st + skip_dw, skip_dw < STAGE_DW ? STAGE_DW - skip_dw : 0u, xs, data + ep + cons, a.xovf, 1u, nd, f0, f1);
-            }
-        } else {
-            const uint32_t* const tl = a.tails + t.aux1;
-            v0 = lane < sz ? tl[lane] : 0u;
-            v1 = lane + 64 < sz ? tl[lane + 64] : 0u;
-            f0 = lane < sz ? tl[sz + lane] : 0u;
-            f1 = lane + 64 < sz ? tl[sz + lane + 64] : 0u;
-        }
-        const uint32_t g0 = (lane < sz) ? v0 + 1u : 0u, g1 = (lane + 64 < sz) ? v1 + 1u : 0u;
-        const uint32_t i0 = wave_incl_scan(g0);
-        const uint32_t i1 = wave_incl_scan(g1) + bcast(i0, 63);
+        const SideBlock k = side_decode_block(a.arena, a.skip, a.xslots, a.xovf, a.tails, a.term, b, st, xs);
         const size_t gpos = (size_t)b * 128u;
-        if (lane < sz) { a.out_docs[gpos + lane] = base + i0 - 1u; a.out_freqs[gpos + lane] = f0 + 1u; }
-        if (lane + 64 < sz) { a.out_docs[gpos + lane + 64] = base + i1 - 1u; a.out_freqs[gpos + lane + 64] = f1 + 1u; }
+        if (lane < k.sz) { a.out_docs[gpos + lane] = k.d0; a.out_freqs[gpos + lane] = k.f0; }
+        if (lane + 64 < k.sz) { a.out_docs[gpos + lane + 64] = k.d1; a.out_freqs[gpos + lane + 64] = k.f1; }
+        wave_sync();
+    }
+}
+
+// ------------------------------------------------------------------ whole-index verification
+// Every block (chunk) of every list decoded and compared with a collection staged in CSR form (VerifyArgs, abi_structs.hpp): one
+// launch for the whole index, one wave per block, grid-strided over the index-wide block numbers. A wave finds the list of its
+// block in the per-list block prefix (QTerm::blk_base / nblocks) by binary search and rebinds only when the list changes.
+
+// the last list whose blk_base <= g, at or after `lo` (a wave's block numbers only grow; lists[lo].blk_base <= g)
+DS2I_DEV uint32_t verify_list_of(const QTerm* lists, uint32_t nlists, uint32_t g, uint32_t lo) {
+    uint32_t hi = nlists;
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (uniform(lists[mid].blk_base) <= g) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// postings [0, sz) of one decoded block (value i in lane i & 63: d0 / f0 hold i = lane, d1 / f1 i = lane + 64) against the
+// collection's postings from `at` on; the block's first difference, if any, is published
+DS2I_DEV void verify_compare(const VerifyArgs& a, uint64_t at, uint32_t sz, uint32_t d0, uint32_t d1, uint32_t f0, uint32_t f1) {
+    const uint32_t lane = lane_id();
+    uint32_t k0 = 0, k1 = 0; // 0: equal, 1: the doc-id differs, 2: the doc-id matches and the freq differs
+    if (lane < sz) k0 = d0 != a.exp_docs[at + lane] ? 1u : f0 != a.exp_freqs[at + lane] ? 2u : 0u;
+    if (lane + 64 < sz) k1 = d1 != a.exp_docs[at + lane + 64] ? 1u : f1 != a.exp_freqs[at + lane + 64] ? 2u : 0u;
+    const uint64_t m0 = ballot(k0 != 0u), m1 = ballot(k1 != 0u);
+    if (!(m0 | m1)) return;
+    const uint32_t src = (uint32_t)__builtin_ctzll(m0 ? m0 : m1);
+    const uint32_t kind = bcast(m0 ? k0 : k1, src);
+    const unsigned long long key = ((unsigned long long)(at + src + (m0 ? 0u : 64u)) << 1) | (kind == 2u ? 1ull : 0ull);
+    if (lane == 0) atomicMin(a.first_bad, key);
+}
+
+__global__ void __launch_bounds__(64) k_verify_index(VerifyArgs a) {
+    __shared__ Lds<1> L;
+    BatchArgs ba{};
+    ba.arena = a.arena;
+    ba.bits0 = a.bits0;
+    ba.bits1 = a.bits1;
+    ba.codec = a.codec;
+    ba.num_docs = a.num_docs;
+    Ctx cx = make_ctx<-1, MetaLds>(L, ba);
+    const uint32_t lane = lane_id();
+    uint32_t l = 0;
+    unsigned long long base = 0, end = 0, first = 0; // the bound list: its blocks [base, end) and its first posting in the collection
+    for (unsigned long long g = blockIdx.x; g < a.total_blocks; g += gridDim.x) {
+        if (g >= end) {
+            l = verify_list_of(a.lists, a.nlists, (uint32_t)g, l);
+            const QTerm t = a.lists[l];
+            cx.bind(0, t);
+            base = t.blk_base;
+            end = base + t.nblocks;
+            first = a.list_first[l];
+        }
+        cx.decode_docs(0, (uint32_t)(g - base));
+        cx.decode_freqs(0);
+        verify_compare(a, first + cx.m(0, M_GPOS), cx.m(0, M_SIZE), L.docs[0][lane], L.docs[0][lane + 64], L.freqs[0][lane], L.freqs[0][lane + 64]);
+        wave_sync();
+    }
+}
+
+// The same through the exception side slots + tail table (side_decode_block, the decode of k_decode_list_side)
+__global__ void __launch_bounds__(64) k_verify_index_side(VerifyArgs a) {
+    __shared__ uint32_t st[STAGE_DW];
+    __shared__ uint32_t xs[XSLOT_DW];
+    uint32_t l = 0;
+    unsigned long long base = 0, end = 0, first = 0;
+    QTerm t{};
+    for (unsigned long long g = blockIdx.x; g < a.total_blocks; g += gridDim.x) {
+        if (g >= end) {
+            l = verify_list_of(a.lists, a.nlists, (uint32_t)g, l);
+            t = a.lists[l];
+            base = t.blk_base;
+            end = base + t.nblocks;
+            first = a.list_first[l];
+        }
+        const uint32_t b = (uint32_t)(g - base);
+        const SideBlock k = side_decode_block(a.arena, a.skip, a.xslots, a.xovf, a.tails, t, b, st, xs);
+        verify_compare(a, first + (unsigned long long)b * 128u, k.sz, k.d0, k.d1, k.f0, k.f1);
         wave_sync();
     }
 }

@@ -25,6 +25,9 @@ hipError_t ds2i_launch_build_side_tables(const ds2i_dev::SideArgs& a, unsigned g
 hipError_t ds2i_launch_list_top_bmw(const float* bmw, const ds2i_dev::QTerm* lists, uint32_t nlists, float* out, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_decode_list(const ds2i_dev::DecodeArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_decode_list_side(const ds2i_dev::DecodeArgs& a, unsigned grid, hipStream_t s);
+// every block of every list against a staged collection; _side: block_optpfor through the side slots and the tail table
+hipError_t ds2i_launch_verify_index(const ds2i_dev::VerifyArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_verify_index_side(const ds2i_dev::VerifyArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_selftest(const uint32_t* in, uint32_t* out, unsigned blocks, hipStream_t s);
 hipError_t ds2i_launch_selftest_bm25(const uint32_t* freqs, const float* norm_lens, float* out, uint32_t n, hipStream_t s);
 hipError_t ds2i_launch_calib_read(const uint32_t* base, unsigned long long ndw, uint32_t* out, unsigned grid, hipStream_t s);

@@ -312,6 +312,47 @@ struct ds2i_synth_params;
 int ds2i_hip_synth_encode(int device, const struct ds2i_synth_params* p, int threads, ds2i_blob** index_image,
                           ds2i_blob** wand_image, uint64_t* total_postings, double* generate_s, double* device_ms);
 
+/* Verification of an index against the collection it was built from (the last step of the reference's
+ * create_freq_index --check): every list of the index is decoded on the GPU -- ONE launch over all blocks (chunks) of all lists,
+ * one wavefront per block, with the decoders the query and decode paths use -- and every doc-id and freq compared with the
+ * collection, staged once in HBM in the CSR form of ds2i_hip_encode_index. Only the first difference comes back.
+ * The report: `what` says what differs first, in this order: the number of documents, the number of lists, the length of a list
+ * (these three on the host, before any device is touched), then the first posting in (list, position) order whose doc-id
+ * differs, or whose doc-id matches and whose freq differs -- the same answer whatever the scheduling. `got` is what the index
+ * holds, `expected` what the collection holds: DS2I_VERIFY_NUM_DOCS / _LISTS fill got / expected only, _LENGTH fills list and the
+ * two lengths, _DOCID / _FREQ fill all four. postings_checked: the postings before the first difference (all of them when
+ * what == DS2I_VERIFY_OK). device_ms (may be NULL): the hipEvent time of the kernel; 0 when no kernel ran.
+ * The return code is DS2I_OK whenever the comparison ran, difference or not; errors are bad arguments (DS2I_EINVAL: a null
+ * pointer, an unknown kind, list_offsets not starting at 0 or decreasing), a bad image (DS2I_EFORMAT), the device, memory.
+ * The collection is staged whole beside the index: 8 bytes per posting of device memory.
+ * Like the reference's check this is for images a builder wrote: an image's structure is trusted exactly as far as
+ * ds2i_hip_index_open trusts it, and the decoders are not hardened against hostile payload bytes. */
+enum ds2i_hip_verify_what {
+    DS2I_VERIFY_OK = 0,
+    DS2I_VERIFY_NUM_DOCS = 1,
+    DS2I_VERIFY_LISTS = 2,
+    DS2I_VERIFY_LENGTH = 3,
+    DS2I_VERIFY_DOCID = 4,
+    DS2I_VERIFY_FREQ = 5
+};
+typedef struct ds2i_hip_verify_report {
+    int what;
+    uint64_t list, position, got, expected;
+    uint64_t postings_checked;
+} ds2i_hip_verify_report;
+/* The handle as queries read it: the transcoded image when the upload transcoded; block_optpfor with side tables through the
+ * side-slot decoder of the stream kernels, or the general decoders under DS2I_DECODE_GENERAL (the choice ds2i_hip_decode_list makes). */
+int ds2i_hip_index_verify(ds2i_hip_index* idx, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                          const uint32_t* docs, const uint32_t* freqs, ds2i_hip_verify_report* report, double* device_ms);
+/* The caller's bytes with the on-disk decoders of that kind (all nine kinds): the image is parsed on the host, the structure
+ * compared, and only then uploaded bare (no tables, no transcoding), verified by the same kernel and closed. */
+int ds2i_hip_verify_collection(int device, int index_kind, const void* image, size_t bytes, uint64_t num_docs, uint64_t nlists,
+                               const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                               ds2i_hip_verify_report* report, double* device_ms);
+/* Diagnostic: the host seconds of this thread's last verification: seconds[0] the host parse of the image and the structure
+ * comparison (ds2i_hip_verify_collection only), seconds[1] its bare upload (likewise), seconds[2] the staging of the postings. */
+void ds2i_hip_verify_host_seconds(double seconds[3]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
