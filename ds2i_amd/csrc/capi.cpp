@@ -13,15 +13,16 @@
 #include <string>
 #include <vector>
 
-#include "capi_internal.hpp"
+#include <mutex>
+#include <thread>
+
+#include "capi_util.hpp"
 #include "launchers.hpp"
 #include "knobs.hpp"
 #include "../../include/ds2i_build.h"
 #include "host_index.hpp"
+#include "host_parallel.hpp"
 #include "host_pef.hpp"
-#include <atomic>
-#include <mutex>
-#include <thread>
 
 using ds2i_dev::BatchArgs;
 using ds2i_dev::DecodeArgs;
@@ -67,19 +68,6 @@ void free_index(ds2i_hip_index* x) {
     if (x->s_merge) (void)hipStreamDestroy(x->s_merge);
     delete x;
 }
-
-// device temporaries of one function: freed on every path out of it
-struct DevTemps {
-    std::vector<void*> p;
-    ~DevTemps() { for (void* x : p) if (x) (void)hipFree(x); }
-    template <class T> hipError_t alloc(T** out, size_t bytes) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes ? bytes : 4);
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T*)q;
-        return e;
-    }
-};
 
 // Per-block (per-chunk) maximum of bm25::doc_term_weight over the block's postings -- the block-level analogue of
 // wand_data's max_term_weight (wand_data.hpp:40-52), computed ON THE DEVICE with the kernels' own float32 arithmetic:
@@ -558,9 +546,7 @@ static int index_open_transcoded(int device, int kind, const void* index_image, 
 
 int ds2i_hip_index_open(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image,
                         size_t wand_bytes, ds2i_hip_index** out) {
-    if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
-    if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
-    if (device < 0 || device >= ds2i_hip_device_count()) return ds2i_set_error(DS2I_EDEVICE, "ds2i_hip_index_open: no such HIP device");
+    // (the arguments are checked by index_open_impl, which every way in passes first)
     const Ds2iKnobs kn = ds2i_knobs(); // (every upload reads the knobs once: the index that serves the queries carries them)
     const bool transcode = (kind == DS2I_BLOCK_MIXED && !kn.mixed_native) || (kind >= DS2I_OPT && kind <= DS2I_UNIFORM && !kn.pef_native);
     if (transcode) {
@@ -569,32 +555,25 @@ int ds2i_hip_index_open(int device, int kind, const void* index_image, size_t in
     return index_open_impl(device, kind, index_image, index_bytes, wand_image, wand_bytes, false, kn, out);
 }
 
-static int index_open_impl(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, bool bare,
-                           const Ds2iKnobs& kn, ds2i_hip_index** out, size_t budget_base_bytes) {
-    if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
-    if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM)
-        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
-    int ndev = ds2i_hip_device_count();
-    if (device < 0 || device >= ndev) return ds2i_set_error(DS2I_EDEVICE, "ds2i_hip_index_open: no such HIP device");
-    std::unique_ptr<ds2i_hip_index, void (*)(ds2i_hip_index*)> x(new ds2i_hip_index, free_index);
-    x->device = device;
-    x->kind = kind;
-    x->knobs = kn;
-    const bool freq_layout = ds2i_host::is_freq_layout(kind); // opt / ef / single / uniform: freq_index images
-    ds2i_host::block_index_view view;
-    ds2i_host::opt_index_view oview;
-    ds2i_host::wand_view wv;
-    try {
-        oview.layout = kind;
-        if (freq_layout) oview.parse(index_image, index_bytes);
-        else view.parse(index_image, index_bytes);
-        if (wand_image) wv.parse(wand_image, wand_bytes);
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
-    }
-    x->size = freq_layout ? oview.size : view.size;
-    x->num_docs = freq_layout ? oview.num_docs : view.num_docs;
+// ---- an upload in steps (index_open_impl below): parse and stage one of the two layouts on the host, upload, streams, tables.
+// What is staged on the host before anything goes to the device:
+struct OpenStaging {
+    std::vector<uint8_t> arena;       // what d_arena receives (arena_bytes of it)
+    std::vector<uint32_t> skip;       // block indexes: what d_skip receives
+    bool has_bits = false;            // freq_index: its docs / freqs bit vectors (in the caller's image) go up too
+    const uint8_t* bits[2] = {};
+    uint64_t bits_bytes[2] = {0, 0};
+    ds2i_host::wand_view wv;          // the wand image, if there is one (x->has_wand)
+};
+
+// x->size and x->num_docs are known: the wand image is parsed and held against them, the per-list arrays get their size
+static int open_take_wand(ds2i_hip_index* x, const void* wand_image, size_t wand_bytes, ds2i_host::wand_view& wv) {
     if (wand_image) {
+        try {
+            wv.parse(wand_image, wand_bytes);
+        } catch (std::exception const& e) {
+            return ds2i_set_error(DS2I_EFORMAT, e.what());
+        }
         if (wv.num_docs != x->num_docs || wv.num_terms < x->size)
             return ds2i_set_error(DS2I_EFORMAT, "wand data does not match the index (num_docs / terms)");
         x->has_wand = true;
@@ -606,64 +585,41 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
     x->list_end.resize(V);
     x->list_n.resize(V);
     x->list_nb.resize(V);
-    std::vector<uint8_t> arena;
-    if (freq_layout) {
-        // freq_index (opt / ef / single / uniform): the two bit vectors go to HBM unchanged; every list is additionally flattened into a chunk
-        // directory (cmax[] + 12-dword entries) so that the device treats <=128-posting chunks like blocks.
-        x->list_aux0.resize(V);
-        x->list_aux1.resize(V);
-        std::vector<ds2i_host::pef_list_dir> dirs(V);
-        std::atomic<uint64_t> next(0);
-        std::string err;
-        std::mutex mu;
-        auto worker = [&]() {
-            try {
-                for (;;) {
-                    uint64_t t = next.fetch_add(1);
-                    if (t >= V) break;
-                    oview.build_dir(t, dirs[t]);
-                }
-            } catch (std::exception const& e) {
-                std::lock_guard<std::mutex> g(mu);
-                err = e.what();
-            }
-        };
-        unsigned nth = std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-        std::vector<std::thread> pool;
-        for (unsigned i = 0; i < nth; ++i) pool.emplace_back(worker);
-        for (auto& th : pool) th.join();
-        if (!err.empty()) return ds2i_set_error(DS2I_EFORMAT, err.c_str());
-        uint64_t cursor = 0;
-        for (uint64_t t = 0; t < V; ++t) {
-            const uint64_t nch = dirs[t].chunks.size();
-            x->list_off[t] = cursor;                                   // cmax[]
-            x->list_end[t] = (cursor + 4 * nch + 15) & ~uint64_t(15);   // chunk entries
-            cursor = x->list_end[t] + nch * sizeof(ds2i_host::pef_chunk);
-            x->list_n[t] = dirs[t].n;
-            x->list_nb[t] = (uint32_t)nch;
-            x->list_aux0[t] = dirs[t].docs_bit0;
-            x->list_aux1[t] = dirs[t].freqs_bit0;
-        }
-        x->arena_bytes = ((cursor + 15) & ~uint64_t(15)) + 4096;
-        try {
-            arena.assign(x->arena_bytes, 0);
-        } catch (std::bad_alloc const&) {
-            return ds2i_set_error(DS2I_ENOMEM, "out of host memory staging the chunk directory");
-        }
-        for (uint64_t t = 0; t < V; ++t) {
-            std::memcpy(arena.data() + x->list_off[t], dirs[t].cmax.data(), 4 * dirs[t].cmax.size());
-            std::memcpy(arena.data() + x->list_end[t], dirs[t].chunks.data(), dirs[t].chunks.size() * sizeof(ds2i_host::pef_chunk));
-            ds2i_host::pef_list_dir().chunks.swap(dirs[t].chunks);
-        }
-    } else {
-    // Device arena: every list is copied byte-for-byte, shifted by <= 3 pad bytes so that its
-    // block_max / block_endpoint tables (which follow vbyte(n)) are dword aligned in HBM.
+    return DS2I_OK;
+}
+
+// blocks (chunks) are numbered list by list in index order
+static void open_number_blocks(ds2i_hip_index* x) {
+    const uint64_t V = x->size;
+    x->list_blk_base.resize(V);
+    for (uint64_t t = 0; t < V; ++t) {
+        x->list_blk_base[t] = x->total_blocks;
+        x->total_blocks += x->list_nb[t];
+    }
+}
+
+// A block index. Device arena: every list is copied byte-for-byte, shifted by <= 3 pad bytes so that its block_max / block_endpoint
+// tables (which follow vbyte(n)) are dword aligned in HBM. Beside it the interleaved skip table (auxiliary, like the list-offset table):
+// entry b of a list = {block_max[b], byte offset where block b ends inside the list's blocks area}. The probe of find_block_info() that
+// locates a block then also delivers its four table words, which saves the dependent table load of a non-sequential decode.
+static int open_stage_block_index(ds2i_hip_index* x, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, OpenStaging& st) {
+    ds2i_host::block_index_view view;
+    try {
+        view.parse(index_image, index_bytes);
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    }
+    x->size = view.size;
+    x->num_docs = view.num_docs;
+    const int rc = open_take_wand(x, wand_image, wand_bytes, st.wv);
+    if (rc) return rc;
+    const uint64_t V = x->size;
     uint64_t cursor = 0;
     for (uint64_t t = 0; t < V; ++t) {
         const uint8_t* lp = view.lists + view.list_offsets[t];
         const uint64_t len = view.list_offsets[t + 1] - view.list_offsets[t];
         uint32_t n = 0;
-        uint32_t vl = ds2i_host_vbyte(lp, len, n);
+        const uint32_t vl = ds2i_host_vbyte(lp, len, n);
         if (!vl || !n) return ds2i_set_error(DS2I_EFORMAT, "posting list header is corrupt");
         const uint64_t nb = (uint64_t(n) + 127) / 128;
         if (len < vl + 8 * nb - 4) return ds2i_set_error(DS2I_EFORMAT, "posting list shorter than its block tables");
@@ -677,68 +633,119 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
     }
     x->arena_bytes = ((cursor + 3) & ~uint64_t(3)) + 4096; // zero slack: decoders may over-read
     try {
-        arena.assign(x->arena_bytes, 0);
+        st.arena.assign(x->arena_bytes, 0);
     } catch (std::bad_alloc const&) {
         return ds2i_set_error(DS2I_ENOMEM, "out of host memory staging the index");
     }
     for (uint64_t t = 0; t < V; ++t)
-        std::memcpy(arena.data() + x->list_off[t], view.lists + view.list_offsets[t],
-                    view.list_offsets[t + 1] - view.list_offsets[t]);
+        std::memcpy(st.arena.data() + x->list_off[t], view.lists + view.list_offsets[t], view.list_offsets[t + 1] - view.list_offsets[t]);
+    open_number_blocks(x);
+    try {
+        st.skip.resize(2 * x->total_blocks);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory staging the skip table");
     }
-    x->list_blk_base.resize(V);
-    for (uint64_t t = 0; t < V; ++t) { // blocks (chunks) are numbered list by list in index order
-        x->list_blk_base[t] = x->total_blocks;
-        x->total_blocks += x->list_nb[t];
+    for (uint64_t t = 0; t < V; ++t) {
+        const uint8_t* lp = view.lists + view.list_offsets[t];
+        const uint64_t len = view.list_offsets[t + 1] - view.list_offsets[t];
+        uint32_t n = 0;
+        const uint32_t vl = ds2i_host_vbyte(lp, len, n);
+        const uint64_t nb = x->list_nb[t];
+        const uint8_t* maxs = lp + vl;
+        const uint8_t* eps = maxs + 4 * nb;
+        const uint64_t data_len = len - vl - (8 * nb - 4);
+        uint32_t* out = st.skip.data() + 2 * x->list_blk_base[t];
+        for (uint64_t b = 0; b < nb; ++b) {
+            uint32_t mx, ep = (uint32_t)data_len;
+            std::memcpy(&mx, maxs + 4 * b, 4);
+            if (b + 1 < nb) std::memcpy(&ep, eps + 4 * b, 4);
+            out[2 * b] = mx;
+            out[2 * b + 1] = ep;
+        }
     }
-    HIP_OK(hipSetDevice(device));
+    return DS2I_OK;
+}
+
+// A freq_index (opt / ef / single / uniform): the two bit vectors go to HBM unchanged; every list is additionally flattened into a chunk
+// directory (cmax[] + 12-dword entries), which is this kind's arena, so that the device treats <=128-posting chunks like blocks.
+static int open_stage_freq_index(ds2i_hip_index* x, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, OpenStaging& st) {
+    ds2i_host::opt_index_view oview;
+    try {
+        oview.layout = x->kind;
+        oview.parse(index_image, index_bytes);
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    }
+    x->size = oview.size;
+    x->num_docs = oview.num_docs;
+    const int rc = open_take_wand(x, wand_image, wand_bytes, st.wv);
+    if (rc) return rc;
+    st.has_bits = true;
+    st.bits[0] = oview.docs_bits.bytes;
+    st.bits[1] = oview.freqs_bits.bytes;
+    st.bits_bytes[0] = oview.docs_bits.nbytes;
+    st.bits_bytes[1] = oview.freqs_bits.nbytes;
+    const uint64_t V = x->size;
+    x->list_aux0.resize(V);
+    x->list_aux1.resize(V);
+    std::vector<ds2i_host::pef_list_dir> dirs(V);
+    try {
+        ds2i_host::parallel_for(V, std::max(1u, std::min(64u, std::thread::hardware_concurrency())), [&](uint64_t t, unsigned) { oview.build_dir(t, dirs[t]); });
+    } catch (std::exception const& e) {
+        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    }
+    uint64_t cursor = 0;
+    for (uint64_t t = 0; t < V; ++t) {
+        const uint64_t nch = dirs[t].chunks.size();
+        x->list_off[t] = cursor;                                   // cmax[]
+        x->list_end[t] = (cursor + 4 * nch + 15) & ~uint64_t(15);   // chunk entries
+        cursor = x->list_end[t] + nch * sizeof(ds2i_host::pef_chunk);
+        x->list_n[t] = dirs[t].n;
+        x->list_nb[t] = (uint32_t)nch;
+        x->list_aux0[t] = dirs[t].docs_bit0;
+        x->list_aux1[t] = dirs[t].freqs_bit0;
+    }
+    x->arena_bytes = ((cursor + 15) & ~uint64_t(15)) + 4096;
+    try {
+        st.arena.assign(x->arena_bytes, 0);
+    } catch (std::bad_alloc const&) {
+        return ds2i_set_error(DS2I_ENOMEM, "out of host memory staging the chunk directory");
+    }
+    for (uint64_t t = 0; t < V; ++t) {
+        std::memcpy(st.arena.data() + x->list_off[t], dirs[t].cmax.data(), 4 * dirs[t].cmax.size());
+        std::memcpy(st.arena.data() + x->list_end[t], dirs[t].chunks.data(), dirs[t].chunks.size() * sizeof(ds2i_host::pef_chunk));
+        ds2i_host::pef_list_dir().chunks.swap(dirs[t].chunks);
+    }
+    open_number_blocks(x);
+    return DS2I_OK;
+}
+
+// the device's copy: the arena, then what the layout staged beside it -- the skip table (a block index) or the two bit vectors (a
+// freq_index), never both -- then norm_lens
+static int open_upload(ds2i_hip_index* x, const OpenStaging& st) {
+    HIP_OK(hipSetDevice(x->device));
     hipDeviceProp_t prop;
-    HIP_OK(hipGetDeviceProperties(&prop, device));
+    HIP_OK(hipGetDeviceProperties(&prop, x->device));
     x->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     HIP_OK(hipMalloc((void**)&x->d_arena, x->arena_bytes));
-    HIP_OK(hipMemcpy(x->d_arena, arena.data(), x->arena_bytes, hipMemcpyHostToDevice));
-    if (!freq_layout && x->total_blocks) {
-        // Interleaved skip table (auxiliary, like the list-offset table): entry b of a list = {block_max[b], byte offset
-        // where block b ends inside the list's blocks area}. The probe of find_block_info() that locates a block then
-        // also delivers its four table words, which saves the dependent table load of a non-sequential decode.
-        std::vector<uint32_t> skip;
-        try {
-            skip.resize(2 * x->total_blocks);
-        } catch (std::bad_alloc const&) {
-            return ds2i_set_error(DS2I_ENOMEM, "out of host memory staging the skip table");
-        }
-        for (uint64_t t = 0; t < V; ++t) {
-            const uint8_t* lp = view.lists + view.list_offsets[t];
-            const uint64_t len = view.list_offsets[t + 1] - view.list_offsets[t];
-            uint32_t n = 0;
-            const uint32_t vl = ds2i_host_vbyte(lp, len, n);
-            const uint64_t nb = x->list_nb[t];
-            const uint8_t* maxs = lp + vl;
-            const uint8_t* eps = maxs + 4 * nb;
-            const uint64_t data_len = len - vl - (8 * nb - 4);
-            uint32_t* out = skip.data() + 2 * x->list_blk_base[t];
-            for (uint64_t b = 0; b < nb; ++b) {
-                uint32_t mx, ep = (uint32_t)data_len;
-                std::memcpy(&mx, maxs + 4 * b, 4);
-                if (b + 1 < nb) std::memcpy(&ep, eps + 4 * b, 4);
-                out[2 * b] = mx;
-                out[2 * b + 1] = ep;
-            }
-        }
+    HIP_OK(hipMemcpy(x->d_arena, st.arena.data(), x->arena_bytes, hipMemcpyHostToDevice));
+    if (!st.skip.empty()) {
         HIP_OK(hipMalloc((void**)&x->d_skip, 8 * x->total_blocks));
-        HIP_OK(hipMemcpy(x->d_skip, skip.data(), 8 * x->total_blocks, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(x->d_skip, st.skip.data(), 8 * x->total_blocks, hipMemcpyHostToDevice));
         x->extra_bytes += 8 * x->total_blocks;
     }
-    if (freq_layout) {
-        const uint64_t b0 = oview.docs_bits.nbytes, b1 = oview.freqs_bits.nbytes;
+    if (st.has_bits) {
+        const uint64_t b0 = st.bits_bytes[0], b1 = st.bits_bytes[1];
         HIP_OK(hipMalloc((void**)&x->d_bits0, b0 + 4096));
         HIP_OK(hipMalloc((void**)&x->d_bits1, b1 + 4096));
         HIP_OK(hipMemset(x->d_bits0 + b0, 0, 4096));
         HIP_OK(hipMemset(x->d_bits1 + b1, 0, 4096));
-        HIP_OK(hipMemcpy(x->d_bits0, oview.docs_bits.bytes, b0, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(x->d_bits1, oview.freqs_bits.bytes, b1, hipMemcpyHostToDevice));
-        x->extra_bytes = b0 + b1 + 8192;
+        HIP_OK(hipMemcpy(x->d_bits0, st.bits[0], b0, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(x->d_bits1, st.bits[1], b1, hipMemcpyHostToDevice));
+        x->extra_bytes = b0 + b1 + 8192; // (assigned: nothing was counted before, a freq_index has no skip table)
     }
     if (x->has_wand) {
+        const ds2i_host::wand_view& wv = st.wv;
         HIP_OK(hipMalloc((void**)&x->d_norm_lens, 4 * (wv.num_docs + 1)));
         HIP_OK(hipMemcpy(x->d_norm_lens, wv.norm_lens, 4 * wv.num_docs, hipMemcpyHostToDevice));
         float mn = std::numeric_limits<float>::infinity();
@@ -750,33 +757,62 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
         x->min_norm_len = wv.num_docs && mn >= 0.f ? mn : 0.f; // 0 is a valid lower bound for any collection
     }
     HIP_OK(hipMalloc((void**)&x->d_ticket, 64 * sizeof(unsigned int)));
-    {
-        // One stream per class, all of ONE priority. Rounds 2-4 gave the many-list classes a higher queue priority than the <=2-list
-        // flood; with the stream kernels what the priorities do turned out to depend on the history of the process (an index
-        // uploaded after another one had been closed -- every transcoding upload -- ran 18 % slower): equal priorities since round 5.
-        int lo_pri = 0, hi_pri = 0; // numerically lower = higher priority
-        HIP_OK(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
-        for (int c = 0; c < NCLS; ++c) HIP_OK(hipStreamCreateWithPriority(&x->stream[c], hipStreamNonBlocking, (lo_pri + hi_pri) / 2));
-    }
+    return DS2I_OK;
+}
+
+// One stream per class, all of ONE priority. Rounds 2-4 gave the many-list classes a higher queue priority than the <=2-list
+// flood; with the stream kernels what the priorities do turned out to depend on the history of the process (an index
+// uploaded after another one had been closed -- every transcoding upload -- ran 18 % slower): equal priorities since round 5.
+static int open_create_streams(ds2i_hip_index* x) {
+    int lo_pri = 0, hi_pri = 0; // numerically lower = higher priority
+    HIP_OK(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
+    for (int c = 0; c < NCLS; ++c) HIP_OK(hipStreamCreateWithPriority(&x->stream[c], hipStreamNonBlocking, (lo_pri + hi_pri) / 2));
     HIP_OK(hipStreamCreateWithFlags(&x->s_up, hipStreamNonBlocking));
     HIP_OK(hipStreamCreateWithFlags(&x->s_merge, hipStreamNonBlocking));
-    if (!bare) choose_table_plan(x.get(), budget_base_bytes ? budget_base_bytes : index_bytes);
+    return DS2I_OK;
+}
+
+// what the upload builds beside the image (nothing for a bare one), then every term as the planner copies it
+static int open_build_tables(ds2i_hip_index* x, bool bare, size_t budget_base_bytes) {
+    if (!bare) choose_table_plan(x, budget_base_bytes);
     else x->plan_g = 0, x->plan_hints = x->plan_slots = false;
-    if (!bare && x->has_wand && x->total_blocks && x->total_blocks < (1ull << 32) && !kn.no_bmw) {
-        int rc = build_block_max_weights(x.get());
+    if (!bare && x->has_wand && x->total_blocks && x->total_blocks < (1ull << 32) && !x->knobs.no_bmw) {
+        int rc = build_block_max_weights(x);
         if (rc) return rc;
     }
-    if (!bare && kind == DS2I_BLOCK_OPTPFOR) {
-        int rc = build_side_tables(x.get());
+    if (!bare && x->kind == DS2I_BLOCK_OPTPFOR) {
+        int rc = build_side_tables(x);
         if (rc) return rc;
     }
+    const uint64_t V = x->size;
     x->term_proto.resize(V);
     for (uint64_t t = 0; t < V; ++t) {
-        QTerm qt = ds2i_make_qterm(x.get(), (uint32_t)t);
+        QTerm qt = ds2i_make_qterm(x, (uint32_t)t);
         qt.q_weight = x->has_wand ? x->max_term_weight[t] : 0.f;
         qt.max_weight = x->d_bmw ? x->list_bmw[t] : 0.f;
         x->term_proto[t] = qt;
     }
+    return DS2I_OK;
+}
+
+// Every way in passes here first (ds2i_hip_index_open directly or through index_open_transcoded, ds2i_index_open_bare): the arguments
+// are checked here and nowhere else.
+static int index_open_impl(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, bool bare,
+                           const Ds2iKnobs& kn, ds2i_hip_index** out, size_t budget_base_bytes) {
+    if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
+    if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
+    int rc = check_device("ds2i_hip_index_open", device);
+    if (rc) return rc;
+    std::unique_ptr<ds2i_hip_index, void (*)(ds2i_hip_index*)> x(new ds2i_hip_index, free_index);
+    x->device = device;
+    x->kind = kind;
+    x->knobs = kn;
+    OpenStaging st;
+    rc = (ds2i_host::is_freq_layout(kind) ? open_stage_freq_index : open_stage_block_index)(x.get(), index_image, index_bytes, wand_image, wand_bytes, st);
+    if (rc) return rc;
+    if ((rc = open_upload(x.get(), st))) return rc;
+    if ((rc = open_create_streams(x.get()))) return rc;
+    if ((rc = open_build_tables(x.get(), bare, budget_base_bytes ? budget_base_bytes : index_bytes))) return rc;
     *out = x.release();
     return DS2I_OK;
 }

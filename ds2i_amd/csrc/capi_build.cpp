@@ -2,7 +2,6 @@
 #include <atomic>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
 
@@ -14,6 +13,7 @@
 #include "host_index.hpp"
 #include "host_pef.hpp"
 #include "host_hybrid.hpp"
+#include "host_parallel.hpp"
 #include "host_synth.hpp"
 
 using namespace ds2i_host;
@@ -26,22 +26,6 @@ struct ds2i_wand_builder {
     std::vector<float> norm_lens, max_w;
 };
 
-namespace {
-synth_params to_params(const ds2i_synth_params* p) {
-    synth_params s;
-    s.seed = p->seed; s.num_docs = p->num_docs; s.num_terms = p->num_terms; s.zipf_exp = p->zipf_exp;
-    s.top_df_frac = p->top_df_frac; s.min_len = p->min_len; s.clustered_every = p->clustered_every;
-    s.topics = p->topics; s.topic_boost = p->topic_boost;
-    return s;
-}
-} // namespace
-
-#define DS2I_TRY try {
-#define DS2I_CATCH                                                                       \
-    } catch (std::bad_alloc const&) { return ds2i_set_error(-7, "out of memory"); }     \
-    catch (std::invalid_argument const& e) { return ds2i_set_error(-1, e.what()); }      \
-    catch (std::exception const& e) { return ds2i_set_error(-2, e.what()); }
-
 extern "C" {
 
 const uint8_t* ds2i_blob_data(const ds2i_blob* b) { return b ? b->data.data() : nullptr; }
@@ -49,7 +33,7 @@ size_t ds2i_blob_size(const ds2i_blob* b) { return b ? b->data.size() : 0; }
 void ds2i_blob_free(ds2i_blob* b) { delete b; }
 
 int ds2i_builder_create(int codec, uint64_t num_docs, ds2i_builder** out) {
-    if (!out || codec < 0 || codec > LAYOUT_UNIFORM) return ds2i_set_error(-1, "ds2i_builder_create: bad argument");
+    if (!out || codec < 0 || codec > LAYOUT_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_builder_create: bad argument");
     DS2I_TRY
     auto* h = new ds2i_builder;
     if (is_freq_layout(codec)) h->opt.reset(new opt_index_builder(num_docs, global_parameters(), codec));
@@ -59,7 +43,7 @@ int ds2i_builder_create(int codec, uint64_t num_docs, ds2i_builder** out) {
     DS2I_CATCH
 }
 int ds2i_builder_add_posting_list(ds2i_builder* b, uint64_t n, const uint32_t* docs, const uint32_t* freqs) {
-    if (!b || !docs || !freqs) return ds2i_set_error(-1, "ds2i_builder_add_posting_list: null argument");
+    if (!b || !docs || !freqs) return ds2i_set_error(DS2I_EINVAL, "ds2i_builder_add_posting_list: null argument");
     DS2I_TRY
     if (b->opt) b->opt->add_posting_list(n, docs, freqs);
     else b->b->add_posting_list(n, docs, freqs);
@@ -67,7 +51,7 @@ int ds2i_builder_add_posting_list(ds2i_builder* b, uint64_t n, const uint32_t* d
     DS2I_CATCH
 }
 int ds2i_builder_freeze(ds2i_builder* b, ds2i_blob** image) {
-    if (!b || !image) return ds2i_set_error(-1, "ds2i_builder_freeze: null argument");
+    if (!b || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_builder_freeze: null argument");
     DS2I_TRY
     auto* blob = new ds2i_blob;
     if (b->opt) b->opt->freeze(blob->data);
@@ -79,7 +63,7 @@ int ds2i_builder_freeze(ds2i_builder* b, ds2i_blob** image) {
 void ds2i_builder_free(ds2i_builder* b) { delete b; }
 
 int ds2i_wand_create(const uint32_t* doc_sizes, uint64_t num_docs, ds2i_wand_builder** out) {
-    if (!doc_sizes || !out || !num_docs) return ds2i_set_error(-1, "ds2i_wand_create: bad argument");
+    if (!doc_sizes || !out || !num_docs) return ds2i_set_error(DS2I_EINVAL, "ds2i_wand_create: bad argument");
     DS2I_TRY
     auto* w = new ds2i_wand_builder;
     compute_norm_lens(doc_sizes, num_docs, w->norm_lens);
@@ -88,14 +72,14 @@ int ds2i_wand_create(const uint32_t* doc_sizes, uint64_t num_docs, ds2i_wand_bui
     DS2I_CATCH
 }
 int ds2i_wand_add_list(ds2i_wand_builder* w, uint64_t n, const uint32_t* docs, const uint32_t* freqs) {
-    if (!w || !docs || !freqs) return ds2i_set_error(-1, "ds2i_wand_add_list: null argument");
+    if (!w || !docs || !freqs) return ds2i_set_error(DS2I_EINVAL, "ds2i_wand_add_list: null argument");
     for (uint64_t i = 0; i < n; ++i)
-        if (docs[i] >= w->norm_lens.size()) return ds2i_set_error(-1, "ds2i_wand_add_list: doc id out of range");
+        if (docs[i] >= w->norm_lens.size()) return ds2i_set_error(DS2I_EINVAL, "ds2i_wand_add_list: doc id out of range");
     w->max_w.push_back(list_max_weight(w->norm_lens.data(), n, docs, freqs));
     return 0;
 }
 int ds2i_wand_freeze(ds2i_wand_builder* w, ds2i_blob** image) {
-    if (!w || !image) return ds2i_set_error(-1, "ds2i_wand_freeze: null argument");
+    if (!w || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_wand_freeze: null argument");
     DS2I_TRY
     auto* blob = new ds2i_blob;
     wand_freeze(w->norm_lens, w->max_w, blob->data);
@@ -106,7 +90,7 @@ int ds2i_wand_freeze(ds2i_wand_builder* w, ds2i_blob** image) {
 void ds2i_wand_free(ds2i_wand_builder* w) { delete w; }
 
 int ds2i_encode_block(int codec, const uint32_t* values, uint32_t sum, uint32_t n, ds2i_blob** out) {
-    if (!values || !out || n == 0 || n > BLOCK) return ds2i_set_error(-1, "ds2i_encode_block: bad argument");
+    if (!values || !out || n == 0 || n > BLOCK) return ds2i_set_error(DS2I_EINVAL, "ds2i_encode_block: bad argument");
     DS2I_TRY
     auto* blob = new ds2i_blob;
     block_encode(codec, values, sum, n, blob->data);
@@ -117,19 +101,19 @@ int ds2i_encode_block(int codec, const uint32_t* values, uint32_t sum, uint32_t 
 // the host half of the BM25 scorer exactly as the query path uses it (query weights in plan_batch, max_term_weight in
 // the wand builder); element-wise so that tests can hold it against the reference's bm25.hpp
 int ds2i_bm25_query_term_weight(const uint64_t* qtf, const uint64_t* df, uint64_t num_docs, uint64_t n, float* out) {
-    if (!qtf || !df || !out) return ds2i_set_error(-1, "ds2i_bm25_query_term_weight: null argument");
+    if (!qtf || !df || !out) return ds2i_set_error(DS2I_EINVAL, "ds2i_bm25_query_term_weight: null argument");
     for (uint64_t i = 0; i < n; ++i) out[i] = ds2i_host::bm25::query_term_weight(qtf[i], df[i], num_docs);
     return 0;
 }
 int ds2i_bm25_doc_term_weight(const uint64_t* freq, const float* norm_len, uint64_t n, float* out) {
-    if (!freq || !norm_len || !out) return ds2i_set_error(-1, "ds2i_bm25_doc_term_weight: null argument");
+    if (!freq || !norm_len || !out) return ds2i_set_error(DS2I_EINVAL, "ds2i_bm25_doc_term_weight: null argument");
     for (uint64_t i = 0; i < n; ++i) out[i] = ds2i_host::bm25::doc_term_weight(freq[i], norm_len[i]);
     return 0;
 }
 
 int ds2i_write_sequence(int seq_kind, const uint64_t* values, uint64_t n, uint64_t universe, const uint8_t params[5],
                         ds2i_blob** bits, uint64_t* nbits) {
-    if (!values || !bits || !nbits || !n) return ds2i_set_error(-1, "ds2i_write_sequence: bad argument");
+    if (!values || !bits || !nbits || !n) return ds2i_set_error(DS2I_EINVAL, "ds2i_write_sequence: bad argument");
     DS2I_TRY
     ds2i_host::global_parameters gp;
     if (params) {
@@ -149,7 +133,7 @@ int ds2i_write_sequence(int seq_kind, const uint64_t* values, uint64_t n, uint64
     case DS2I_SEQ_PARTITIONED_STRICT: ds2i_host::partitioned_write<true>(bvb, values, universe, n, gp); break;
     case DS2I_SEQ_UNIFORM_INDEXED: ds2i_host::uniform_write<false>(bvb, values, universe, n, gp); break;
     case DS2I_SEQ_UNIFORM_STRICT: ds2i_host::uniform_write<true>(bvb, values, universe, n, gp); break;
-    default: return ds2i_set_error(-1, "ds2i_write_sequence: unknown sequence kind");
+    default: return ds2i_set_error(DS2I_EINVAL, "ds2i_write_sequence: unknown sequence kind");
     }
     auto* blob = new ds2i_blob;
     const uint8_t* w = (const uint8_t*)bvb.words().data();
@@ -161,14 +145,14 @@ int ds2i_write_sequence(int seq_kind, const uint64_t* values, uint64_t n, uint64
 }
 
 int ds2i_encode_vbyte(uint32_t value, ds2i_blob** out) {
-    if (!out) return ds2i_set_error(-1, "ds2i_encode_vbyte: null argument");
+    if (!out) return ds2i_set_error(DS2I_EINVAL, "ds2i_encode_vbyte: null argument");
     auto* blob = new ds2i_blob;
     vbyte_encode(value, blob->data);
     *out = blob;
     return 0;
 }
 int ds2i_encode_posting_list(int codec, uint32_t n, const uint32_t* docs, const uint32_t* freqs, ds2i_blob** out) {
-    if (!docs || !freqs || !out || !n) return ds2i_set_error(-1, "ds2i_encode_posting_list: bad argument");
+    if (!docs || !freqs || !out || !n) return ds2i_set_error(DS2I_EINVAL, "ds2i_encode_posting_list: bad argument");
     DS2I_TRY
     auto* blob = new ds2i_blob;
     write_posting_list(codec, blob->data, n, docs, freqs);
@@ -184,12 +168,12 @@ int ds2i_opt_list_directory(const void* opt_image, size_t bytes, uint32_t term, 
 int ds2i_freq_list_directory(int kind, const void* opt_image, size_t bytes, uint32_t term, ds2i_blob** cmax,
                              ds2i_blob** chunks, uint64_t info[5]) {
     if (!opt_image || !cmax || !chunks || !info || !is_freq_layout(kind))
-        return ds2i_set_error(-1, "ds2i_freq_list_directory: bad argument");
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_freq_list_directory: bad argument");
     DS2I_TRY
     opt_index_view v;
     v.layout = kind;
     v.parse(opt_image, bytes);
-    if (term >= v.size) return ds2i_set_error(-3, "term id out of range");
+    if (term >= v.size) return ds2i_set_error(DS2I_ETERM, "term id out of range");
     pef_list_dir dir;
     v.build_dir(term, dir);
     auto* bc = new ds2i_blob;
@@ -215,19 +199,19 @@ uint64_t ds2i_synth_list_upper_bound(const ds2i_synth_params* p, uint32_t term) 
 }
 int ds2i_synth_list(const ds2i_synth_params* p, uint32_t term, uint32_t* docs, uint32_t* freqs, uint64_t capacity,
                     uint64_t* n) {
-    if (!p || !docs || !freqs || !n) return ds2i_set_error(-1, "ds2i_synth_list: null argument");
+    if (!p || !docs || !freqs || !n) return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_list: null argument");
     DS2I_TRY
     std::vector<uint32_t> d, f;
     uint64_t len = synth_list(to_params(p), term, d, f);
     *n = len;
-    if (len > capacity) return ds2i_set_error(-1, "ds2i_synth_list: capacity too small");
+    if (len > capacity) return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_list: capacity too small");
     std::memcpy(docs, d.data(), 4 * len);
     std::memcpy(freqs, f.data(), 4 * len);
     return 0;
     DS2I_CATCH
 }
 int ds2i_synth_doc_sizes(const ds2i_synth_params* p, uint32_t* sizes) {
-    if (!p || !sizes) return ds2i_set_error(-1, "ds2i_synth_doc_sizes: null argument");
+    if (!p || !sizes) return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_doc_sizes: null argument");
     DS2I_TRY
     std::vector<uint32_t> s;
     synth_doc_sizes(to_params(p), s);
@@ -236,7 +220,7 @@ int ds2i_synth_doc_sizes(const ds2i_synth_params* p, uint32_t* sizes) {
     DS2I_CATCH
 }
 int ds2i_synth_queries(uint64_t seed, uint32_t num_terms, uint32_t nq, uint32_t* terms, uint32_t* offsets) {
-    if (!terms || !offsets || !num_terms) return ds2i_set_error(-1, "ds2i_synth_queries: bad argument");
+    if (!terms || !offsets || !num_terms) return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_queries: bad argument");
     DS2I_TRY
     std::vector<uint32_t> t, o;
     synth_queries(seed, num_terms, nq, t, o);
@@ -247,7 +231,7 @@ int ds2i_synth_queries(uint64_t seed, uint32_t num_terms, uint32_t nq, uint32_t*
 }
 
 int ds2i_synth_queries_topical(const ds2i_synth_params* pp, uint64_t seed, uint32_t nq, uint32_t same_topic_pct, uint32_t* terms, uint32_t* offsets) {
-    if (!pp || !terms || !offsets || !pp->num_terms) return ds2i_set_error(-1, "ds2i_synth_queries_topical: bad argument");
+    if (!pp || !terms || !offsets || !pp->num_terms) return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_queries_topical: bad argument");
     DS2I_TRY
     std::vector<uint32_t> t, o;
     synth_queries_topical(to_params(pp), seed, nq, same_topic_pct, t, o);
@@ -259,7 +243,7 @@ int ds2i_synth_queries_topical(const ds2i_synth_params* pp, uint64_t seed, uint3
 
 int ds2i_synth_build(const ds2i_synth_params* pp, int codec, int threads, ds2i_blob** index_image,
                      ds2i_blob** wand_image, uint64_t* total_postings) {
-    if (!pp || !index_image || codec < 0 || codec > LAYOUT_UNIFORM) return ds2i_set_error(-1, "ds2i_synth_build: bad argument");
+    if (!pp || !index_image || codec < 0 || codec > LAYOUT_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_build: bad argument");
     const bool freq_layout = is_freq_layout(codec);
     DS2I_TRY
     const synth_params p = to_params(pp);
@@ -274,31 +258,15 @@ int ds2i_synth_build(const ds2i_synth_params* pp, int codec, int threads, ds2i_b
     std::vector<bytes_t> enc(V);
     std::vector<bitvec_builder> enc_docs(freq_layout ? V : 0), enc_freqs(freq_layout ? V : 0);
     std::vector<float> max_w(V);
-    std::atomic<uint32_t> next(0);
     std::atomic<uint64_t> postings(0);
-    std::string err;
-    std::mutex err_mu;
-    auto worker = [&]() {
-        std::vector<uint32_t> d, f;
-        try {
-            for (;;) {
-                uint32_t t = next.fetch_add(1);
-                if (t >= V) break;
-                uint64_t n = synth_list(p, t, d, f);
-                if (freq_layout) opt_index_builder::encode_list(p.num_docs, global_parameters(), n, d.data(), f.data(), enc_docs[t], enc_freqs[t], codec);
-                else write_posting_list(codec, enc[t], (uint32_t)n, d.data(), f.data());
-                max_w[t] = list_max_weight(norm_lens.data(), n, d.data(), f.data());
-                postings += n;
-            }
-        } catch (std::exception const& e) {
-            std::lock_guard<std::mutex> g(err_mu);
-            err = e.what();
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int i = 0; i < threads; ++i) pool.emplace_back(worker);
-    for (auto& th : pool) th.join();
-    if (!err.empty()) return ds2i_set_error(-2, err.c_str());
+    std::vector<std::vector<uint32_t>> d(threads), f(threads); // every worker's list
+    parallel_for(V, (unsigned)threads, [&](uint64_t t, unsigned w) {
+        const uint64_t n = synth_list(p, (uint32_t)t, d[w], f[w]);
+        if (freq_layout) opt_index_builder::encode_list(p.num_docs, global_parameters(), n, d[w].data(), f[w].data(), enc_docs[t], enc_freqs[t], codec);
+        else write_posting_list(codec, enc[t], (uint32_t)n, d[w].data(), f[w].data());
+        max_w[t] = list_max_weight(norm_lens.data(), n, d[w].data(), f[w].data());
+        postings += n;
+    });
     auto* ib = new ds2i_blob;
     if (freq_layout) {
         opt_index_builder builder(p.num_docs, global_parameters(), codec);
@@ -330,34 +298,26 @@ int ds2i_synth_build(const ds2i_synth_params* pp, int codec, int threads, ds2i_b
 
 // ---------------------------------------------------------------- block_mixed optimiser (host_hybrid.hpp)
 void ds2i_hybrid_default_model(ds2i_hybrid_model* m) {
-    if (!m) return;
-    hybrid_model d;
-    m->pfor_base = d.pfor_base; m->pfor_exc = d.pfor_exc; m->pfor_exc_many = d.pfor_exc_many;
-    m->varint = d.varint; m->interp_base = d.interp_base; m->interp_node = d.interp_node;
+    if (m) *m = from_model(hybrid_model());
 }
 int ds2i_hybrid_create(uint64_t num_docs, const ds2i_hybrid_model* model, ds2i_hybrid** out) {
-    if (!out) return ds2i_set_error(-1, "ds2i_hybrid_create: null argument");
+    if (!out) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_create: null argument");
     DS2I_TRY
-    hybrid_model m;
-    if (model) {
-        m.pfor_base = model->pfor_base; m.pfor_exc = model->pfor_exc; m.pfor_exc_many = model->pfor_exc_many;
-        m.varint = model->varint; m.interp_base = model->interp_base; m.interp_node = model->interp_node;
-    }
     auto* h = new ds2i_hybrid;
-    h->b.reset(new hybrid_index_builder(num_docs, m));
+    h->b.reset(new hybrid_index_builder(num_docs, to_model(model)));
     *out = h;
     return 0;
     DS2I_CATCH
 }
 int ds2i_hybrid_add_posting_list(ds2i_hybrid* h, uint64_t n, const uint32_t* docs, const uint32_t* freqs, const uint32_t* access) {
-    if (!h || !docs || !freqs) return ds2i_set_error(-1, "ds2i_hybrid_add_posting_list: null argument");
+    if (!h || !docs || !freqs) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_add_posting_list: null argument");
     DS2I_TRY
     h->b->add_posting_list(n, docs, freqs, access);
     return 0;
     DS2I_CATCH
 }
 int ds2i_hybrid_analyse(ds2i_hybrid* h, int threads, uint64_t* min_space, uint64_t* max_space) {
-    if (!h) return ds2i_set_error(-1, "ds2i_hybrid_analyse: null argument");
+    if (!h) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_analyse: null argument");
     DS2I_TRY
     if (!h->b->analysed()) h->b->analyse(threads);
     if (min_space) *min_space = h->b->min_space();
@@ -367,10 +327,10 @@ int ds2i_hybrid_analyse(ds2i_hybrid* h, int threads, uint64_t* min_space, uint64
 }
 int ds2i_hybrid_freeze(ds2i_hybrid* h, uint64_t budget_bytes, int threads, ds2i_blob** image, double* rate, uint64_t* space,
                        double* model_time, uint64_t type_counts[6]) {
-    if (!h || !image) return ds2i_set_error(-1, "ds2i_hybrid_freeze: null argument");
+    if (!h || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_freeze: null argument");
     DS2I_TRY
     if (!h->b->analysed()) h->b->analyse(threads);
-    if (budget_bytes < h->b->min_space()) return ds2i_set_error(-1, "budget below the smallest possible index");
+    if (budget_bytes < h->b->min_space()) return ds2i_set_error(DS2I_EINVAL, "budget below the smallest possible index");
     const double r = h->b->solve(budget_bytes);
     uint64_t s = 0;
     double t = 0;
@@ -385,12 +345,12 @@ int ds2i_hybrid_freeze(ds2i_hybrid* h, uint64_t budget_bytes, int threads, ds2i_
     DS2I_CATCH
 }
 int ds2i_hybrid_hull(const ds2i_hybrid* h, uint64_t list, uint64_t block, int side, void* points, uint32_t capacity, uint32_t* n) {
-    if (!h || !n || (!points && capacity)) return ds2i_set_error(-1, "ds2i_hybrid_hull: null argument");
-    if (!h->b->analysed()) return ds2i_set_error(-1, "ds2i_hybrid_hull: the builder is not analysed");
+    if (!h || !n || (!points && capacity)) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_hull: null argument");
+    if (!h->b->analysed()) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_hull: the builder is not analysed");
     static_assert(sizeof(hybrid_point) == 8, "hybrid_point is the published {float, uint16, uint8, int8}");
     uint32_t cnt = 0;
     const hybrid_point* p = h->b->hull(list, block, side, cnt);
-    if (!p) return ds2i_set_error(-1, "ds2i_hybrid_hull: no such part");
+    if (!p) return ds2i_set_error(DS2I_EINVAL, "ds2i_hybrid_hull: no such part");
     *n = cnt;
     if (points && capacity) std::memcpy(points, p, sizeof(hybrid_point) * std::min(cnt, capacity));
     return 0;
@@ -404,15 +364,10 @@ int ds2i_synth_build_hybrid(const ds2i_synth_params* pp, int threads, const ds2i
                             double budget_frac, ds2i_blob** index_image, ds2i_blob** wand_image, uint64_t* total_postings,
                             uint64_t type_counts[6]) {
     if (!pp || !index_image || !(budget_frac >= 0.0 && budget_frac <= 1.0))
-        return ds2i_set_error(-1, "ds2i_synth_build_hybrid: bad argument");
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_synth_build_hybrid: bad argument");
     DS2I_TRY
     const synth_params p = to_params(pp);
     if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-    hybrid_model m;
-    if (model) {
-        m.pfor_base = model->pfor_base; m.pfor_exc = model->pfor_exc; m.pfor_exc_many = model->pfor_exc_many;
-        m.varint = model->varint; m.interp_base = model->interp_base; m.interp_node = model->interp_node;
-    }
     const uint32_t V = p.num_terms;
     std::vector<uint32_t> sizes;
     synth_doc_sizes(p, sizes);
@@ -423,21 +378,13 @@ int ds2i_synth_build_hybrid(const ds2i_synth_params* pp, int threads, const ds2i
     std::vector<float> max_w(V, 0.f);
     std::vector<uint64_t> len(V, 0);
     {
-        std::atomic<uint32_t> next(0);
-        auto worker = [&]() {
-            std::vector<uint32_t> d, f;
-            for (;;) {
-                const uint32_t t = next.fetch_add(1);
-                if (t >= V) break;
-                len[t] = synth_list(p, t, d, f);
-                max_w[t] = list_max_weight(norm_lens.data(), len[t], d.data(), f.data());
-            }
-        };
-        std::vector<std::thread> pool;
-        for (int i = 0; i < threads; ++i) pool.emplace_back(worker);
-        for (auto& th : pool) th.join();
+        std::vector<std::vector<uint32_t>> d(threads), f(threads); // every worker's list
+        parallel_for(V, (unsigned)threads, [&](uint64_t t, unsigned w) {
+            len[t] = synth_list(p, (uint32_t)t, d[w], f[w]);
+            max_w[t] = list_max_weight(norm_lens.data(), len[t], d[w].data(), f[w].data());
+        });
     }
-    hybrid_index_builder hb(p.num_docs, m);
+    hybrid_index_builder hb(p.num_docs, to_model(model));
     uint64_t base = 0, postings = 0;
     for (uint32_t t = 0; t < V; ++t) {
         const uint64_t blocks = ceil_div(len[t], (uint64_t)BLOCK);

@@ -12,48 +12,26 @@
 // list (host_freq_plan.hpp: headers, and the place of every base sequence), freq_encode_kernels.hip writes the base sequences.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <memory>
-#include <mutex>
 #include <thread>
 #include <vector>
 
+#include "../../include/ds2i_build.h"
 #include "capi_blob.hpp"
 #include "capi_hybrid.hpp"
-#include "capi_internal.hpp"
+#include "capi_util.hpp"
 #include "host_freq_plan.hpp"
 #include "host_index.hpp"
+#include "host_parallel.hpp"
+#include "host_synth.hpp"
 #include "launchers.hpp"
 
 namespace {
-struct DevFree {
-    std::vector<void*> p;
-    ~DevFree() { for (void* x : p) if (x) (void)hipFree(x); }
-    template <class T> hipError_t alloc(T** out, size_t bytes) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T*)q;
-        return e;
-    }
-};
-struct Events { // destroyed on every path out of a function
-    hipEvent_t e[4] = {};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
-
-int check_device(const char* who, int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return ds2i_set_error(DS2I_EDEVICE, (std::string(who) + ": no such HIP device").c_str());
-    return DS2I_OK;
-}
-
 // A collection in CSR form staged on the device, with the block tables both kernels walk
 struct EncStage {
-    DevFree dev;
+    DevTemps dev;
     ds2i_dev::EncArgs a{};
     uint64_t nlists = 0, nblocks = 0;
     const uint64_t* list_offsets = nullptr;
@@ -78,11 +56,9 @@ struct EncStage {
             nblocks += (n + 127) / 128;
         }
         if (nblocks >= (1ull << 32)) return ds2i_set_error(DS2I_EINVAL, "more than 2^32 blocks");
-        try {
-            blk_list.resize(nblocks);
-        } catch (std::bad_alloc const&) {
-            return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-        }
+        DS2I_TRY
+        blk_list.resize(nblocks);
+        DS2I_CATCH
         for (uint64_t t = 0; t < nlists; ++t) {
             const uint64_t nb = (offs[t + 1] - offs[t] + 127) / 128;
             std::fill(blk_list.begin() + list_blk0[t], blk_list.begin() + list_blk0[t] + nb, (uint32_t)t);
@@ -147,20 +123,16 @@ struct EncStage {
 
     // the device-written list bytes wrapped into the block_freq_index image of that codec
     int wrap(int codec, uint64_t num_docs, uint64_t bytes, const std::vector<uint64_t>& list_end, ds2i_blob** image) {
-        try {
-            ds2i_host::bytes_t lists(bytes);
-            HIP_OK(hipMemcpy(lists.data(), a.out, bytes, hipMemcpyDeviceToHost));
-            ds2i_host::block_index_builder builder(codec, num_docs);
-            builder.set_encoded_lists(std::move(lists), list_end);
-            std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
-            builder.freeze(blob->data);
-            *image = blob.release();
-        } catch (std::bad_alloc const&) {
-            return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-        } catch (std::exception const& e) {
-            return ds2i_set_error(DS2I_EFORMAT, e.what());
-        }
+        DS2I_TRY
+        ds2i_host::bytes_t lists(bytes);
+        HIP_OK(hipMemcpy(lists.data(), a.out, bytes, hipMemcpyDeviceToHost));
+        ds2i_host::block_index_builder builder(codec, num_docs);
+        builder.set_encoded_lists(std::move(lists), list_end);
+        std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
+        builder.freeze(blob->data);
+        *image = blob.release();
         return DS2I_OK;
+        DS2I_CATCH
     }
 };
 #define STAGE_OK(call)                 \
@@ -172,59 +144,21 @@ struct EncStage {
 // plan pass, layout, write pass of one codec over a staged collection; ms accumulates the hipEvent time of the two passes
 int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image, double& ms) {
     const uint64_t nblocks = st.nblocks;
-    Events evs;
-    for (auto& x : evs.e) HIP_OK(hipEventCreate(&x));
-    const hipEvent_t e0 = evs.e[0], e1 = evs.e[1], e2 = evs.e[2], e3 = evs.e[3];
-    // ---- plan pass
-    HIP_OK(hipEventRecord(e0, nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 0, st.a, st.grid, nullptr));
-    HIP_OK(hipEventRecord(e1, nullptr));
+    auto pass = [&](int which) { return nblocks ? ds2i_launch_encode(codec, which, st.a, st.grid, nullptr) : hipSuccess; };
+    // ---- plan pass (the copy of the sizes below would wait for it anyway)
+    HIP_OK(timed_span(nullptr, ms, [&] { return pass(0); }));
     std::vector<uint32_t> psize(2 * nblocks);
     HIP_OK(hipMemcpy(psize.data(), st.a.psize, 8 * nblocks, hipMemcpyDeviceToHost));
     std::vector<uint64_t> list_end;
     uint64_t bytes = 0;
     STAGE_OK(st.lay_out(psize, list_end, bytes));
     // ---- write pass
-    HIP_OK(hipEventRecord(e2, nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_encode(codec, 1, st.a, st.grid, nullptr));
-    HIP_OK(hipEventRecord(e3, nullptr));
-    HIP_OK(hipEventSynchronize(e3));
-    float ms_plan = 0.f, ms_write = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms_plan, e0, e1));
-    HIP_OK(hipEventElapsedTime(&ms_write, e2, e3));
-    ms += (double)ms_plan + ms_write;
+    HIP_OK(timed_span(nullptr, ms, [&] { return pass(1); }));
     return st.wrap(codec, num_docs, bytes, list_end, image);
 }
 
 // ---- the Elias-Fano layouts (freq_index: opt, ef, single, uniform) over a staged collection
 constexpr int FREQ_PLAN_THREADS = 16; // the planning pool's cap: never the whole machine's CPU count
-
-// `fn(t)` for every list on the host pool ds2i_synth_build uses (threads drawing list numbers), at most FREQ_PLAN_THREADS wide
-template <class Fn>
-void for_each_list(uint64_t nlists, Fn fn) {
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned threads = (unsigned)std::min<uint64_t>(std::min<unsigned>(hw, FREQ_PLAN_THREADS), std::max<uint64_t>(nlists, 1));
-    std::atomic<uint64_t> next(0);
-    std::string err;
-    std::mutex err_mu;
-    auto worker = [&]() {
-        try {
-            for (;;) {
-                const uint64_t t = next.fetch_add(1);
-                if (t >= nlists) break;
-                fn(t);
-            }
-        } catch (std::exception const& e) {
-            std::lock_guard<std::mutex> g(err_mu);
-            err = e.what();
-        }
-    };
-    std::vector<std::thread> pool;
-    for (unsigned i = 1; i < threads; ++i) pool.emplace_back(worker);
-    worker();
-    for (auto& th : pool) th.join();
-    if (!err.empty()) throw std::runtime_error(err);
-}
 
 // Plan on the host (for opt: optimal_partition, list-parallel), prefix sums and base sequences on the device, headers ORed into
 // the downloaded vectors, opt_index_builder::freeze around them. ms accumulates the hipEvent time of the kernels; the host's two
@@ -239,9 +173,12 @@ int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32
     const uint64_t postings = offs[nlists];
     const global_parameters params;
     std::vector<freq_list_plan> plans(nlists);
-    for_each_list(nlists, [&](uint64_t t) {
+    // (the calling thread and up to FREQ_PLAN_THREADS - 1 more, never more threads than lists)
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    const unsigned threads = (unsigned)std::min<uint64_t>(std::min<unsigned>(hw, FREQ_PLAN_THREADS), std::max<uint64_t>(nlists, 1));
+    parallel_for(nlists, threads, [&](uint64_t t, unsigned) {
         plan_list(layout, num_docs, params, offs[t], offs[t + 1] - offs[t], docs + offs[t], freqs + offs[t], plans[t]);
-    });
+    }, true);
     // where every list starts in the two bit vectors; the jobs move to their final offsets
     std::vector<uint64_t> ends[2], head_at[2];
     std::vector<ds2i_dev::FreqJob> jobs[2];
@@ -287,40 +224,29 @@ int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32
         fa[side].nbits = ends[side].back();
         std::vector<ds2i_dev::FreqJob>().swap(jobs[side]);
     }
-    Events evs;
-    HIP_OK(hipEventCreate(&evs.e[0]));
-    HIP_OK(hipEventCreate(&evs.e[1]));
-    HIP_OK(hipEventRecord(evs.e[0], nullptr));
-    if (st.nblocks) {
-        HIP_OK(ds2i_launch_freq_prefix_sums(st.a, nlists, d_blk_base, d_cum, st.grid, nullptr));
-        HIP_OK(ds2i_launch_freq_write(0, fa[0], st.grid, nullptr));
-        HIP_OK(ds2i_launch_freq_write(1, fa[1], st.grid, nullptr));
-    }
-    HIP_OK(hipEventRecord(evs.e[1], nullptr));
-    HIP_OK(hipEventSynchronize(evs.e[1]));
-    float t = 0.f;
-    HIP_OK(hipEventElapsedTime(&t, evs.e[0], evs.e[1]));
-    ms += t;
+    HIP_OK(timed_span(nullptr, ms, [&] {
+        if (!st.nblocks) return hipSuccess;
+        hipError_t e = ds2i_launch_freq_prefix_sums(st.a, nlists, d_blk_base, d_cum, st.grid, nullptr);
+        if (e == hipSuccess) e = ds2i_launch_freq_write(0, fa[0], st.grid, nullptr);
+        if (e == hipSuccess) e = ds2i_launch_freq_write(1, fa[1], st.grid, nullptr);
+        return e;
+    }));
     // ---- host: the headers join the device's words; the container is the host builder's
     const auto t2 = std::chrono::steady_clock::now();
-    try {
-        bitvec_builder bits[2];
-        for (int side = 0; side < 2; ++side) {
-            bits[side].zero_extend(ends[side].back());
-            HIP_OK(hipMemcpy(bits[side].words().data(), fa[side].out, 8 * words[side], hipMemcpyDeviceToHost));
-            for (uint64_t l = 0; l < nlists; ++l) or_bits_at(bits[side].words(), ends[side][l], plans[l].head[side]);
-        }
-        std::vector<freq_list_plan>().swap(plans);
-        opt_index_builder builder(num_docs, params, layout);
-        builder.set_encoded(std::move(bits[0]), std::move(ends[0]), std::move(bits[1]), std::move(ends[1]));
-        std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
-        builder.freeze(blob->data);
-        *image = blob.release();
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    DS2I_TRY
+    bitvec_builder bits[2];
+    for (int side = 0; side < 2; ++side) {
+        bits[side].zero_extend(ends[side].back());
+        HIP_OK(hipMemcpy(bits[side].words().data(), fa[side].out, 8 * words[side], hipMemcpyDeviceToHost));
+        for (uint64_t l = 0; l < nlists; ++l) or_bits_at(bits[side].words(), ends[side][l], plans[l].head[side]);
     }
+    std::vector<freq_list_plan>().swap(plans);
+    opt_index_builder builder(num_docs, params, layout);
+    builder.set_encoded(std::move(bits[0]), std::move(ends[0]), std::move(bits[1]), std::move(ends[1]));
+    std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
+    builder.freeze(blob->data);
+    *image = blob.release();
+    DS2I_CATCH
     freq_host_s[0] = std::chrono::duration<double>(t1 - t0).count();
     freq_host_s[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count();
     return DS2I_OK;
@@ -335,18 +261,11 @@ int wand_max_staged(EncStage& st, const std::vector<float>& norm_lens, std::vect
     HIP_OK(st.dev.alloc(&d_max, 4 * st.nlists));
     HIP_OK(hipMemcpy(d_norm, norm_lens.data(), 4 * norm_lens.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemset(d_max, 0, 4 * st.nlists));
-    Events evs;
-    HIP_OK(hipEventCreate(&evs.e[0]));
-    HIP_OK(hipEventCreate(&evs.e[1]));
-    HIP_OK(hipEventRecord(evs.e[0], nullptr));
-    if (st.nblocks)
-        HIP_OK(ds2i_launch_wand_list_max(st.a.docs, st.a.freqs, st.a.list_in, st.a.blk_list, st.a.list_blk0, st.a.nblocks, d_norm,
-                                         norm_lens.size(), d_max, st.grid, nullptr));
-    HIP_OK(hipEventRecord(evs.e[1], nullptr));
-    HIP_OK(hipEventSynchronize(evs.e[1]));
-    float t = 0.f;
-    HIP_OK(hipEventElapsedTime(&t, evs.e[0], evs.e[1]));
-    ms += t;
+    HIP_OK(timed_span(nullptr, ms, [&] {
+        return st.nblocks ? ds2i_launch_wand_list_max(st.a.docs, st.a.freqs, st.a.list_in, st.a.blk_list, st.a.list_blk0, st.a.nblocks, d_norm,
+                                                      norm_lens.size(), d_max, st.grid, nullptr)
+                          : hipSuccess;
+    }));
     max_w.resize(st.nlists);
     HIP_OK(hipMemcpy(max_w.data(), d_max, 4 * st.nlists, hipMemcpyDeviceToHost));
     return DS2I_OK;
@@ -428,13 +347,9 @@ extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_do
     int codec = 0;
     STAGE_OK(encoder_kind_of("ds2i_hip_encode_index", index_kind, codec));
     if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings("ds2i_hip_encode_index", num_docs, nlists, list_offsets, docs, freqs));
-    try {
-        return build_images("ds2i_hip_encode_index", device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) { // the planner of the Elias-Fano layouts
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
-    }
+    DS2I_TRY
+    return build_images("ds2i_hip_encode_index", device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms);
+    DS2I_CATCH
 }
 
 extern "C" void ds2i_hip_encode_host_seconds(double seconds[2]) {
@@ -446,13 +361,11 @@ extern "C" int ds2i_hip_build_wand(int device, const uint32_t* doc_sizes, uint64
     if (!doc_sizes || !num_docs || !list_offsets || !docs || !freqs || !wand_image)
         return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_build_wand: bad argument");
     STAGE_OK(check_postings("ds2i_hip_build_wand", num_docs, nlists, list_offsets, docs));
-    try {
-        std::vector<float> norm_lens;
-        ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
-        return build_images("ds2i_hip_build_wand", device, 0, num_docs, &norm_lens, nlists, list_offsets, docs, freqs, nullptr, wand_image, device_ms);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    }
+    DS2I_TRY
+    std::vector<float> norm_lens;
+    ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
+    return build_images("ds2i_hip_build_wand", device, 0, num_docs, &norm_lens, nlists, list_offsets, docs, freqs, nullptr, wand_image, device_ms);
+    DS2I_CATCH
 }
 
 extern "C" int ds2i_hip_build_collection(int device, int index_kind, const uint32_t* doc_sizes, uint64_t num_docs, uint64_t nlists,
@@ -464,16 +377,12 @@ extern "C" int ds2i_hip_build_collection(int device, int index_kind, const uint3
     STAGE_OK(encoder_kind_of("ds2i_hip_build_collection", index_kind, codec));
     STAGE_OK(check_postings("ds2i_hip_build_collection", num_docs, nlists, list_offsets, docs));
     if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings("ds2i_hip_build_collection", num_docs, nlists, list_offsets, docs, freqs));
-    try {
-        std::vector<float> norm_lens;
-        if (wand_image) ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
-        return build_images("ds2i_hip_build_collection", device, codec, num_docs, &norm_lens, nlists, list_offsets, docs, freqs, index_image,
-                            wand_image, device_ms);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
-    }
+    DS2I_TRY
+    std::vector<float> norm_lens;
+    if (wand_image) ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
+    return build_images("ds2i_hip_build_collection", device, codec, num_docs, &norm_lens, nlists, list_offsets, docs, freqs, index_image,
+                        wand_image, device_ms);
+    DS2I_CATCH
 }
 
 // ---------------------------------------------------------------- block_mixed optimiser on the device
@@ -498,16 +407,7 @@ int hybrid_csr(const char* who, const ds2i_host::hybrid_index_builder& hb, std::
 int hybrid_analyse_on(EncStage& st, ds2i_host::hybrid_index_builder& hb, double& ms) {
     const uint64_t nblocks = st.nblocks;
     HIP_OK(st.dev.alloc(&st.a.rec, sizeof(ds2i_host::hybrid_part_rec) * 2 * nblocks));
-    Events evs;
-    HIP_OK(hipEventCreate(&evs.e[0]));
-    HIP_OK(hipEventCreate(&evs.e[1]));
-    HIP_OK(hipEventRecord(evs.e[0], nullptr));
-    if (nblocks) HIP_OK(ds2i_launch_hybrid_plan(st.a, st.grid, nullptr));
-    HIP_OK(hipEventRecord(evs.e[1], nullptr));
-    HIP_OK(hipEventSynchronize(evs.e[1]));
-    float t = 0.f;
-    HIP_OK(hipEventElapsedTime(&t, evs.e[0], evs.e[1]));
-    ms += t;
+    HIP_OK(timed_span(nullptr, ms, [&] { return nblocks ? ds2i_launch_hybrid_plan(st.a, st.grid, nullptr) : hipSuccess; }));
     std::vector<ds2i_host::hybrid_part_rec> recs(2 * nblocks);
     HIP_OK(hipMemcpy(recs.data(), st.a.rec, sizeof(ds2i_host::hybrid_part_rec) * 2 * nblocks, hipMemcpyDeviceToHost));
     hb.analyse_from_records(recs.data(), 0);
@@ -517,181 +417,126 @@ int hybrid_analyse_on(EncStage& st, ds2i_host::hybrid_index_builder& hb, double&
 
 extern "C" int ds2i_hip_hybrid_analyse(ds2i_hybrid* h, int device, uint64_t* min_space, uint64_t* max_space, double* device_ms) {
     if (!h) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_analyse: null argument");
-    try {
-        ds2i_host::hybrid_index_builder& hb = *h->b;
-        double ms = 0.0;
-        if (hb.analysed()) {
-            STAGE_OK(check_device("ds2i_hip_hybrid_analyse", device));
-        } else {
-            std::vector<uint64_t> offs;
-            std::vector<uint32_t> docs, freqs;
-            STAGE_OK(hybrid_csr("ds2i_hip_hybrid_analyse", hb, offs, docs, freqs));
-            EncStage st;
-            STAGE_OK(st.upload("ds2i_hip_hybrid_analyse", device, hb.lists(), offs.data(), docs.data(), freqs.data()));
-            STAGE_OK(hybrid_analyse_on(st, hb, ms));
-        }
-        if (min_space) *min_space = hb.min_space();
-        if (max_space) *max_space = hb.max_space();
-        if (device_ms) *device_ms = ms;
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    DS2I_TRY
+    ds2i_host::hybrid_index_builder& hb = *h->b;
+    double ms = 0.0;
+    if (hb.analysed()) {
+        STAGE_OK(check_device("ds2i_hip_hybrid_analyse", device));
+    } else {
+        std::vector<uint64_t> offs;
+        std::vector<uint32_t> docs, freqs;
+        STAGE_OK(hybrid_csr("ds2i_hip_hybrid_analyse", hb, offs, docs, freqs));
+        EncStage st;
+        STAGE_OK(st.upload("ds2i_hip_hybrid_analyse", device, hb.lists(), offs.data(), docs.data(), freqs.data()));
+        STAGE_OK(hybrid_analyse_on(st, hb, ms));
     }
+    if (min_space) *min_space = hb.min_space();
+    if (max_space) *max_space = hb.max_space();
+    if (device_ms) *device_ms = ms;
     return DS2I_OK;
+    DS2I_CATCH
 }
 
 extern "C" int ds2i_hip_hybrid_freeze(ds2i_hybrid* h, int device, uint64_t budget_bytes, ds2i_blob** image, double* rate,
                                       uint64_t* space, double* model_time, uint64_t type_counts[6], double* device_ms) {
     if (!h || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_freeze: null argument");
-    try {
-        ds2i_host::hybrid_index_builder& hb = *h->b;
-        double ms = 0.0;
-        std::vector<uint64_t> offs;
-        std::vector<uint32_t> docs, freqs;
-        STAGE_OK(hybrid_csr("ds2i_hip_hybrid_freeze", hb, offs, docs, freqs));
-        EncStage st;
-        STAGE_OK(st.upload("ds2i_hip_hybrid_freeze", device, hb.lists(), offs.data(), docs.data(), freqs.data()));
-        if (!hb.analysed()) STAGE_OK(hybrid_analyse_on(st, hb, ms));
-        if (budget_bytes < hb.min_space()) return ds2i_set_error(DS2I_EINVAL, "budget below the smallest possible index");
-        const double r = hb.solve(budget_bytes);
-        uint64_t s = 0;
-        double t = 0;
-        hb.evaluate(r, s, t);
-        // the choice of every part: (type, b) for the kernel, its bytes for the layout (a hull point's space IS the
-        // size of the part in that encoding, type byte included), the counts of the full blocks
-        const uint64_t nblocks = st.nblocks;
-        std::vector<uint8_t> choice(4 * nblocks);
-        std::vector<uint32_t> psize(2 * nblocks);
-        uint64_t tc[6] = {0, 0, 0, 0, 0, 0};
-        {
-            uint64_t part = 0;
-            uint64_t t_list = 0, left = hb.lists() ? hb.list_size(0) : 0; // postings of the current list from this block on
-            hb.for_each_choice(r, [&](ds2i_host::hybrid_point const& c) {
-                choice[2 * part] = c.type;
-                choice[2 * part + 1] = (uint8_t)c.b;
-                psize[part] = c.space;
-                if (left >= ds2i_host::BLOCK) ++tc[3 * (part & 1) + c.type];
-                if (part & 1) {
-                    left -= std::min<uint64_t>(left, ds2i_host::BLOCK);
-                    if (!left && ++t_list < hb.lists()) left = hb.list_size(t_list);
-                }
-                ++part;
-            });
-            if (part != 2 * nblocks) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_freeze: the analysis does not match the lists");
-        }
-        uint8_t* d_choice = nullptr;
-        HIP_OK(st.dev.alloc(&d_choice, 4 * nblocks));
-        HIP_OK(hipMemcpy(d_choice, choice.data(), 4 * nblocks, hipMemcpyHostToDevice));
-        st.a.choice = d_choice;
-        std::vector<uint64_t> list_end;
-        uint64_t bytes = 0;
-        STAGE_OK(st.lay_out(psize, list_end, bytes));
-        Events evs;
-        HIP_OK(hipEventCreate(&evs.e[0]));
-        HIP_OK(hipEventCreate(&evs.e[1]));
-        HIP_OK(hipEventRecord(evs.e[0], nullptr));
-        if (nblocks) HIP_OK(ds2i_launch_encode(ds2i_host::CODEC_MIXED, 1, st.a, st.grid, nullptr));
-        HIP_OK(hipEventRecord(evs.e[1], nullptr));
-        HIP_OK(hipEventSynchronize(evs.e[1]));
-        float tw = 0.f;
-        HIP_OK(hipEventElapsedTime(&tw, evs.e[0], evs.e[1]));
-        ms += tw;
-        // the kernel reports what it wrote: it must be what the hulls promised, or the layout is wrong
-        std::vector<uint32_t> wrote(2 * nblocks);
-        HIP_OK(hipMemcpy(wrote.data(), st.a.psize, 8 * nblocks, hipMemcpyDeviceToHost));
-        if (wrote != psize) return ds2i_set_error(DS2I_EFORMAT, "ds2i_hip_hybrid_freeze: a part was written at another size than its hull point");
-        STAGE_OK(st.wrap(ds2i_host::CODEC_MIXED, hb.num_docs(), bytes, list_end, image));
-        if (rate) *rate = r;
-        if (space) *space = s;
-        if (model_time) *model_time = t;
-        if (type_counts) for (int i = 0; i < 6; ++i) type_counts[i] = tc[i];
-        if (device_ms) *device_ms = ms;
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
+    DS2I_TRY
+    ds2i_host::hybrid_index_builder& hb = *h->b;
+    double ms = 0.0;
+    std::vector<uint64_t> offs;
+    std::vector<uint32_t> docs, freqs;
+    STAGE_OK(hybrid_csr("ds2i_hip_hybrid_freeze", hb, offs, docs, freqs));
+    EncStage st;
+    STAGE_OK(st.upload("ds2i_hip_hybrid_freeze", device, hb.lists(), offs.data(), docs.data(), freqs.data()));
+    if (!hb.analysed()) STAGE_OK(hybrid_analyse_on(st, hb, ms));
+    if (budget_bytes < hb.min_space()) return ds2i_set_error(DS2I_EINVAL, "budget below the smallest possible index");
+    const double r = hb.solve(budget_bytes);
+    uint64_t s = 0;
+    double t = 0;
+    hb.evaluate(r, s, t);
+    // the choice of every part: (type, b) for the kernel, its bytes for the layout (a hull point's space IS the
+    // size of the part in that encoding, type byte included), the counts of the full blocks
+    const uint64_t nblocks = st.nblocks;
+    std::vector<uint8_t> choice(4 * nblocks);
+    std::vector<uint32_t> psize(2 * nblocks);
+    uint64_t tc[6] = {0, 0, 0, 0, 0, 0};
+    {
+        uint64_t part = 0;
+        uint64_t t_list = 0, left = hb.lists() ? hb.list_size(0) : 0; // postings of the current list from this block on
+        hb.for_each_choice(r, [&](ds2i_host::hybrid_point const& c) {
+            choice[2 * part] = c.type;
+            choice[2 * part + 1] = (uint8_t)c.b;
+            psize[part] = c.space;
+            if (left >= ds2i_host::BLOCK) ++tc[3 * (part & 1) + c.type];
+            if (part & 1) {
+                left -= std::min<uint64_t>(left, ds2i_host::BLOCK);
+                if (!left && ++t_list < hb.lists()) left = hb.list_size(t_list);
+            }
+            ++part;
+        });
+        if (part != 2 * nblocks) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_hybrid_freeze: the analysis does not match the lists");
     }
+    uint8_t* d_choice = nullptr;
+    HIP_OK(st.dev.alloc(&d_choice, 4 * nblocks));
+    HIP_OK(hipMemcpy(d_choice, choice.data(), 4 * nblocks, hipMemcpyHostToDevice));
+    st.a.choice = d_choice;
+    std::vector<uint64_t> list_end;
+    uint64_t bytes = 0;
+    STAGE_OK(st.lay_out(psize, list_end, bytes));
+    HIP_OK(timed_span(nullptr, ms, [&] { return nblocks ? ds2i_launch_encode(ds2i_host::CODEC_MIXED, 1, st.a, st.grid, nullptr) : hipSuccess; }));
+    // the kernel reports what it wrote: it must be what the hulls promised, or the layout is wrong
+    std::vector<uint32_t> wrote(2 * nblocks);
+    HIP_OK(hipMemcpy(wrote.data(), st.a.psize, 8 * nblocks, hipMemcpyDeviceToHost));
+    if (wrote != psize) return ds2i_set_error(DS2I_EFORMAT, "ds2i_hip_hybrid_freeze: a part was written at another size than its hull point");
+    STAGE_OK(st.wrap(ds2i_host::CODEC_MIXED, hb.num_docs(), bytes, list_end, image));
+    if (rate) *rate = r;
+    if (space) *space = s;
+    if (model_time) *model_time = t;
+    if (type_counts) for (int i = 0; i < 6; ++i) type_counts[i] = tc[i];
+    if (device_ms) *device_ms = ms;
     return DS2I_OK;
+    DS2I_CATCH
 }
 
 // The synthetic collection (ds2i_build.h: ds2i_synth_params) generated on the host threads and encoded ON THE GPU:
 // the fast index-construction path of the benchmark loop. Produces the same two images as ds2i_synth_build(...,
 // DS2I_BLOCK_OPTPFOR, ...), byte for byte.
-#include <atomic>
-#include <chrono>
-#include <mutex>
-#include <thread>
-
-#include "../../include/ds2i_build.h"
-#include "host_synth.hpp"
-
 extern "C" int ds2i_hip_synth_encode(int device, const ds2i_synth_params* pp, int threads, ds2i_blob** index_image,
                                      ds2i_blob** wand_image, uint64_t* total_postings, double* generate_s, double* device_ms) {
     if (!pp || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_synth_encode: null argument");
     using namespace ds2i_host;
-    try {
-        synth_params p;
-        p.seed = pp->seed; p.num_docs = pp->num_docs; p.num_terms = pp->num_terms; p.zipf_exp = pp->zipf_exp;
-        p.top_df_frac = pp->top_df_frac; p.min_len = pp->min_len; p.clustered_every = pp->clustered_every;
-        p.topics = pp->topics; p.topic_boost = pp->topic_boost;
-        if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<uint32_t> sizes;
-        synth_doc_sizes(p, sizes);
-        std::vector<float> norm_lens;
-        compute_norm_lens(sizes.data(), p.num_docs, norm_lens);
-        std::vector<uint32_t>().swap(sizes);
-        const uint32_t V = p.num_terms;
-        std::vector<std::vector<uint32_t>> ld(V), lf(V);
-        std::atomic<uint32_t> next(0);
-        std::string err;
-        std::mutex err_mu;
-        auto run_pool = [&](auto fn) {
-            std::vector<std::thread> pool;
-            for (int i = 0; i < threads; ++i) pool.emplace_back(fn);
-            for (auto& th : pool) th.join();
-        };
-        run_pool([&]() {
-            try {
-                for (;;) {
-                    const uint32_t t = next.fetch_add(1);
-                    if (t >= V) break;
-                    const uint64_t n = synth_list(p, t, ld[t], lf[t]);
-                    ld[t].resize(n);
-                    lf[t].resize(n);
-                    ld[t].shrink_to_fit();
-                    lf[t].shrink_to_fit();
-                }
-            } catch (std::exception const& e) {
-                std::lock_guard<std::mutex> g(err_mu);
-                err = e.what();
-            }
-        });
-        if (!err.empty()) return ds2i_set_error(DS2I_EFORMAT, err.c_str());
-        std::vector<uint64_t> offs(V + 1, 0);
-        for (uint32_t t = 0; t < V; ++t) offs[t + 1] = offs[t] + ld[t].size();
-        std::vector<uint32_t> docs(offs[V] ? offs[V] : 1), freqs(offs[V] ? offs[V] : 1);
-        next = 0;
-        run_pool([&]() {
-            for (;;) {
-                const uint32_t t = next.fetch_add(1);
-                if (t >= V) break;
-                std::memcpy(docs.data() + offs[t], ld[t].data(), 4 * ld[t].size());
-                std::memcpy(freqs.data() + offs[t], lf[t].data(), 4 * lf[t].size());
-                std::vector<uint32_t>().swap(ld[t]);
-                std::vector<uint32_t>().swap(lf[t]);
-            }
-        });
-        if (generate_s) *generate_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        if (total_postings) *total_postings = offs[V];
-        // one staging for both images; max_term_weight comes from the wand kernel (the generator's doc-ids are < num_docs)
-        STAGE_OK(build_images("ds2i_hip_synth_encode", device, CODEC_OPTPFOR, p.num_docs, &norm_lens, V, offs.data(), docs.data(), freqs.data(),
-                              index_image, wand_image, device_ms));
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
-    }
+    DS2I_TRY
+    const synth_params p = to_params(pp);
+    if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> sizes;
+    synth_doc_sizes(p, sizes);
+    std::vector<float> norm_lens;
+    compute_norm_lens(sizes.data(), p.num_docs, norm_lens);
+    std::vector<uint32_t>().swap(sizes);
+    const uint32_t V = p.num_terms;
+    std::vector<std::vector<uint32_t>> ld(V), lf(V);
+    parallel_for(V, (unsigned)threads, [&](uint64_t t, unsigned) {
+        const uint64_t n = synth_list(p, (uint32_t)t, ld[t], lf[t]);
+        ld[t].resize(n);
+        lf[t].resize(n);
+        ld[t].shrink_to_fit();
+        lf[t].shrink_to_fit();
+    });
+    std::vector<uint64_t> offs(V + 1, 0);
+    for (uint32_t t = 0; t < V; ++t) offs[t + 1] = offs[t] + ld[t].size();
+    std::vector<uint32_t> docs(offs[V] ? offs[V] : 1), freqs(offs[V] ? offs[V] : 1);
+    parallel_for(V, (unsigned)threads, [&](uint64_t t, unsigned) {
+        std::memcpy(docs.data() + offs[t], ld[t].data(), 4 * ld[t].size());
+        std::memcpy(freqs.data() + offs[t], lf[t].data(), 4 * lf[t].size());
+        std::vector<uint32_t>().swap(ld[t]);
+        std::vector<uint32_t>().swap(lf[t]);
+    });
+    if (generate_s) *generate_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (total_postings) *total_postings = offs[V];
+    // one staging for both images; max_term_weight comes from the wand kernel (the generator's doc-ids are < num_docs)
+    STAGE_OK(build_images("ds2i_hip_synth_encode", device, CODEC_OPTPFOR, p.num_docs, &norm_lens, V, offs.data(), docs.data(), freqs.data(),
+                          index_image, wand_image, device_ms));
     return DS2I_OK;
+    DS2I_CATCH
 }

@@ -10,7 +10,7 @@
 #include <cstring>
 #include <vector>
 
-#include "capi_internal.hpp"
+#include "capi_util.hpp"
 #include "host_index.hpp"
 #include "host_pef.hpp"
 #include "launchers.hpp"
@@ -18,22 +18,6 @@
 using ds2i_dev::QTerm;
 
 namespace {
-
-struct DevFree { // device temporaries of one function: freed on every path out of it
-    std::vector<void*> p;
-    ~DevFree() { for (void* x : p) if (x) (void)hipFree(x); }
-    template <class T> hipError_t alloc(T** out, size_t bytes) {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, bytes ? bytes : 16);
-        if (e == hipSuccess) p.push_back(q);
-        *out = (T*)q;
-        return e;
-    }
-};
-struct Events {
-    hipEvent_t e[2] = {};
-    ~Events() { for (auto x : e) if (x) (void)hipEventDestroy(x); }
-};
 
 // seconds of {image parse + structure comparison, bare upload of the image, staging of the expected postings} of this thread's last
 // call (ds2i_hip_verify_host_seconds)
@@ -86,14 +70,11 @@ int verify_postings(ds2i_hip_index* idx, const uint64_t* offs, const uint32_t* d
     const auto t0 = std::chrono::steady_clock::now();
     HIP_OK(hipSetDevice(idx->device));
     std::vector<QTerm> lists;
-    try {
-        lists.resize(V);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    }
+    DS2I_TRY
+    lists.resize(V);
+    DS2I_CATCH
     for (uint64_t t = 0; t < V; ++t) lists[t] = ds2i_make_qterm(idx, (uint32_t)t);
-    DevFree dev;
-    Events ev;
+    DevTemps dev;
     QTerm* d_lists = nullptr;
     uint32_t *d_docs = nullptr, *d_freqs = nullptr;
     uint64_t* d_first = nullptr;
@@ -130,13 +111,8 @@ int verify_postings(ds2i_hip_index* idx, const uint64_t* offs, const uint32_t* d
     const unsigned grid = (unsigned)std::min<uint64_t>(idx->total_blocks, uint64_t(idx->num_cus) * 16);
     // block_optpfor with side tables: through the stream kernels' decoder (DS2I_DECODE_GENERAL=1: the general decoders)
     const bool side = idx->side_tables() && !idx->knobs.decode_general;
-    for (auto& x : ev.e) HIP_OK(hipEventCreate(&x));
-    HIP_OK(hipEventRecord(ev.e[0], idx->stream[0]));
-    HIP_OK(side ? ds2i_launch_verify_index_side(a, grid, idx->stream[0]) : ds2i_launch_verify_index(a, grid, idx->stream[0]));
-    HIP_OK(hipEventRecord(ev.e[1], idx->stream[0]));
-    HIP_OK(hipEventSynchronize(ev.e[1]));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    double ms = 0.0;
+    HIP_OK(timed_span(idx->stream[0], ms, [&] { return side ? ds2i_launch_verify_index_side(a, grid, idx->stream[0]) : ds2i_launch_verify_index(a, grid, idx->stream[0]); }));
     if (device_ms) *device_ms = ms;
     HIP_OK(hipMemcpy(&key, d_bad, 8, hipMemcpyDeviceToHost));
     if (key == ds2i_dev::VERIFY_NONE) return DS2I_OK;
@@ -150,12 +126,10 @@ int verify_postings(ds2i_hip_index* idx, const uint64_t* offs, const uint32_t* d
     r->postings_checked = at;
     // what the index holds there: the single-list decode of that one list (the same choice of decoder)
     std::vector<uint32_t> ld, lf;
-    try {
-        ld.resize(idx->list_n[t]);
-        lf.resize(idx->list_n[t]);
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    }
+    DS2I_TRY
+    ld.resize(idx->list_n[t]);
+    lf.resize(idx->list_n[t]);
+    DS2I_CATCH
     uint64_t n = 0;
     const int rc = ds2i_hip_decode_list(idx, (uint32_t)t, ld.data(), lf.data(), ld.size(), &n);
     if (rc != DS2I_OK) return rc;
@@ -191,40 +165,37 @@ int ds2i_hip_verify_collection(int device, int index_kind, const void* image, si
     const auto t0 = std::chrono::steady_clock::now();
     uint64_t img_docs = 0, img_lists = 0;
     std::vector<uint32_t> img_len;
-    try {
-        if (ds2i_host::is_freq_layout(index_kind)) {
-            ds2i_host::opt_index_view v;
-            v.layout = index_kind;
-            v.parse(image, bytes);
-            img_docs = v.num_docs;
-            img_lists = v.size;
-            img_len.resize(v.size);
-            for (uint64_t t = 0; t < v.size; ++t) img_len[t] = (uint32_t)v.list_length(t);
-        } else {
-            ds2i_host::block_index_view v;
-            v.parse(image, bytes);
-            img_docs = v.num_docs;
-            img_lists = v.size;
-            img_len.resize(v.size);
-            for (uint64_t t = 0; t < v.size; ++t) {
-                uint32_t n = 0;
-                if (!ds2i_host_vbyte(v.lists + v.list_offsets[t], v.list_offsets[t + 1] - v.list_offsets[t], n) || !n)
-                    return ds2i_set_error(DS2I_EFORMAT, "posting list header is corrupt");
-                img_len[t] = n;
-            }
+    DS2I_TRY
+    if (ds2i_host::is_freq_layout(index_kind)) {
+        ds2i_host::opt_index_view v;
+        v.layout = index_kind;
+        v.parse(image, bytes);
+        img_docs = v.num_docs;
+        img_lists = v.size;
+        img_len.resize(v.size);
+        for (uint64_t t = 0; t < v.size; ++t) img_len[t] = (uint32_t)v.list_length(t);
+    } else {
+        ds2i_host::block_index_view v;
+        v.parse(image, bytes);
+        img_docs = v.num_docs;
+        img_lists = v.size;
+        img_len.resize(v.size);
+        for (uint64_t t = 0; t < v.size; ++t) {
+            uint32_t n = 0;
+            if (!ds2i_host_vbyte(v.lists + v.list_offsets[t], v.list_offsets[t + 1] - v.list_offsets[t], n) || !n)
+                return ds2i_set_error(DS2I_EFORMAT, "posting list header is corrupt");
+            img_len[t] = n;
         }
-    } catch (std::bad_alloc const&) {
-        return ds2i_set_error(DS2I_ENOMEM, "out of host memory");
-    } catch (std::exception const& e) {
-        return ds2i_set_error(DS2I_EFORMAT, e.what());
     }
+    DS2I_CATCH
     std::memset(report, 0, sizeof *report);
     if (device_ms) *device_ms = 0.0;
     const bool differs = structure_differs(img_docs, img_lists, img_len.data(), num_docs, nlists, list_offsets, report);
     verify_host_s[0] = seconds_since(t0);
     if (differs) return DS2I_OK;
     // ---- the device: a bare upload (no tables, no transcoding), the kernel, close
-    if (device < 0 || device >= ds2i_hip_device_count()) return ds2i_set_error(DS2I_EDEVICE, "ds2i_hip_verify_collection: no such HIP device");
+    rc = check_device("ds2i_hip_verify_collection", device);
+    if (rc != DS2I_OK) return rc;
     ds2i_hip_index* idx = nullptr;
     const auto t1 = std::chrono::steady_clock::now();
     rc = ds2i_index_open_bare(device, index_kind, image, bytes, &idx);

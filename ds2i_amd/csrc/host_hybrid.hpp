@@ -25,6 +25,7 @@
 #include "abi_structs.hpp"
 #include "host_encode.hpp"
 #include "host_index.hpp"
+#include "host_parallel.hpp"
 
 namespace ds2i_host {
 
@@ -181,42 +182,37 @@ public:
 
     // computes every block's hull (threaded). Afterwards min_space()/max_space() are known.
     void analyse(int threads) {
-        const size_t V = m_lists.size();
-        std::atomic<size_t> next(0);
-        auto worker = [&]() {
-            std::vector<hybrid_point> hull;
+        threads = thread_count(threads);
+        std::vector<std::vector<hybrid_point>> hulls(threads); // every worker's scratch
+        parallel_for(m_lists.size(), (unsigned)threads, [&](uint64_t t, unsigned w) {
+            std::vector<hybrid_point>& hull = hulls[w];
             uint32_t dbuf[BLOCK], fbuf[BLOCK];
-            for (;;) {
-                const size_t t = next.fetch_add(1);
-                if (t >= V) break;
-                list_t& L = m_lists[t];
-                std::vector<uint32_t> vd, vf;
-                if (L.is_virtual) m_provider(t, vd, vf);
-                const std::vector<uint32_t>& D = L.is_virtual ? vd : L.docs;
-                const std::vector<uint32_t>& F = L.is_virtual ? vf : L.freqs;
-                const uint64_t n = D.size(), blocks = ceil_div(n, (uint64_t)BLOCK);
-                L.hull_off.assign(2 * blocks + 1, 0);
-                L.hull.clear();
-                uint32_t last_doc = uint32_t(-1), block_base = 0;
-                size_t k = 0;
-                for (uint64_t b = 0; b < blocks; ++b) {
-                    const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (uint32_t)(n % BLOCK);
-                    for (uint32_t i = 0; i < cur; ++i, ++k) {
-                        dbuf[i] = D[k] - last_doc - 1;
-                        last_doc = D[k];
-                        fbuf[i] = F[k] - 1;
-                    }
-                    hybrid_block_points(dbuf, last_doc - block_base - (cur - 1), cur, L.access.empty() ? 0 : L.access[2 * b], m_model, hull);
-                    L.hull.insert(L.hull.end(), hull.begin(), hull.end());
-                    L.hull_off[2 * b + 1] = (uint32_t)L.hull.size();
-                    hybrid_block_points(fbuf, uint32_t(-1), cur, L.access.empty() ? 0 : L.access[2 * b + 1], m_model, hull);
-                    L.hull.insert(L.hull.end(), hull.begin(), hull.end());
-                    L.hull_off[2 * b + 2] = (uint32_t)L.hull.size();
-                    block_base = last_doc + 1;
+            list_t& L = m_lists[t];
+            std::vector<uint32_t> vd, vf;
+            if (L.is_virtual) m_provider(t, vd, vf);
+            const std::vector<uint32_t>& D = L.is_virtual ? vd : L.docs;
+            const std::vector<uint32_t>& F = L.is_virtual ? vf : L.freqs;
+            const uint64_t n = D.size(), blocks = ceil_div(n, (uint64_t)BLOCK);
+            L.hull_off.assign(2 * blocks + 1, 0);
+            L.hull.clear();
+            uint32_t last_doc = uint32_t(-1), block_base = 0;
+            size_t k = 0;
+            for (uint64_t b = 0; b < blocks; ++b) {
+                const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (uint32_t)(n % BLOCK);
+                for (uint32_t i = 0; i < cur; ++i, ++k) {
+                    dbuf[i] = D[k] - last_doc - 1;
+                    last_doc = D[k];
+                    fbuf[i] = F[k] - 1;
                 }
+                hybrid_block_points(dbuf, last_doc - block_base - (cur - 1), cur, L.access.empty() ? 0 : L.access[2 * b], m_model, hull);
+                L.hull.insert(L.hull.end(), hull.begin(), hull.end());
+                L.hull_off[2 * b + 1] = (uint32_t)L.hull.size();
+                hybrid_block_points(fbuf, uint32_t(-1), cur, L.access.empty() ? 0 : L.access[2 * b + 1], m_model, hull);
+                L.hull.insert(L.hull.end(), hull.begin(), hull.end());
+                L.hull_off[2 * b + 2] = (uint32_t)L.hull.size();
+                block_base = last_doc + 1;
             }
-        };
-        run_threads(threads, worker);
+        });
         m_analysed = true;
     }
 
@@ -255,52 +251,46 @@ public:
         if (!m_analysed) analyse(threads);
         const size_t V = m_lists.size();
         std::vector<bytes_t> enc(V);
-        std::atomic<size_t> next(0);
         std::atomic<uint64_t> tc[6];
         for (auto& c : tc) c = 0;
-        auto worker = [&]() {
+        parallel_for(V, (unsigned)thread_count(threads), [&](uint64_t t, unsigned) {
             uint32_t dbuf[BLOCK], fbuf[BLOCK];
-            for (;;) {
-                const size_t t = next.fetch_add(1);
-                if (t >= V) break;
-                list_t const& L = m_lists[t];
-                std::vector<uint32_t> vd, vf;
-                if (L.is_virtual) m_provider(t, vd, vf);
-                const std::vector<uint32_t>& D = L.is_virtual ? vd : L.docs;
-                const std::vector<uint32_t>& F = L.is_virtual ? vf : L.freqs;
-                bytes_t& out = enc[t];
-                const uint32_t n = (uint32_t)D.size();
-                vbyte_encode(n, out);
-                const uint64_t blocks = ceil_div((uint64_t)n, (uint64_t)BLOCK);
-                const size_t begin_maxs = out.size(), begin_endpoints = begin_maxs + 4 * blocks,
-                             begin_blocks = begin_endpoints + 4 * (blocks - 1);
-                out.resize(begin_blocks);
-                uint32_t last_doc = uint32_t(-1), block_base = 0;
-                size_t k = 0;
-                for (uint64_t b = 0; b < blocks; ++b) {
-                    const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (n % BLOCK);
-                    for (uint32_t i = 0; i < cur; ++i, ++k) {
-                        dbuf[i] = D[k] - last_doc - 1;
-                        last_doc = D[k];
-                        fbuf[i] = F[k] - 1;
-                    }
-                    std::memcpy(&out[begin_maxs + 4 * b], &last_doc, 4);
-                    for (int side = 0; side < 2; ++side) {
-                        const hybrid_point* h = L.hull.data() + L.hull_off[2 * b + side];
-                        const hybrid_point& c = h[hybrid_choose(h, L.hull_off[2 * b + side + 1] - L.hull_off[2 * b + side], rate)];
-                        mixed_encode_type((mixed_type)c.type, c.b, side ? fbuf : dbuf,
-                                          side ? uint32_t(-1) : last_doc - block_base - (cur - 1), cur, out);
-                        if (cur == BLOCK) ++tc[3 * side + c.type];
-                    }
-                    if (b != blocks - 1) {
-                        const uint32_t ep = (uint32_t)(out.size() - begin_blocks);
-                        std::memcpy(&out[begin_endpoints + 4 * b], &ep, 4);
-                    }
-                    block_base = last_doc + 1;
+            list_t const& L = m_lists[t];
+            std::vector<uint32_t> vd, vf;
+            if (L.is_virtual) m_provider(t, vd, vf);
+            const std::vector<uint32_t>& D = L.is_virtual ? vd : L.docs;
+            const std::vector<uint32_t>& F = L.is_virtual ? vf : L.freqs;
+            bytes_t& out = enc[t];
+            const uint32_t n = (uint32_t)D.size();
+            vbyte_encode(n, out);
+            const uint64_t blocks = ceil_div((uint64_t)n, (uint64_t)BLOCK);
+            const size_t begin_maxs = out.size(), begin_endpoints = begin_maxs + 4 * blocks,
+                         begin_blocks = begin_endpoints + 4 * (blocks - 1);
+            out.resize(begin_blocks);
+            uint32_t last_doc = uint32_t(-1), block_base = 0;
+            size_t k = 0;
+            for (uint64_t b = 0; b < blocks; ++b) {
+                const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (n % BLOCK);
+                for (uint32_t i = 0; i < cur; ++i, ++k) {
+                    dbuf[i] = D[k] - last_doc - 1;
+                    last_doc = D[k];
+                    fbuf[i] = F[k] - 1;
                 }
+                std::memcpy(&out[begin_maxs + 4 * b], &last_doc, 4);
+                for (int side = 0; side < 2; ++side) {
+                    const hybrid_point* h = L.hull.data() + L.hull_off[2 * b + side];
+                    const hybrid_point& c = h[hybrid_choose(h, L.hull_off[2 * b + side + 1] - L.hull_off[2 * b + side], rate)];
+                    mixed_encode_type((mixed_type)c.type, c.b, side ? fbuf : dbuf,
+                                      side ? uint32_t(-1) : last_doc - block_base - (cur - 1), cur, out);
+                    if (cur == BLOCK) ++tc[3 * side + c.type];
+                }
+                if (b != blocks - 1) {
+                    const uint32_t ep = (uint32_t)(out.size() - begin_blocks);
+                    std::memcpy(&out[begin_endpoints + 4 * b], &ep, 4);
+                }
+                block_base = last_doc + 1;
             }
-        };
-        run_threads(threads, worker);
+        });
         block_index_builder builder(CODEC_MIXED, m_num_docs);
         for (size_t t = 0; t < V; ++t) {
             builder.add_encoded_list(enc[t].data(), enc[t].size());
@@ -327,27 +317,23 @@ public:
         const size_t V = m_lists.size();
         std::vector<uint64_t> blk0(V + 1, 0);
         for (size_t t = 0; t < V; ++t) blk0[t + 1] = blk0[t] + ceil_div((uint64_t)m_lists[t].docs.size(), (uint64_t)BLOCK);
-        std::atomic<size_t> next(0);
-        auto worker = [&]() {
-            std::vector<hybrid_point> hull;
-            for (;;) {
-                const size_t t = next.fetch_add(1);
-                if (t >= V) break;
-                list_t& L = m_lists[t];
-                const uint64_t n = L.docs.size(), blocks = blk0[t + 1] - blk0[t];
-                L.hull_off.assign(2 * blocks + 1, 0);
-                L.hull.clear();
-                for (uint64_t b = 0; b < blocks; ++b) {
-                    const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (uint32_t)(n % BLOCK);
-                    for (int side = 0; side < 2; ++side) {
-                        hybrid_hull_of(recs[2 * (blk0[t] + b) + side], cur, L.access.empty() ? 0 : L.access[2 * b + side], m_model, hull);
-                        L.hull.insert(L.hull.end(), hull.begin(), hull.end());
-                        L.hull_off[2 * b + side + 1] = (uint32_t)L.hull.size();
-                    }
+        threads = thread_count(threads);
+        std::vector<std::vector<hybrid_point>> hulls(threads); // every worker's scratch
+        parallel_for(V, (unsigned)threads, [&](uint64_t t, unsigned w) {
+            std::vector<hybrid_point>& hull = hulls[w];
+            list_t& L = m_lists[t];
+            const uint64_t n = L.docs.size(), blocks = blk0[t + 1] - blk0[t];
+            L.hull_off.assign(2 * blocks + 1, 0);
+            L.hull.clear();
+            for (uint64_t b = 0; b < blocks; ++b) {
+                const uint32_t cur = ((b + 1) * BLOCK <= n) ? BLOCK : (uint32_t)(n % BLOCK);
+                for (int side = 0; side < 2; ++side) {
+                    hybrid_hull_of(recs[2 * (blk0[t] + b) + side], cur, L.access.empty() ? 0 : L.access[2 * b + side], m_model, hull);
+                    L.hull.insert(L.hull.end(), hull.begin(), hull.end());
+                    L.hull_off[2 * b + side + 1] = (uint32_t)L.hull.size();
                 }
             }
-        };
-        run_threads(threads, worker);
+        });
         m_analysed = true;
     }
     // hull of one part (analysed builders): null if there is no such part
@@ -375,13 +361,7 @@ private:
         std::vector<hybrid_point> hull;  // concatenated hulls
         std::vector<uint32_t> hull_off;  // 2 * blocks + 1 offsets (docs block 0, freqs block 0, docs block 1, ...)
     };
-    template <class F>
-    static void run_threads(int threads, F& f) {
-        if (threads <= 0) threads = (int)std::max(1u, std::thread::hardware_concurrency());
-        std::vector<std::thread> pool;
-        for (int i = 0; i < threads; ++i) pool.emplace_back(f);
-        for (auto& th : pool) th.join();
-    }
+    static int thread_count(int threads) { return threads > 0 ? threads : (int)std::max(1u, std::thread::hardware_concurrency()); } // (<= 0: the machine's)
     uint64_t m_num_docs;
     hybrid_model m_model;
     std::vector<list_t> m_lists;

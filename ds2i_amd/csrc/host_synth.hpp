@@ -9,6 +9,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "../../include/ds2i_build.h"
+
 namespace ds2i_host {
 
 struct synth_params {
@@ -27,6 +29,15 @@ struct synth_params {
     uint32_t topics = 0;
     uint32_t topic_boost = 0;
 };
+
+// the published form (ds2i_build.h) of the parameters
+inline synth_params to_params(const ds2i_synth_params* p) {
+    synth_params s;
+    s.seed = p->seed; s.num_docs = p->num_docs; s.num_terms = p->num_terms; s.zipf_exp = p->zipf_exp;
+    s.top_df_frac = p->top_df_frac; s.min_len = p->min_len; s.clustered_every = p->clustered_every;
+    s.topics = p->topics; s.topic_boost = p->topic_boost;
+    return s;
+}
 
 inline uint32_t synth_home_topic(synth_params const& p, uint32_t term) {
     uint64_t x = p.seed ^ (0xA24BAED4963EE407ull * (uint64_t(term) + 1));

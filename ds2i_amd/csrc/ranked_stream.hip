@@ -35,6 +35,9 @@
 
 #include "device_enum.hpp"
 #include "device_score.hpp"
+#ifdef DS2I_RS_PHASE
+#define DS2I_STREAM_PHASE
+#endif
 #include "stream_common.hpp"
 #include "dispatch.hpp"
 #include "launchers.hpp"
@@ -83,9 +86,8 @@ struct LdsRS {
 // NK > 1 (ranked_and with k > 64; topk_queue has no limit, queries.hpp:152-197): NK scores per lane (TopKBig<NK>: k <= 64 NK) at the
 // price of NK registers and NK times the work per heap insert -- fewer waves per SIMD. These instantiations also take one-term
 // queries (nt = 1 in a capacity-4 launch: no list 1, every test on it passes), which otherwise keep their class kernel.
-#define RS_WAVES_K(NT, NK) ((NK) == 1 ? RS_WAVES(NT) : (RS_WAVES(NT) < ((NK) <= 4 ? 4 : 3) ? RS_WAVES(NT) : ((NK) <= 4 ? 4 : 3)))
 template <int NT, bool STATS, bool AND = false, bool FREQS = false, int NK = 1>
-__global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) DS2I_KN(k_ranked_stream)(BatchArgs a_unused) {
+__global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_ranked_stream)(BatchArgs a_unused) {
     static_assert(AND || !FREQS, "FREQS is a variant of AND");
     static_assert(NK == 1 || !AND, "the big heap is ranked_and's");
     static_assert(NT >= 2 && NT <= 16, "list capacities 2..16");
@@ -100,31 +102,10 @@ __global__ void __launch_bounds__(64, RS_WAVES_K(NT, NK)) DS2I_KN(k_ranked_strea
     // Stats::phase_cycles (profiles/probes/rs_phase_probe.py). PT(slot) closes the interval since the previous PT and books it.
     unsigned long long pt[PH_COUNT] = {};
     unsigned long long pt_prev = __builtin_readcyclecounter();
-#define PT(slot) do { const unsigned long long t_ = __builtin_readcyclecounter(); pt[slot] += t_ - pt_prev; pt_prev = t_; } while (0)
-#else
-#define PT(slot) ((void)0)
 #endif
 #ifdef DS2I_LINE_COUNT
     // diagnostic build: distinct 128-byte lines requested by the hand-placed gathers, by purpose (reported through Stats::phase_cycles)
     unsigned long long lc[PH_COUNT] = {};
-    // lines touched by one wave instruction whose active lanes read `bytes` bytes (lanes in ascending address order)
-    auto lines_of = [&](const void* addr, bool active, uint32_t bytes) -> uint32_t {
-        const unsigned long long lo = (unsigned long long)(uintptr_t)addr >> 7, hi = ((unsigned long long)(uintptr_t)addr + bytes - 1) >> 7;
-        const uint64_t act = ballot(active);
-        unsigned long long prev_hi = ~0ull; // previous ACTIVE lane's last line
-        uint32_t n = 0;
-        for (uint64_t m = act; m; m &= m - 1) {
-            const uint32_t src = (uint32_t)__builtin_ctzll(m);
-            const unsigned long long l = ((unsigned long long)bcast((uint32_t)(lo >> 32), src) << 32) | bcast((uint32_t)lo, src);
-            const unsigned long long h = ((unsigned long long)bcast((uint32_t)(hi >> 32), src) << 32) | bcast((uint32_t)hi, src);
-            n += (uint32_t)(h - l + 1) - ((l == prev_hi) ? 1u : 0u);
-            prev_hi = h;
-        }
-        return n;
-    };
-#define LC(slot, expr) lc[slot] += (expr)
-#else
-#define LC(slot, expr) ((void)0)
 #endif
     const uint32_t nslice = rs_args()->nslice;
     for (uint32_t tkt = blockIdx.x; tkt < nslice; tkt += gridDim.x) {

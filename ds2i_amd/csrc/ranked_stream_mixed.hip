@@ -31,10 +31,12 @@
 
 #include "device_enum.hpp"
 #include "device_score.hpp"
+#include "stream_common.hpp"
 #include "dispatch.hpp"
 #include "launchers.hpp"
 
 using namespace ds2i_dev;
+using namespace ds2i_dev::stream;
 
 namespace {
 
@@ -61,11 +63,9 @@ struct LdsRS {
     uint32_t exc[EXC_LDS_DW];    // Simple16 scratch + field table
 };
 
-// first block >= from of a list whose block_max >= lb, with its table words; rows = the list's interleaved skip table
-// ({block_max, end offset} per block), wtab = its block weights. 64 rows per probe: the 64 after `from`, then a 64-ary
-// search (the reference scans block_max linearly, block_posting_list.hpp:134-137).
-struct Found { uint32_t blk, bmax, base, ep; float w; };
-DS2I_DEV bool find_block_rows(const uint2* tab, const float* wtab, uint32_t nb, uint32_t from, uint32_t lb, Found& o) {
+// stream_common.hpp's find_block_rows with the first probe's rows loaded HERE, after the `from >= nb` test (the shared form takes them
+// as an argument its caller requested a round trip earlier, whatever the test says: the two compile to different code)
+DS2I_DEV bool find_block_rows_late(const uint2* tab, const float* wtab, uint32_t nb, uint32_t from, uint32_t lb, Found& o) {
     const uint32_t lane = lane_id();
     if (from >= nb) return false;
     float wv = 0.f;
@@ -111,84 +111,6 @@ DS2I_DEV bool find_block_rows(const uint2* tab, const float* wtab, uint32_t nb, 
     return true;
 }
 
-// position of c in the sorted block d[128] (valid iff `want`): binary search per lane
-DS2I_DEV bool rs_member(const uint32_t* d, uint32_t c, bool want, uint32_t& pos) {
-    uint32_t idx = 0;
-    if (want) {
-#pragma unroll
-        for (uint32_t step = 64; step; step >>= 1)
-            if (d[idx + step - 1] < c) idx += step;
-    }
-    pos = idx;
-    return want && d[idx] == c;
-}
-
-DS2I_DEV void store_topk_rs(float* topk, uint32_t* topk_len, uint32_t k, uint32_t slot, const TopK& tk) {
-    const uint32_t lane = lane_id();
-    if (lane < k) topk[(size_t)slot * k + lane] = tk.v;
-    if (lane == 0) topk_len[slot] = tk.n;
-}
-DS2I_DEV void store_topk_rs(float* topk, uint32_t* topk_len, uint32_t k, uint32_t slot, const TopKD& tk, uint32_t* docs) {
-    const uint32_t lane = lane_id();
-    if (lane < k) { topk[(size_t)slot * k + lane] = tk.v; docs[(size_t)slot * k + lane] = tk.d; }
-    if (lane == 0) topk_len[slot] = tk.n;
-}
-
-template <int I, int N, class F>
-DS2I_DEV void rs_for(F& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        rs_for<I + 1, N>(f);
-    }
-}
-template <int I, int LO, class F>
-DS2I_DEV void rs_for_down(F& f) { // I-1 down to LO
-    if constexpr (I > LO) {
-        f(std::integral_constant<int, I - 1>{});
-        rs_for_down<I - 1, LO>(f);
-    }
-}
-
-// The argument block is ~40 pointers and scalars. Read as a by-value kernel argument the compiler loads all of them at
-// kernel entry and keeps them in SGPRs for the kernel's lifetime (the old kernels sit at the 102-SGPR limit with three
-// VGPRs of spilled scalars because of it). Here the kernarg segment is addressed explicitly: the few hot fields are read
-// where a unit starts, the cold ones at their use site through a pointer the optimiser cannot see through (so the loads
-// stay where they are written instead of being hoisted above the loops).
-typedef const BatchArgs __attribute__((address_space(4))) * KArgs; // (constant address space: uniform reads are s_load)
-DS2I_DEV KArgs rs_args() {
-    KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(p));
-    return p;
-}
-
-// ---- loads the compiler must not count. hipcc drains vmcnt to 0 wherever control flow joins with a load pending on
-// some path, which would put every round trip back on the critical path; these are issued and waited for by hand.
-// (i) block bytes: LDS-DMA, global -> LDS with no register in between (nothing the compiler could copy or spill early);
-DS2I_DEV uint32_t rs_lds_offset(const void* p) { return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p; }
-// 512 bytes at g (4-byte aligned) -> LDS byte offset `lds`; voff = lane * 4. M0 is the DMA's LDS base: compiler-reserved,
-// so it is saved, set and restored inside each statement.
-DS2I_DEV void rs_prefetch512(const uint8_t* g, uint32_t lds, uint32_t voff) {
-    uint32_t keep;
-    // (the instruction offset moves the global AND the LDS address: measured, profiles/probes/ldsdma_probe.hip)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\tglobal_load_lds_dword %1, %2 offset:256\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(g), "s"(uniform(lds)) : "memory");
-}
-// (ii) range-table bytes: LDS-DMA as well -- tab[off] of every lane lands, zero-extended, in the dword at LDS byte offset
-// lds + 4 * lane (measured with the same probe). A hand-issued load into a VGPR is not an option: for the compiler the
-// destination is written when the statement ends, and under register pressure it did copy the still-pending register
-// (tests/asm_audit.py found it before the GPU did).
-DS2I_DEV void rs_gather_u8(const uint8_t* tab, uint32_t off, uint32_t lds) {
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_ubyte %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(off), "s"(tab), "s"(uniform(lds)) : "memory");
-}
-// one lane of a VGPR takes a wave-uniform value (v_writelane_b32; there is no builtin for it in this toolchain)
-template <int LANE> DS2I_DEV void rs_writelane(uint32_t& dst, uint32_t v) {
-    const uint32_t sv = uniform(v);
-    asm("v_writelane_b32 %0, %1, %2" : "+v"(dst) : "s"(sv), "n"(LANE));
-}
-template <int N> DS2I_DEV void rs_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // optpfor / interpolative block -> gaps or freqs-1 in (v0, v1), value i in lane i & 63, slot i >> 6. The common case
 // (full block inside the staged 512 bytes) never touches global memory; anything else takes the general decoder and is
 // made opaque, so that no output of this function is ever "pending on vmcnt" for the compiler: the caller's prefetches
@@ -227,25 +149,6 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) DS2I_KN(k_ranked_stream_mixe
 #ifdef DS2I_LINE_COUNT
     // diagnostic build: distinct 128-byte lines requested by the hand-placed gathers, by purpose (reported through Stats::phase_cycles)
     unsigned long long lc[PH_COUNT] = {};
-    // lines touched by one wave instruction whose active lanes read `bytes` bytes at ascending addresses
-    auto lines_of = [&](const void* addr, bool active, uint32_t bytes) -> uint32_t {
-        const unsigned long long lo = (unsigned long long)(uintptr_t)addr >> 7, hi = ((unsigned long long)(uintptr_t)addr + bytes - 1) >> 7;
-        const uint64_t act = ballot(active);
-        // previous ACTIVE lane's last line
-        unsigned long long prev_hi = ~0ull;
-        uint32_t n = 0;
-        for (uint64_t m = act; m; m &= m - 1) {
-            const uint32_t src = (uint32_t)__builtin_ctzll(m);
-            const unsigned long long l = ((unsigned long long)bcast((uint32_t)(lo >> 32), src) << 32) | bcast((uint32_t)lo, src);
-            const unsigned long long h = ((unsigned long long)bcast((uint32_t)(hi >> 32), src) << 32) | bcast((uint32_t)hi, src);
-            n += (uint32_t)(h - l + 1) - ((l == prev_hi) ? 1u : 0u);
-            prev_hi = h;
-        }
-        return n;
-    };
-#define LC(slot, expr) lc[slot] += (expr)
-#else
-#define LC(slot, expr) ((void)0)
 #endif
     const uint32_t nslice = rs_args()->nslice;
     for (uint32_t tkt = blockIdx.x; tkt < nslice; tkt += gridDim.x) {
@@ -585,7 +488,7 @@ __global__ void __launch_bounds__(64, RS_WAVES(NT)) DS2I_KN(k_ranked_stream_mixe
                             const uint32_t amin = todo0 ? bcast(dB0, (uint32_t)__builtin_ctzll(todo0)) : bcast(dB1, (uint32_t)__builtin_ctzll(todo1));
                             if (curj == 0xFFFFFFFFu || amin > bmj) {
                                 Found fb;
-                                const bool found = find_block_rows(tabj, wtabj, nbj, curj + 1u, amin, fb);
+                                const bool found = find_block_rows_late(tabj, wtabj, nbj, curj + 1u, amin, fb);
                                 LC(PH_FIND, 1);
                                 if (!found) { // list j has nothing >= amin: no later document of list 0 can be a result either
                                     s_bm_examined += 1;

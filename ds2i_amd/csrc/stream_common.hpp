@@ -1,5 +1,5 @@
-// Pieces shared by the software-pipelined stream kernels (ranked_stream.hip: ranked_and / and; union_stream.hip: wand /
-// maxscore / ranked_or): block search over a list's interleaved skip table, membership in a decoded block, explicit kernarg
+// Pieces shared by the software-pipelined stream kernels (ranked_stream.hip: ranked_and / and; ranked_stream_mixed.hip: ranked_and
+// on block_mixed; union_stream.hip: wand / maxscore / ranked_or): block search over a list's interleaved skip table, membership in a decoded block, explicit kernarg
 // addressing, and the loads that are issued and waited for BY HAND (LDS-DMA block prefetch, LDS-DMA byte gathers, counted
 // s_waitcnt). gfx950 / CDNA4, wave64. Everything here is DS2I_DEV (force-inlined device code).
 #pragma once
@@ -166,6 +166,12 @@ DS2I_DEV void rs_prefetch_blk(const uint8_t* g, uint32_t lds, const uint32_t* gx
                  : "=&s"(keep) : "v"(voff), "s"(g), "s"(uniform(lds)), "s"(gx), "s"(uniform(lds_x)) : "memory");
 }
 static constexpr int PF_LOADS = 3; // hand-issued loads of one block prefetch
+// ... the 512 bytes alone (k_ranked_stream_mixed: a block_mixed index has no side slots)
+DS2I_DEV void rs_prefetch512(const uint8_t* g, uint32_t lds, uint32_t voff) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\tglobal_load_lds_dword %1, %2 offset:256\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(g), "s"(uniform(lds)) : "memory");
+}
 // (i') one dword at g, read past this CU's L1 (sc1: other CUs update it with atomics) -> the 64 dwords at LDS byte offset lds
 DS2I_DEV void rs_fetch_word(const unsigned int* g, uint32_t lds) {
     uint32_t keep;
@@ -263,5 +269,45 @@ DS2I_DEV float rs_dtw_bound(uint32_t freq, float norm_len) {
     return f * __builtin_amdgcn_rcpf(f + 1.2f * (0.5f + 0.5f * norm_len)) * (1.0f + 1.0f / 1048576.0f);
 }
 
+// waves per SIMD of a stream kernel whose heap holds NK scores per lane (k <= 64 NK): the NK registers and NK times the work per
+// heap insert leave room for 4 (NK <= 4) or 3 waves at the most; NK = 1 keeps the kernel's own figure
+constexpr int waves_for_k(int base_waves, int nk) {
+    return nk == 1 ? base_waves : (base_waves < (nk <= 4 ? 4 : 3) ? base_waves : (nk <= 4 ? 4 : 3));
+}
+
+// (-DDS2I_LINE_COUNT) distinct 128-byte lines touched by one wave instruction whose active lanes read `bytes` bytes at ascending addresses
+DS2I_DEV uint32_t lines_of(const void* addr, bool active, uint32_t bytes) {
+    const unsigned long long lo = (unsigned long long)(uintptr_t)addr >> 7, hi = ((unsigned long long)(uintptr_t)addr + bytes - 1) >> 7;
+    const uint64_t act = ballot(active);
+    unsigned long long prev_hi = ~0ull; // previous ACTIVE lane's last line
+    uint32_t n = 0;
+    for (uint64_t m = act; m; m &= m - 1) {
+        const uint32_t src = (uint32_t)__builtin_ctzll(m);
+        const unsigned long long l = ((unsigned long long)bcast((uint32_t)(lo >> 32), src) << 32) | bcast((uint32_t)lo, src);
+        const unsigned long long h = ((unsigned long long)bcast((uint32_t)(hi >> 32), src) << 32) | bcast((uint32_t)hi, src);
+        n += (uint32_t)(h - l + 1) - ((l == prev_hi) ? 1u : 0u);
+        prev_hi = h;
+    }
+    return n;
+}
+
 } // namespace stream
 } // namespace ds2i_dev
+
+// ---- diagnostic builds of the stream kernels: what a wave spends where, reported through Stats::phase_cycles. Each macro books into an
+// array the kernel declares under the same flag, and is nothing in the product build.
+// -DDS2I_RS_PHASE (ranked_stream.hip) / -DDS2I_US_PHASE (union_stream.hip): the unit names its flag as DS2I_STREAM_PHASE before it
+// includes this header. PT(slot) closes the interval of shader cycles since the previous PT and books it in pt[slot]; EV(slot, n) counts events.
+#ifdef DS2I_STREAM_PHASE
+#define PT(slot) do { const unsigned long long t_ = __builtin_readcyclecounter(); pt[slot] += t_ - pt_prev; pt_prev = t_; } while (0)
+#define EV(slot, n) pt[slot] += (n)
+#else
+#define PT(slot) ((void)0)
+#define EV(slot, n) ((void)0)
+#endif
+// -DDS2I_LINE_COUNT: LC(slot, lines) books 128-byte lines requested by the hand-placed gathers, by purpose, in lc[slot] (lines_of above)
+#ifdef DS2I_LINE_COUNT
+#define LC(slot, expr) lc[slot] += (expr)
+#else
+#define LC(slot, expr) ((void)0)
+#endif

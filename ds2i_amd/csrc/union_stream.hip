@@ -37,6 +37,9 @@
 
 #include "device_enum.hpp"
 #include "device_score.hpp"
+#ifdef DS2I_US_PHASE
+#define DS2I_STREAM_PHASE
+#endif
 #include "stream_common.hpp"
 #include "dispatch.hpp"
 #include "launchers.hpp"
@@ -68,9 +71,8 @@ struct LdsUS {
 enum { LS_CUR = 0, LS_BMAX, LS_N, LS_BB, LS_LOLO, LS_LOHI, LS_QW, LS_TLLO, LS_TLHI, LS_RSC };
 
 // NK > 1 (k > 64; topk_queue has no limit, queries.hpp:152-197): NK scores per lane (TopKBig<NK>: k <= 64 NK), fewer waves per SIMD
-#define US_WAVES_K(NT, NK) ((NK) == 1 ? US_WAVES(NT) : (US_WAVES(NT) < ((NK) <= 4 ? 4 : 3) ? US_WAVES(NT) : ((NK) <= 4 ? 4 : 3)))
 template <int NT, bool STATS, int NK = 1>
-__global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) DS2I_KN(k_union_stream)(BatchArgs a_unused) {
+__global__ void __launch_bounds__(64, waves_for_k(US_WAVES(NT), NK)) DS2I_KN(k_union_stream)(BatchArgs a_unused) {
     static_assert(NT >= 2 && NT <= 16, "list capacities 2..16");
     __shared__ LdsUS<NT> L;
     const uint32_t lane = lane_id();
@@ -83,11 +85,6 @@ __global__ void __launch_bounds__(64, US_WAVES_K(NT, NK)) DS2I_KN(k_union_stream
     // reported through Stats::phase_cycles (profiles/probes/us_phase_probe.py). PT(slot) closes the interval since the previous PT.
     unsigned long long pt[PH_COUNT] = {};
     unsigned long long pt_prev = __builtin_readcyclecounter();
-#define PT(slot) do { const unsigned long long t_ = __builtin_readcyclecounter(); pt[slot] += t_ - pt_prev; pt_prev = t_; } while (0)
-#define EV(slot, n) pt[slot] += (n)
-#else
-#define PT(slot) ((void)0)
-#define EV(slot, n) ((void)0)
 #endif
     const uint32_t nslice = rs_args()->nslice;
     for (uint32_t tkt = blockIdx.x; tkt < nslice; tkt += gridDim.x) {
