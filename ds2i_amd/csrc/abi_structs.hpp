@@ -167,6 +167,9 @@ struct RmwLevels {
     // it; or_query ORs its words into the union instead of decoding its blocks.
     static __host__ __device__ bool has_bitmap(uint32_t n, uint32_t num_docs) { return (uint64_t)n * 64u >= num_docs; }
     static __host__ __device__ uint64_t bitmap_bytes(uint32_t num_docs) { return ((((uint64_t)num_docs + 31u) / 32u * 4u + 63u) & ~63ull) + 64u; }
+    // k_ranked_stream fetches one byte of list 1 ahead for EVERY candidate: the bitmap's instead of the membership hint's where the
+    // list has a bitmap and a 128-byte line of it (1024 doc-ids) covers no fewer doc-ids than a line of hints (128 << shift)
+    static __host__ __device__ bool bitmap_first(uint32_t n, uint32_t num_docs, uint32_t shift) { return has_bitmap(n, num_docs) && shift <= 3u; }
 };
 struct BmwArgs {
     const uint8_t* arena;

@@ -14,7 +14,8 @@
 //                              posting gets a bound of its own list-0 term score from its freq alone
 //         stage B (block i)    its range-table gathers -- issued only for the candidates whose own bound + the other lists'
 //                              maxima could enter the heap -- are consumed: zero byte = the document is in no intersection;
-//                              otherwise own bound + own bytes against the heap threshold, then the membership hints
+//                              otherwise own bound + own bytes against the heap threshold, then the membership hints (a dense
+//                              list's exact bitmap in their place)
 //         stage C (block i)    only if somebody survived: norm_len, exact list-0 score, then list 1 .. NT-1 in order (locate
 //                              block -> block-weight test -> decode -> membership -> score), heap insert
 //     so the gather round trip of a block is covered by the decode of the next one and the block-bytes round trip by a
@@ -127,13 +128,6 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         tk.init(a->k);
         unsigned long long and_count = 0; // (AND: results of this unit)
         unsigned long long and_fsum = 0;  // (FREQS: this lane's share of the unit's freq checksum)
-        // (AND, batches prepared with want_matches: the doc-ids of the intersection, in order, into the unit's segment of the match
-        // buffer -- 128 slots per block of list 0 from the query's offset, compacted by ds2i_hip_batch_fetch_matches)
-        uint32_t* and_out = nullptr;
-        if constexpr (AND) {
-            uint32_t* const om = a->out_matches;
-            if (om) and_out = om + rs_uniform64(a->match_off[q]) + 128ull * blk_begin;
-        }
         // ---- list 0: the stream
         const uint32_t n0 = uniform(qt[0].n), nb0 = (n0 + 127u) >> 7;
         const uint32_t vl0 = 1u + (n0 >= (1u << 7)) + (n0 >= (1u << 14)) + (n0 >= (1u << 21)) + (n0 >= (1u << 28));
@@ -143,7 +137,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         const uint32_t* const xs0 = a->xslots + (size_t)XSLOT_DW * bb0; // list 0's side slots
         // ---- lists 1 .. NT-1: range table (hot), the rest of the QTerm is read when a candidate gets that far
         const uint8_t* rt[NT];
-        uint32_t rsh[NT];
+        uint32_t rsh[NT]; // (read a shift through shift_of() below: rsh[1] also carries the RS_BM bit)
         float rsc[NT];
         auto bind_one = [&](auto jc) __attribute__((always_inline)) {
             constexpr int j = decltype(jc)::value;
@@ -165,20 +159,18 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         }
         // the collection's shortest document: a posting of list 0 with freq f scores at most qw0 * doc_term_weight(f, min_nl) there
         const float min_nl = a->min_norm_len;
-        const long long hdelta = a->rmh ? (long long)(a->rmh - a->rmw) : 0ll; // hint of an entry = the byte at the same offset of the parallel buffer
-        // Three and four lists: the byte fetched ahead for every candidate is list 1's HINT, not its weight. A weight byte lets a
-        // candidate through whenever its range holds any posting (one candidate in 4..6, each then costing a line per further
-        // list); the hint also settles the ranges with a single posting, so that the further lists are asked about a few per cent
-        // of the candidates only -- first their hints, then, for what is left, every list's weight for the threshold test.
-        // (Two lists: the weight stays first, its threshold test removes more than the hint does.)
-        const bool hint_first = (AND || RS_HINT_FIRST(NT)) && hdelta != 0; // (AND: the hint is the answer, the weight says nothing it needs)
-        const uint8_t* const gt1 = hint_first ? rt[1] + hdelta : rt[1];
         // block of list j whose doc-ids and freqs are in L.dj[j-1] / L.fj[j-1] (cur = ~0: none) and its block_max. Only stage C
         // touches them: they live in the lanes of one VGPR (v_readlane / v_writelane at a constant lane).
         // Together with the list's geometry (postings, first row in the per-block tables, arena offset, query weight): read once
         // per unit, here, so that stage C starts with its first memory request instead of a dependent read of the QTerm.
-        // (nine lanes per list: one VGPR up to 8 lists, three for 16)
-        constexpr int NCOLD = ((NT - 1) * 9 + 63) / 64;
+        // (nine lanes per list; behind them the unit's own scalars that only rare paths read, X_*: one VGPR up to 6 lists, two for
+        // 8, three for 16)
+        enum { C_CUR = 0, C_BMAX = 1, C_N = 2, C_BB = 3, C_LOLO = 4, C_LOHI = 5, C_QW = 6, C_TLLO = 7, C_TLHI = 8, C_PER = 9 };
+        // hint of an entry = the byte at the same offset of the parallel buffer (X_HD: that offset, 0 = no hints); the collection size
+        // if the dense lists carry bitmaps, else 0 (X_ND); the shared floor word (X_FW) and histogram (X_SH, X_BOUND: its counters, the score bound that scales them); AND:
+        // the unit's segment of the match buffer (X_OUT)
+        enum { X_HD = (NT - 1) * C_PER, X_ND = X_HD + 2, X_FW = X_ND + 1, X_SH = X_FW + 2, X_BOUND = X_SH + 2, X_OUT = X_BOUND + 1, X_END = X_OUT + 2 };
+        constexpr int NCOLD = (X_END + 63) / 64;
         uint32_t cold[NCOLD];
 #pragma unroll
         for (int i = 0; i < NCOLD; ++i) cold[i] = 0xFFFFFFFFu;
@@ -196,9 +188,50 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 else rs_writelane_at(cold[NCOLD - 1], v, l & 63u);
             }
         };
-        enum { C_CUR = 0, C_BMAX = 1, C_N = 2, C_BB = 3, C_LOLO = 4, C_LOHI = 5, C_QW = 6, C_TLLO = 7, C_TLHI = 8, C_PER = 9 };
 #define cget(l) cold_get((uint32_t)(l))
 #define cset(l, v) rs_writelane<((l) & 63)>(cold[(l) >> 6], (v))
+#define cget64(l) (((unsigned long long)cget((l) + 1) << 32) | cget(l))
+#define cset64(l, v) do { const unsigned long long v_ = (unsigned long long)(v); cset(l, (uint32_t)v_); cset((l) + 1, (uint32_t)(v_ >> 32)); } while (0)
+        // Three and four lists: the byte fetched ahead for every candidate is list 1's HINT, not its weight. A weight byte lets a
+        // candidate through whenever its range holds any posting (one candidate in 4..6, each then costing a line per further
+        // list); the hint also settles the ranges with a single posting, so that the further lists are asked about a few per cent
+        // of the candidates only -- first their hints, then, for what is left, every list's weight for the threshold test.
+        // (Two lists: the weight stays first, its threshold test removes more than the hint does.)
+        // A list dense enough to carry its exact BITMAP behind its table (RmwLevels::has_bitmap) is asked that instead of its hint: a
+        // bit is the answer for every candidate, also where a range holds several postings (hint 255: "unknown", settled only by a
+        // search and a decode in stage C), and a line of it covers 1024 doc-ids. Fetched ahead for every candidate (list 1) only
+        // where that is no fewer than a hint line covers (RmwLevels::bitmap_first); on demand for the survivors (lists 2..) always.
+        // RS_BM in rsh[1] = list 1's byte is a bitmap byte; shift_of() is the list's shift proper.
+        constexpr bool HF = AND || RS_HINT_FIRST(NT); // (AND: the hint is the answer, the weight says nothing it needs)
+        constexpr uint32_t RS_BM = 256u;
+        auto shift_of = [&](auto jc) __attribute__((always_inline)) -> uint32_t {
+            constexpr int j = decltype(jc)::value;
+            if constexpr (HF && j == 1) return rsh[1] & 31u;
+            else return rsh[j];
+        };
+        bool hint_first = false;
+        const uint8_t* gt1 = rt[1];
+        {
+            const uint8_t* const rmh = a->rmh;
+            const long long hdelta = rmh ? (long long)(rmh - a->rmw) : 0ll;
+            const uint32_t nd_bm = a->rmw_bitmaps ? a->num_docs : 0u;
+            cset64(X_HD, hdelta);
+            cset(X_ND, nd_bm);
+            if constexpr (HF) {
+                hint_first = hdelta != 0;
+                if (hint_first) gt1 = rt[1] + hdelta;
+                if (hint_first && has1 && nd_bm != 0u && RmwLevels::bitmap_first(uniform(qt[1].n), nd_bm, rsh[1])) {
+                    gt1 = rt[1] + RmwLevels(nd_bm, rsh[1]).bytes();
+                    rsh[1] |= RS_BM;
+                }
+            }
+        }
+        // (AND, batches prepared with want_matches: the doc-ids of the intersection, in order, into the unit's segment of the match
+        // buffer -- 128 slots per block of list 0 from the query's offset, compacted by ds2i_hip_batch_fetch_matches; 0 = not wanted)
+        if constexpr (AND) {
+            uint32_t* const om = a->out_matches;
+            cset64(X_OUT, om ? (unsigned long long)(uintptr_t)(om + rs_uniform64(a->match_off[q]) + 128ull * blk_begin) : 0ull);
+        }
         {
             auto park = [&](auto jc) __attribute__((always_inline)) {
                 constexpr int j = decltype(jc)::value;
@@ -216,11 +249,20 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
             rs_for<1, NT>(park);
         }
         // ---- pruning state: the parts of a split query share a score histogram (device_score.hpp)
-        unsigned int* const q_hist = a->q_hist;
-        const bool shared_floor = AND ? false : (!whole && q_hist);
-        ScoreHist sh;
-        sh.init(shared_floor ? q_hist : nullptr, shared_floor ? uniform(u.hist_slot) : 0u, shared_floor ? rs_uniformf(qt[0].max_bmw + qt[0].suf_bmw) : 0.f,
-                1.0f - 1.0f / 1048576.0f);
+        // (the histogram is touched only when a score enters the heap: its counters and the score bound that scales it wait in `cold`,
+        // hist() puts it together there)
+        bool shared_floor = false;
+        if constexpr (!AND) {
+            unsigned int* const q_hist = a->q_hist;
+            shared_floor = !whole && q_hist;
+            cset64(X_SH, shared_floor ? (unsigned long long)(uintptr_t)(q_hist + 256u * uniform(u.hist_slot)) : 0ull);
+            cset(X_BOUND, shared_floor ? __float_as_uint(rs_uniformf(qt[0].max_bmw + qt[0].suf_bmw)) : 0u);
+        }
+        auto hist = [&]() __attribute__((always_inline)) -> ScoreHist {
+            ScoreHist sh;
+            sh.init((unsigned int*)(uintptr_t)cget64(X_SH), 0u, __uint_as_float(cget(X_BOUND)), 1.0f - 1.0f / 1048576.0f);
+            return sh;
+        };
         // can a score enter the heap: s >= floor && (heap not full || s > k-th score) (TopK::would_enter), branch-free on two
         // wave-uniform values that are refreshed whenever the heap or the floor changes
         float e_floor = tk.floor, e_gt = -__builtin_inff();
@@ -233,12 +275,13 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         // >= 0, so the bit patterns order like the values): whoever puts a score into its heap re-reads the histogram -- the only
         // moment the floor can have moved -- and raises the word; everybody else gets the word with every block, fetched an
         // iteration ahead by LDS-DMA, instead of a 256-counter scan every fourth block on the critical path.
-        unsigned int* const fwp = shared_floor ? (unsigned int*)rs_uniform_ptr(a->q_floor + uniform(u.hist_slot)) : nullptr;
+        auto fwp = [&]() __attribute__((always_inline)) -> unsigned int* { return (unsigned int*)(uintptr_t)cget64(X_FW); };
+        cset64(X_FW, shared_floor ? (unsigned long long)(uintptr_t)rs_uniform_ptr(a->q_floor + uniform(u.hist_slot)) : 0ull);
         auto adopt_word = [&](uint32_t bits) __attribute__((always_inline)) {
             const float f = __uint_as_float(bits);
             if (bits != 0u && f > tk.floor) { tk.floor = f; refresh(); }
         };
-        if (shared_floor) adopt_word(uniform(__hip_atomic_load(fwp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
+        if (shared_floor) adopt_word(uniform(__hip_atomic_load(fwp(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
         // ---- the 64-row window of list 0's table (lane j: row s_first + j; lane 0 is the row before the first block the window
         // can serve, unless that is block 0) and, per row, what a document of that block can score at most: block weight + for
         // each other list the largest range-table entry over the block's own doc-id span (read from the level whose entries are
@@ -270,8 +313,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
             auto one_list = [&](auto jc) __attribute__((always_inline)) {
                 constexpr int j = decltype(jc)::value;
                 if ((uint32_t)j >= nt) return;
-                const RmwLevels g(rs_args()->num_docs, rsh[j]);
-                uint32_t lsh = rsh[j], lvl = 0;
+                const RmwLevels g(rs_args()->num_docs, shift_of(jc));
+                uint32_t lsh = shift_of(jc), lvl = 0;
                 while (lvl < 2 && (t2 >> lsh) - (b2 >> lsh) >= 16u) { lsh += 6; ++lvl; }
                 const uint32_t lo = b2 >> lsh, hi = t2 >> lsh;
                 const bool fits = hi - lo < 16u;
@@ -349,7 +392,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 const uint8_t* const g = rs_uniform_ptr(data0 + N.ep); // (full blocks of a block_optpfor list are dword aligned; a partial last block is not read from here)
                 rs_prefetch_blk((const uint8_t*)((uintptr_t)g & ~(uintptr_t)3), st_base + bufN * (STAGE_DW * 4u), rs_uniform_ptr(xs0 + (size_t)XSLOT_DW * N.blk),
                                 xs_base + bufN * (XSLOT_DW * 4u), voff);
-                if (shared_floor) rs_fetch_word(fwp, fw_base);
+                if (shared_floor) rs_fetch_word(fwp(), fw_base);
                 LC(PH_STREAM, lines_of((const uint8_t*)((uintptr_t)g & ~(uintptr_t)3) + 8u * lane, true, 8u));
             }
             if (haveA) {
@@ -385,7 +428,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 // those of the prefetch above
                 if (haveN) { if (shared_floor) rs_wait_vm<PF_LOADS + 1>(); else rs_wait_vm<PF_LOADS>(); } else rs_wait_vm<0>();
                 PT(PH_TOPK);
-                // the byte fetched ahead: list 1's weight (2 lists) or hint (3, 4 lists); without a list 1: "several postings", which passes every test
+                // the byte fetched ahead: list 1's weight (2 lists), hint, or bitmap byte (3+ lists, AND); without a list 1: "several postings", which passes every test
                 const uint32_t x0 = has1 ? L.gb[0][lane] : 255u, x1 = has1 ? L.gb[1][lane] : 255u;
                 GP gP0 = x0, gP1 = x1;
                 // (the threshold only rises: a candidate alive now was alive when the gathers were issued, so its byte is there)
@@ -395,45 +438,64 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 // a range wider than rmh_code is injective over, or no hints at all)
                 uint32_t need0 = 0, need1 = 0;
                 if (hint_first) {
-                    ok0 = ok0 & ((x0 == 255u) | (x0 == rmh_code(dB0, rsh[1])));
-                    ok1 = ok1 & ((x1 == 255u) | (x1 == rmh_code(dB1, rsh[1])));
+                    constexpr std::integral_constant<int, 1> one{};
+                    const uint32_t s1 = shift_of(one);
+                    const bool bm1 = (rsh[1] & RS_BM) != 0u; // (list 1's byte is the candidate's byte of its bitmap: bit doc & 7 is the answer)
+                    ok0 = ok0 & (bm1 ? ((x0 >> (dB0 & 7u)) & 1u) != 0u : ((x0 == 255u) | (x0 == rmh_code(dB0, s1))));
+                    ok1 = ok1 & (bm1 ? ((x1 >> (dB1 & 7u)) & 1u) != 0u : ((x1 == 255u) | (x1 == rmh_code(dB1, s1))));
                     gP0 = gP1 = 0u;
                     if constexpr (AND) {
-                        need0 = ((x0 == 255u) | (rsh[1] > 7u)) ? 2u : 0u;
-                        need1 = ((x1 == 255u) | (rsh[1] > 7u)) ? 2u : 0u;
+                        need0 = (!bm1 & ((x0 == 255u) | (s1 > 7u))) ? 2u : 0u;
+                        need1 = (!bm1 & ((x1 == 255u) | (s1 > 7u))) ? 2u : 0u;
                     }
                     LC(PH_C_SURV1, __builtin_popcountll(ballot(ok0)) + __builtin_popcountll(ballot(ok1)));
                     if constexpr (NT > 2) {
-                        if (ballot(ok0) | ballot(ok1)) { // the further lists' hints, all requested before any is tested
+                        if (ballot(ok0) | ballot(ok1)) { // the further lists' hints (bitmap bytes where they have one), all requested before any is tested
                             uint32_t h0[NT] = {}, h1[NT] = {};
+                            const long long hdelta = (long long)cget64(X_HD);
+                            const uint32_t nd_bm = cget(X_ND);
+                            uint32_t bmm = 0; // bit j: list j answers from its bitmap (derived here, for the survivors' round trip only)
                             auto hload = [&](auto jc) __attribute__((always_inline)) {
                                 constexpr int j = decltype(jc)::value;
-                                const uint8_t* const ht = rt[j] + hdelta;
-                                h0[j] = (ok0 & ((uint32_t)j < nt)) ? (uint32_t)ht[dB0 >> rsh[j]] : 0u;
-                                h1[j] = (ok1 & ((uint32_t)j < nt)) ? (uint32_t)ht[dB1 >> rsh[j]] : 0u;
-                                LC(PH_MEMBER, lines_of(ht + (dB0 >> rsh[j]), ok0, 1u) + lines_of(ht + (dB1 >> rsh[j]), ok1, 1u));
+                                const uint8_t* ht = rt[j] + hdelta;
+                                uint32_t sj = shift_of(jc);
+                                if ((uint32_t)j < nt && nd_bm != 0u && RmwLevels::has_bitmap(cget((j - 1) * C_PER + C_N), nd_bm)) {
+                                    ht = rt[j] + RmwLevels(nd_bm, sj).bytes();
+                                    sj = 3u;
+                                    bmm |= 1u << j;
+                                }
+                                h0[j] = (ok0 & ((uint32_t)j < nt)) ? (uint32_t)ht[dB0 >> sj] : 0u;
+                                h1[j] = (ok1 & ((uint32_t)j < nt)) ? (uint32_t)ht[dB1 >> sj] : 0u;
+                                LC(PH_MEMBER, lines_of(ht + (dB0 >> sj), ok0, 1u) + lines_of(ht + (dB1 >> sj), ok1, 1u));
                             };
                             rs_for<2, NT>(hload);
                             auto htest = [&](auto jc) __attribute__((always_inline)) {
                                 constexpr int j = decltype(jc)::value;
                                 if ((uint32_t)j >= nt) return;
-                                ok0 = ok0 & (h0[j] != 0u) & ((h0[j] == 255u) | (h0[j] == rmh_code(dB0, rsh[j])));
-                                ok1 = ok1 & (h1[j] != 0u) & ((h1[j] == 255u) | (h1[j] == rmh_code(dB1, rsh[j])));
+                                const bool bmj = ((bmm >> j) & 1u) != 0u;
+                                ok0 = ok0 & (bmj ? ((h0[j] >> (dB0 & 7u)) & 1u) != 0u : ((h0[j] != 0u) & ((h0[j] == 255u) | (h0[j] == rmh_code(dB0, shift_of(jc))))));
+                                ok1 = ok1 & (bmj ? ((h1[j] >> (dB1 & 7u)) & 1u) != 0u : ((h1[j] != 0u) & ((h1[j] == 255u) | (h1[j] == rmh_code(dB1, shift_of(jc))))));
                                 if constexpr (AND) {
-                                    need0 |= ((h0[j] == 255u) | (rsh[j] > 7u)) ? (1u << j) : 0u;
-                                    need1 |= ((h1[j] == 255u) | (rsh[j] > 7u)) ? (1u << j) : 0u;
+                                    need0 |= (!bmj & ((h0[j] == 255u) | (shift_of(jc) > 7u))) ? (1u << j) : 0u;
+                                    need1 |= (!bmj & ((h1[j] == 255u) | (shift_of(jc) > 7u))) ? (1u << j) : 0u;
                                 }
                             };
                             rs_for<2, NT>(htest);
                             rs_settle_vm();
                         }
                     }
-                    if (!AND && (ballot(ok0) | ballot(ok1))) { // every list's weight byte for what is left (AND: nothing to weigh)
+                    // every list's weight byte for what is left (AND: nothing to weigh). Not while the unit has no threshold: with the heap
+                    // short of k scores and no floor, enters() holds for every score, so the bytes would decide nothing in this stage or in
+                    // stage C. INVARIANT: that state cannot end between here and the end of this block's stage C -- refresh() runs only
+                    // after a heap insert, which is stage C's last step, or in adopt_word() at the top of the loop -- so gP0 / gP1 = 0
+                    // ("the other lists add nothing") are read by tests that pass whatever they say, and by nothing else.
+                    const bool no_thr = !AND && e_gt == -__builtin_inff() && e_floor <= 0.f;
+                    if (!AND && !no_thr && (ballot(ok0) | ballot(ok1))) {
                         auto wload = [&](auto jc) __attribute__((always_inline)) {
                             constexpr int j = decltype(jc)::value;
-                            gP0 |= (GP)((ok0 & ((uint32_t)j < nt)) ? (uint32_t)rt[j][dB0 >> rsh[j]] : 0u) << (8 * (j - 1));
-                            gP1 |= (GP)((ok1 & ((uint32_t)j < nt)) ? (uint32_t)rt[j][dB1 >> rsh[j]] : 0u) << (8 * (j - 1));
-                            LC(PH_FREQS, lines_of(rt[j] + (dB0 >> rsh[j]), ok0, 1u) + lines_of(rt[j] + (dB1 >> rsh[j]), ok1, 1u));
+                            gP0 |= (GP)((ok0 & ((uint32_t)j < nt)) ? (uint32_t)rt[j][dB0 >> shift_of(jc)] : 0u) << (8 * (j - 1));
+                            gP1 |= (GP)((ok1 & ((uint32_t)j < nt)) ? (uint32_t)rt[j][dB1 >> shift_of(jc)] : 0u) << (8 * (j - 1));
+                            LC(PH_FREQS, lines_of(rt[j] + (dB0 >> shift_of(jc)), ok0, 1u) + lines_of(rt[j] + (dB1 >> shift_of(jc)), ok1, 1u));
                         };
                         rs_for<1, NT>(wload);
                         rs_settle_vm();
@@ -449,8 +511,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                         auto load_one = [&](auto jc) __attribute__((always_inline)) {
                             constexpr int j = decltype(jc)::value;
                             if ((uint32_t)j >= nt) return;
-                            gP0 |= (GP)(uint32_t)rt[j][(ok0 ? dB0 : 0u) >> rsh[j]] << (8 * (j - 1));
-                            gP1 |= (GP)(uint32_t)rt[j][(ok1 ? dB1 : 0u) >> rsh[j]] << (8 * (j - 1));
+                            gP0 |= (GP)(uint32_t)rt[j][(ok0 ? dB0 : 0u) >> shift_of(jc)] << (8 * (j - 1));
+                            gP1 |= (GP)(uint32_t)rt[j][(ok1 ? dB1 : 0u) >> shift_of(jc)] << (8 * (j - 1));
                         };
                         rs_for<2, NT>(load_one);
                         auto test_one = [&](auto jc) __attribute__((always_inline)) {
@@ -476,7 +538,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 };
                 if constexpr (AND) {
                     if (!hint_first) { // an upload without hints: a non-zero byte is the answer only where an entry is one doc-id
-                        auto nm = [&](auto jc) __attribute__((always_inline)) { constexpr int j = decltype(jc)::value; if (rsh[j] != 0u && (uint32_t)j < nt) need0 |= 1u << j; };
+                        auto nm = [&](auto jc) __attribute__((always_inline)) { constexpr int j = decltype(jc)::value; if (shift_of(jc) != 0u && (uint32_t)j < nt) need0 |= 1u << j; };
                         rs_for<1, NT>(nm);
                         need1 = need0;
                     }
@@ -487,18 +549,20 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 ok1 = ok1 & enters((boB1 + r1) * BOUND_SLACK);
                 LC(PH_C_VISIT, __builtin_popcountll(ballot(dB0 != 0xFFFFFFFFu)) + __builtin_popcountll(ballot(dB1 != 0xFFFFFFFFu)));
                 if (!hint_first) LC(PH_C_SURV1, __builtin_popcountll(ballot(ok0)) + __builtin_popcountll(ballot(ok1)));
-                if (!hint_first && hdelta && (ballot(ok0) | ballot(ok1))) {
+                // (a hint-first kernel without hints has none to ask here either)
+                if (!HF && (ballot(ok0) | ballot(ok1)) != 0ull && cget64(X_HD) != 0ull) {
+                    const long long hdelta = (long long)cget64(X_HD);
                     // membership hints (BatchArgs::rmh): a weight byte only says that SOME posting of list j lies in the candidate's
                     // range; where that range holds exactly one posting its hint byte says which. A candidate at another offset is
                     // not in the list -- settled here, by one more byte, instead of by a block search and a block decode in stage C.
                     auto hint_one = [&](auto jc) __attribute__((always_inline)) {
                         constexpr int j = decltype(jc)::value;
                         const uint8_t* const ht = rt[j] + hdelta;
-                        const bool hashint = rsh[j] != 0u && (uint32_t)j < nt; // (one doc-id per entry: the weight byte was the answer)
-                        const uint32_t h0 = (ok0 & hashint) ? (uint32_t)ht[dB0 >> rsh[j]] : 255u, h1 = (ok1 & hashint) ? (uint32_t)ht[dB1 >> rsh[j]] : 255u;
-                        LC(PH_MEMBER, lines_of(ht + (dB0 >> rsh[j]), ok0 & hashint, 1u) + lines_of(ht + (dB1 >> rsh[j]), ok1 & hashint, 1u));
-                        ok0 = ok0 & ((h0 == 255u) | (h0 == rmh_code(dB0, rsh[j])));
-                        ok1 = ok1 & ((h1 == 255u) | (h1 == rmh_code(dB1, rsh[j])));
+                        const bool hashint = shift_of(jc) != 0u && (uint32_t)j < nt; // (one doc-id per entry: the weight byte was the answer)
+                        const uint32_t h0 = (ok0 & hashint) ? (uint32_t)ht[dB0 >> shift_of(jc)] : 255u, h1 = (ok1 & hashint) ? (uint32_t)ht[dB1 >> shift_of(jc)] : 255u;
+                        LC(PH_MEMBER, lines_of(ht + (dB0 >> shift_of(jc)), ok0 & hashint, 1u) + lines_of(ht + (dB1 >> shift_of(jc)), ok1 & hashint, 1u));
+                        ok0 = ok0 & ((h0 == 255u) | (h0 == rmh_code(dB0, shift_of(jc))));
+                        ok1 = ok1 & ((h1 == 255u) | (h1 == rmh_code(dB1, shift_of(jc))));
                     };
                     rs_for<1, NT>(hint_one);
                     rs_settle_vm();
@@ -680,6 +744,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                     else rs_for<1, NT>(probe);
                     if constexpr (AND) {
                         const uint64_t m0 = ballot(ok0), m1 = ballot(ok1);
+                        uint32_t* const and_out = (uint32_t*)(uintptr_t)cget64(X_OUT);
                         if (and_out) { // (value i of the block sits in lane i & 63, slot i >> 6: slot 0 first keeps the doc-ids ascending)
                             const uint64_t below = (1ull << lane) - 1ull;
                             const unsigned long long at0 = and_count + (unsigned long long)__builtin_popcountll(m0 & below);
@@ -703,14 +768,14 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                             if (TK_INSERT(tk, v, bcast(half ? dB1 : dB0, src))) {
                                 refresh();
                                 inserted = 1;
-                                if (shared_floor && lane == 0) sh.add(v);
+                                if (shared_floor && lane == 0) hist().add(v);
                             }
                         }
                     }
                     if (shared_floor && inserted) { // the histogram moved: what floor does it imply now
-                        const float f = sh.floor(tk.k);
+                        const float f = hist().floor(tk.k);
                         if (f > 0.f) {
-                            if (lane == 0) __hip_atomic_fetch_max(fwp, __float_as_uint(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                            if (lane == 0) __hip_atomic_fetch_max(fwp(), __float_as_uint(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if (f > tk.floor) { tk.floor = f; refresh(); }
                         }
                     }
@@ -736,9 +801,10 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 if (haveB) {
                     LC(PH_C_ALIVE, __builtin_popcountll(ballot(al0)) + __builtin_popcountll(ballot(al1)));
                     LC(PH_C_GBLOCKS, 1);
-                    rs_gather_u8(gt1, (al0 ? dB0 : 0u) >> rsh[1], gb_base);
-                    rs_gather_u8(gt1, (al1 ? dB1 : 0u) >> rsh[1], gb_base + 256u);
-                    LC(PH_TOPK, lines_of(gt1 + (dB0 >> rsh[1]), al0, 1u) + lines_of(gt1 + (dB1 >> rsh[1]), al1, 1u) + 2u);
+                    const uint32_t gs1 = HF && (rsh[1] & RS_BM) ? 3u : shift_of(std::integral_constant<int, 1>{}); // (a bitmap byte holds 8 doc-ids; 31: no list 1, everybody reads entry 0)
+                    rs_gather_u8(gt1, (al0 ? dB0 : 0u) >> gs1, gb_base);
+                    rs_gather_u8(gt1, (al1 ? dB1 : 0u) >> gs1, gb_base + 256u);
+                    LC(PH_TOPK, lines_of(gt1 + (dB0 >> gs1), al0, 1u) + lines_of(gt1 + (dB1 >> gs1), al1, 1u) + 2u);
                 }
             }
             PT(PH_PROBE);
@@ -754,6 +820,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         rs_wait_vm<0>(); // (a unit left early -- list exhausted -- may still have a prefetch or gathers in flight)
 #undef cget
 #undef cset
+#undef cget64
+#undef cset64
         KArgs r = rs_args();
         if constexpr (STATS) {
             unsigned long long* const clk = r->unit_clock;
