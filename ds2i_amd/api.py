@@ -155,6 +155,12 @@ def lib():
                                                  C.POINTER(VerifyReport), C.POINTER(C.c_double)]
         L.ds2i_hip_verify_host_seconds.argtypes = [C.POINTER(C.c_double)]
         L.ds2i_hip_verify_host_seconds.restype = None
+        L.ds2i_hip_index_extract.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, u64p, C.POINTER(C.c_double)]
+        L.ds2i_hip_extract_collection.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, u64p, u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                                  C.POINTER(C.c_double)]
+        L.ds2i_hip_convert_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_extract_host_seconds.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_extract_host_seconds.restype = None
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -335,6 +341,28 @@ def gpu_verify_collection(kind, image, num_docs, lists, device=0):
     _check(lib().ds2i_hip_verify_collection(device, _codec(kind), image, len(image), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
                                             C.byref(r), C.byref(ms)))
     return _verify_result(r, ms)
+
+
+def gpu_extract_collection(kind, image, device=0):
+    """The collection an index image holds, decoded ON THE GPU in one launch (ds2i_hip_extract_collection): a bare upload of the
+    image and the on-disk decoders of `kind` (any of the nine). List t is docs[offsets[t]:offsets[t + 1]] with the freqs beside
+    it. Returns (num_docs, offsets uint64[lists + 1], docs uint32, freqs uint32, dict(device_ms)). An index holds no document
+    sizes: they do not come back."""
+    n, v, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+    ho, hd, hf = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(lib().ds2i_hip_extract_collection(device, _codec(kind), image, len(image), C.byref(n), C.byref(v), C.byref(ho), C.byref(hd),
+                                             C.byref(hf), C.byref(ms)))
+    offs, docs, freqs = (np.frombuffer(_take_blob(h), dtype=t) for h, t in ((ho, np.uint64), (hd, np.uint32), (hf, np.uint32)))
+    return n.value, offs, docs, freqs, {"device_ms": ms.value}
+
+
+def gpu_convert_index(from_kind, image, to_kind, device=0):
+    """An index image of `from_kind` (any of the nine) as an image of `to_kind` (a kind gpu_encode_index writes), ON THE GPU
+    (ds2i_hip_convert_index): extracted in one launch and encoded where the postings lie; byte-identical to
+    build_index(to_kind, ...) over the same lists. Returns (image bytes, dict(device_ms))."""
+    h, ms = C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_convert_index(device, _codec(from_kind), image, len(image), _codec(to_kind), C.byref(h), C.byref(ms)))
+    return _take_blob(h), {"device_ms": ms.value}
 
 
 def synth_build_gpu(p, device=0, threads=0):
@@ -745,6 +773,19 @@ class Index:
         r, ms = VerifyReport(), C.c_double()
         _check(lib().ds2i_hip_index_verify(self._h, self.num_docs(), n, _ptr(offs), _ptr(docs), _ptr(freqs), C.byref(r), C.byref(ms)))
         return _verify_result(r, ms)
+
+    def extract(self, begin=0, end=None):
+        """The postings of lists [begin, end) (end=None: to the last list) in one launch (ds2i_hip_index_extract), as queries read
+        this index. Returns (offsets uint64[end - begin + 1] from 0, docs uint32, freqs uint32, dict(device_ms))."""
+        L = lib()
+        end = self.size() if end is None else end
+        offs = np.zeros(max(end - begin, 0) + 1, dtype=np.uint64)
+        total, ms = C.c_uint64(), C.c_double()
+        _check(L.ds2i_hip_index_extract(self._h, begin, end, _ptr(offs), None, None, 0, C.byref(total), None))  # the size query
+        docs = np.empty(max(total.value, 1), dtype=np.uint32)
+        freqs = np.empty(max(total.value, 1), dtype=np.uint32)
+        _check(L.ds2i_hip_index_extract(self._h, begin, end, _ptr(offs), _ptr(docs), _ptr(freqs), total.value, C.byref(total), C.byref(ms)))
+        return offs, docs[:total.value], freqs[:total.value], {"device_ms": ms.value}
 
     def calibration_read(self):
         n = C.c_uint64()

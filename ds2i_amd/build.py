@@ -28,7 +28,7 @@ DOCS_UNITS = [(src, name.replace(".hip", "_docs.hip"), ["-DDS2I_DOCS_TU"] + defs
 DEVICE_UNITS = RANKED_UNITS + [("kernels.hip", "kernels.hip", []), ("freq_stream.hip", "freq_stream.hip", []),
                                ("encode_kernels.hip", "encode_kernels.hip", []), ("wand_kernels.hip", "wand_kernels.hip", []),
                                ("freq_encode_kernels.hip", "freq_encode_kernels.hip", [])] + DOCS_UNITS
-HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "capi_build.cpp", "capi_encode.cpp", "capi_verify.cpp"]
+HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "capi_build.cpp", "capi_encode.cpp", "capi_verify.cpp", "capi_extract.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 

@@ -311,6 +311,28 @@ struct VerifyArgs {
     const uint32_t* tails;
 };
 
+// Whole-index decode-and-store (k_extract_index / k_extract_index_side): the walk of the verification over the index-wide block
+// numbers [block_begin, block_end) -- the blocks of `nlists` consecutive lists, `lists` holding those lists only (their blk_base
+// stay index-wide). Posting i of a block of list l goes to out_docs / out_freqs [list_first[l] + (position of the block in its
+// list) + i]; list_first starts at 0 for the first list of the range, and the two buffers hold exactly list_first[nlists] postings.
+struct ExtractArgs {
+    const uint8_t* arena;
+    const uint8_t* bits0;
+    const uint8_t* bits1;
+    const QTerm* lists;         // one per list of the range (ds2i_make_qterm)
+    uint32_t nlists;
+    uint32_t block_begin, block_end;
+    int codec;
+    uint32_t num_docs;
+    uint32_t* out_docs;
+    uint32_t* out_freqs;
+    const uint64_t* list_first; // nlists + 1 posting offsets of the output
+    const void* skip;           // k_extract_index_side: as DecodeArgs
+    const uint32_t* xslots;
+    const uint32_t* xovf;
+    const uint32_t* tails;
+};
+
 // wand / maxscore / ranked_or of a ONE-term query are exactly its ranked_and result: copied from the seed pass (k_copy_seed)
 struct CopySeedArgs {
     const uint32_t* queries;

@@ -29,6 +29,12 @@
 #include "launchers.hpp"
 
 namespace {
+#define STAGE_OK(call)                 \
+    do {                               \
+        const int rc_ = (call);        \
+        if (rc_ != DS2I_OK) return rc_; \
+    } while (0)
+
 // A collection in CSR form staged on the device, with the block tables both kernels walk
 struct EncStage {
     DevTemps dev;
@@ -40,12 +46,34 @@ struct EncStage {
     uint64_t* d_blk_out = nullptr;
     uint64_t* d_list_out = nullptr;
 
+    // the two ways in: upload() copies the postings from the host, adopt() takes postings that are on the device already (the
+    // extraction kernels' output: a conversion never sends them over the bus again) and frees them with the staging
     int upload(const char* who, int device, uint64_t nl, const uint64_t* offs, const uint32_t* docs, const uint32_t* freqs) {
+        STAGE_OK(tables(who, device, nl, offs));
+        const uint64_t total = offs[nlists];
+        uint32_t *d_docs, *d_freqs;
+        HIP_OK(dev.alloc(&d_docs, 4 * total));
+        HIP_OK(dev.alloc(&d_freqs, 4 * total));
+        HIP_OK(hipMemcpy(d_docs, docs, 4 * total, hipMemcpyHostToDevice));
+        HIP_OK(hipMemcpy(d_freqs, freqs, 4 * total, hipMemcpyHostToDevice));
+        a.docs = d_docs;
+        a.freqs = d_freqs;
+        return DS2I_OK;
+    }
+    int adopt(const char* who, int device, uint64_t nl, const uint64_t* offs, uint32_t* d_docs, uint32_t* d_freqs) {
+        dev.p.push_back(d_docs); // (owned from here on, whatever happens below)
+        dev.p.push_back(d_freqs);
+        a.docs = d_docs;
+        a.freqs = d_freqs;
+        return tables(who, device, nl, offs);
+    }
+
+    // everything of the staging but the postings: the offsets and the block tables
+    int tables(const char* who, int device, uint64_t nl, const uint64_t* offs) {
         const int rc = check_device(who, device);
         if (rc != DS2I_OK) return rc;
         nlists = nl;
         list_offsets = offs;
-        const uint64_t total = offs[nlists];
         std::vector<uint32_t> blk_list;
         list_blk0.resize(nlists);
         for (uint64_t t = 0; t < nlists; ++t) {
@@ -67,10 +95,8 @@ struct EncStage {
         hipDeviceProp_t prop;
         HIP_OK(hipGetDeviceProperties(&prop, device));
         grid = (unsigned)std::min<uint64_t>(nblocks ? nblocks : 1, (uint64_t)(prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256) * 32);
-        uint32_t *d_docs, *d_freqs, *d_blk_list, *d_list_blk0;
+        uint32_t *d_blk_list, *d_list_blk0;
         uint64_t* d_list_in;
-        HIP_OK(dev.alloc(&d_docs, 4 * total));
-        HIP_OK(dev.alloc(&d_freqs, 4 * total));
         HIP_OK(dev.alloc(&d_list_in, 8 * (nlists + 1)));
         HIP_OK(dev.alloc(&d_blk_list, 4 * nblocks));
         HIP_OK(dev.alloc(&d_list_blk0, 4 * nlists));
@@ -79,13 +105,9 @@ struct EncStage {
         HIP_OK(dev.alloc(&a.bmax, 4 * nblocks));
         HIP_OK(dev.alloc(&d_blk_out, 8 * (nblocks + 1)));
         HIP_OK(dev.alloc(&d_list_out, 8 * nlists));
-        HIP_OK(hipMemcpy(d_docs, docs, 4 * total, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_freqs, freqs, 4 * total, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(d_list_in, offs, 8 * (nlists + 1), hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(d_blk_list, blk_list.data(), 4 * nblocks, hipMemcpyHostToDevice));
         HIP_OK(hipMemcpy(d_list_blk0, list_blk0.data(), 4 * nlists, hipMemcpyHostToDevice));
-        a.docs = d_docs;
-        a.freqs = d_freqs;
         a.list_in = d_list_in;
         a.blk_list = d_blk_list;
         a.list_blk0 = d_list_blk0;
@@ -135,12 +157,6 @@ struct EncStage {
         DS2I_CATCH
     }
 };
-#define STAGE_OK(call)                 \
-    do {                               \
-        const int rc_ = (call);        \
-        if (rc_ != DS2I_OK) return rc_; \
-    } while (0)
-
 // plan pass, layout, write pass of one codec over a staged collection; ms accumulates the hipEvent time of the two passes
 int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image, double& ms) {
     const uint64_t nblocks = st.nblocks;
@@ -349,6 +365,39 @@ extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_do
     if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings("ds2i_hip_encode_index", num_docs, nlists, list_offsets, docs, freqs));
     DS2I_TRY
     return build_images("ds2i_hip_encode_index", device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms);
+    DS2I_CATCH
+}
+
+// capi_util.hpp: what ds2i_hip_convert_index asks of the encoder
+int ds2i_check_encoder_kind(const char* who, int index_kind) {
+    int codec = 0;
+    return encoder_kind_of(who, index_kind, codec);
+}
+
+int ds2i_encode_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                                uint32_t* d_docs, uint32_t* d_freqs, ds2i_blob** image, double* device_ms) {
+    DS2I_TRY
+    EncStage st;
+    const int adopted = st.adopt(who, device, nlists, list_offsets, d_docs, d_freqs);
+    int codec = 0;
+    STAGE_OK(encoder_kind_of(who, index_kind, codec));
+    STAGE_OK(adopted);
+    double ms = 0.0;
+    ds2i_blob* ib = nullptr;
+    if (ds2i_host::is_freq_layout(codec)) {
+        // the host planner reads the postings: they come down once, and the base sequences are written from the device copy
+        const uint64_t total = list_offsets[nlists];
+        std::vector<uint32_t> docs(total ? total : 1), freqs(total ? total : 1);
+        HIP_OK(hipMemcpy(docs.data(), d_docs, 4 * total, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(freqs.data(), d_freqs, 4 * total, hipMemcpyDeviceToHost));
+        STAGE_OK(check_freq_postings(who, num_docs, nlists, list_offsets, docs.data(), freqs.data()));
+        STAGE_OK(freq_encode_staged(st, codec, num_docs, docs.data(), freqs.data(), &ib, ms));
+    } else {
+        STAGE_OK(encode_staged(st, codec, num_docs, &ib, ms));
+    }
+    *image = ib;
+    if (device_ms) *device_ms = ms;
+    return DS2I_OK;
     DS2I_CATCH
 }
 

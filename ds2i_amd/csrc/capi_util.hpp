@@ -49,3 +49,13 @@ inline int check_device(const char* who, int device) {
         return ds2i_set_error(DS2I_EDEVICE, (std::string(who) + ": no such HIP device").c_str());
     return DS2I_OK;
 }
+
+// capi_encode.cpp, for capi_extract.cpp (ds2i_hip_convert_index). check_encoder_kind: DS2I_OK for the seven kinds the GPU encoder
+// writes, else ds2i_hip_encode_index's DS2I_EINVAL naming them. encode_device_postings: ds2i_hip_encode_index over postings that
+// lie on `device` already (list_offsets on the host); d_docs / d_freqs were hipMalloc-ed and belong to the callee from the call on,
+// whatever it returns. The block codecs never bring the postings to the host; the Elias-Fano layouts bring them down once, for
+// the host planner, and apply ds2i_hip_encode_index's input checks to them.
+struct ds2i_blob;
+int ds2i_check_encoder_kind(const char* who, int index_kind);
+int ds2i_encode_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                                uint32_t* d_docs, uint32_t* d_freqs, ds2i_blob** image, double* device_ms);

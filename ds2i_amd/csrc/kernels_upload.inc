@@ -91,7 +91,8 @@ __global__ void __launch_bounds__(64) k_decode_list_side(DecodeArgs a) {
 // ------------------------------------------------------------------ whole-index verification
 // Every block (chunk) of every list decoded and compared with a collection staged in CSR form (VerifyArgs, abi_structs.hpp): one
 // launch for the whole index, one wave per block, grid-strided over the index-wide block numbers. A wave finds the list of its
-// block in the per-list block prefix (QTerm::blk_base / nblocks) by binary search and rebinds only when the list changes.
+// block in the per-list block prefix (QTerm::blk_base / nblocks) by binary search and rebinds only when the list changes
+// (walk_index / walk_index_side below, which the extraction kernels share).
 
 // the last list whose blk_base <= g, at or after `lo` (a wave's block numbers only grow; lists[lo].blk_base <= g)
 DS2I_DEV uint32_t verify_list_of(const QTerm* lists, uint32_t nlists, uint32_t g, uint32_t lo) {
@@ -118,8 +119,13 @@ DS2I_DEV void verify_compare(const VerifyArgs& a, uint64_t at, uint32_t sz, uint
     if (lane == 0) atomicMin(a.first_bad, key);
 }
 
-__global__ void __launch_bounds__(64) k_verify_index(VerifyArgs a) {
-    __shared__ Lds<1> L;
+// The walk, stated once for the kernels that compare (k_verify_index[_side]) and those that store (k_extract_index[_side]): the wave
+// takes the index-wide block numbers blockIdx.x + [g_begin, g_end) in grid strides, decodes each and hands it to
+// sink(at, left, sz, d0, d1, f0, f1): `at` = the block's first posting in the CSR arrays (a.list_first[l] + its position in the
+// list), `left` = the postings of its list from that position on, value i of its sz postings in lane i & 63 (d0 / f0: i = lane,
+// d1 / f1: i = lane + 64). a.lists holds the lists of the range; their blk_base stay index-wide.
+template <class Args, class Sink>
+DS2I_DEV void walk_index(const Args& a, unsigned long long g_begin, unsigned long long g_end, Lds<1>& L, Sink sink) {
     BatchArgs ba{};
     ba.arena = a.arena;
     ba.bits0 = a.bits0;
@@ -128,9 +134,9 @@ __global__ void __launch_bounds__(64) k_verify_index(VerifyArgs a) {
     ba.num_docs = a.num_docs;
     Ctx cx = make_ctx<-1, MetaLds>(L, ba);
     const uint32_t lane = lane_id();
-    uint32_t l = 0;
+    uint32_t l = 0, n = 0;
     unsigned long long base = 0, end = 0, first = 0; // the bound list: its blocks [base, end) and its first posting in the collection
-    for (unsigned long long g = blockIdx.x; g < a.total_blocks; g += gridDim.x) {
+    for (unsigned long long g = g_begin + blockIdx.x; g < g_end; g += gridDim.x) {
         if (g >= end) {
             l = verify_list_of(a.lists, a.nlists, (uint32_t)g, l);
             const QTerm t = a.lists[l];
@@ -138,22 +144,23 @@ __global__ void __launch_bounds__(64) k_verify_index(VerifyArgs a) {
             base = t.blk_base;
             end = base + t.nblocks;
             first = a.list_first[l];
+            n = t.n;
         }
         cx.decode_docs(0, (uint32_t)(g - base));
         cx.decode_freqs(0);
-        verify_compare(a, first + cx.m(0, M_GPOS), cx.m(0, M_SIZE), L.docs[0][lane], L.docs[0][lane + 64], L.freqs[0][lane], L.freqs[0][lane + 64]);
+        const uint32_t gpos = cx.m(0, M_GPOS);
+        sink(first + gpos, n > gpos ? n - gpos : 0u, cx.m(0, M_SIZE), L.docs[0][lane], L.docs[0][lane + 64], L.freqs[0][lane], L.freqs[0][lane + 64]);
         wave_sync();
     }
 }
 
 // The same through the exception side slots + tail table (side_decode_block, the decode of k_decode_list_side)
-__global__ void __launch_bounds__(64) k_verify_index_side(VerifyArgs a) {
-    __shared__ uint32_t st[STAGE_DW];
-    __shared__ uint32_t xs[XSLOT_DW];
+template <class Args, class Sink>
+DS2I_DEV void walk_index_side(const Args& a, unsigned long long g_begin, unsigned long long g_end, uint32_t* st, uint32_t* xs, Sink sink) {
     uint32_t l = 0;
     unsigned long long base = 0, end = 0, first = 0;
     QTerm t{};
-    for (unsigned long long g = blockIdx.x; g < a.total_blocks; g += gridDim.x) {
+    for (unsigned long long g = g_begin + blockIdx.x; g < g_end; g += gridDim.x) {
         if (g >= end) {
             l = verify_list_of(a.lists, a.nlists, (uint32_t)g, l);
             t = a.lists[l];
@@ -163,9 +170,53 @@ __global__ void __launch_bounds__(64) k_verify_index_side(VerifyArgs a) {
         }
         const uint32_t b = (uint32_t)(g - base);
         const SideBlock k = side_decode_block(a.arena, a.skip, a.xslots, a.xovf, a.tails, t, b, st, xs);
-        verify_compare(a, first + (unsigned long long)b * 128u, k.sz, k.d0, k.d1, k.f0, k.f1);
+        sink(first + (unsigned long long)b * 128u, t.n - b * 128u, k.sz, k.d0, k.d1, k.f0, k.f1);
         wave_sync();
     }
+}
+
+struct VerifySink {
+    const VerifyArgs& a;
+    DS2I_DEV void operator()(unsigned long long at, uint32_t, uint32_t sz, uint32_t d0, uint32_t d1, uint32_t f0, uint32_t f1) const {
+        verify_compare(a, at, sz, d0, d1, f0, f1);
+    }
+};
+
+__global__ void __launch_bounds__(64) k_verify_index(VerifyArgs a) {
+    __shared__ Lds<1> L;
+    walk_index(a, 0ull, a.total_blocks, L, VerifySink{a});
+}
+
+__global__ void __launch_bounds__(64) k_verify_index_side(VerifyArgs a) {
+    __shared__ uint32_t st[STAGE_DW];
+    __shared__ uint32_t xs[XSLOT_DW];
+    walk_index_side(a, 0ull, a.total_blocks, st, xs, VerifySink{a});
+}
+
+// ------------------------------------------------------------------ whole-index extraction
+// The walk of the verification with stores instead of compares (ExtractArgs, abi_structs.hpp): posting i of a block goes to
+// out_docs / out_freqs [at + i] -- two 256-byte rows per side and wave, lane after lane. Lists lie back to back and the buffers have
+// no slack: a lane at or past the block's size stores nothing, and no store passes the end of the block's own list whatever the
+// decoder says of a block's size.
+struct ExtractSink {
+    const ExtractArgs& a;
+    DS2I_DEV void operator()(unsigned long long at, uint32_t left, uint32_t sz, uint32_t d0, uint32_t d1, uint32_t f0, uint32_t f1) const {
+        const uint32_t lane = lane_id();
+        sz = sz < left ? sz : left;
+        if (lane < sz) { a.out_docs[at + lane] = d0; a.out_freqs[at + lane] = f0; }
+        if (lane + 64 < sz) { a.out_docs[at + lane + 64] = d1; a.out_freqs[at + lane + 64] = f1; }
+    }
+};
+
+__global__ void __launch_bounds__(64) k_extract_index(ExtractArgs a) {
+    __shared__ Lds<1> L;
+    walk_index(a, a.block_begin, a.block_end, L, ExtractSink{a});
+}
+
+__global__ void __launch_bounds__(64) k_extract_index_side(ExtractArgs a) {
+    __shared__ uint32_t st[STAGE_DW];
+    __shared__ uint32_t xs[XSLOT_DW];
+    walk_index_side(a, a.block_begin, a.block_end, st, xs, ExtractSink{a});
 }
 
 // ------------------------------------------------------------------ upload-time block-max weights

@@ -28,6 +28,9 @@ hipError_t ds2i_launch_decode_list_side(const ds2i_dev::DecodeArgs& a, unsigned 
 // every block of every list against a staged collection; _side: block_optpfor through the side slots and the tail table
 hipError_t ds2i_launch_verify_index(const ds2i_dev::VerifyArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_verify_index_side(const ds2i_dev::VerifyArgs& a, unsigned grid, hipStream_t s);
+// the same walk over a block range, storing the postings in CSR form; _side: as above
+hipError_t ds2i_launch_extract_index(const ds2i_dev::ExtractArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_extract_index_side(const ds2i_dev::ExtractArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_selftest(const uint32_t* in, uint32_t* out, unsigned blocks, hipStream_t s);
 hipError_t ds2i_launch_selftest_bm25(const uint32_t* freqs, const float* norm_lens, float* out, uint32_t n, hipStream_t s);
 hipError_t ds2i_launch_calib_read(const uint32_t* base, unsigned long long ndw, uint32_t* out, unsigned grid, hipStream_t s);

@@ -19,22 +19,13 @@
 // (list, position, got = what the index holds, expected = what the collection holds, length = the list's length).
 // Exit code: 0 success, 1 the index does not match the collection, 2 an error (an unknown index type among them whenever a
 // verification was asked for; without one it is logged and the exit code stays 0, as before).
-#include "../../include/ds2i_build.h"
-#include "../../include/ds2i_hip.h"
-#include "tool_util.hpp"
+#include "tool_verify.hpp"
 
 #include <cstdlib>
 
 static const char* const USAGE =
     " <index_type> <collection_basename> <output_index> [<output_wand_data>] [--gpu] [--check] [--device <n>]\n"
     "       create_freq_index <index_type> <collection_basename> <existing_index> --check-only [--device <n>]\n";
-
-static void write_blob(const char* path, ds2i_blob* b) {
-    FILE* f = std::fopen(path, "wb");
-    if (!f) throw std::runtime_error(std::string("cannot write ") + path);
-    std::fwrite(ds2i_blob_data(b), 1, ds2i_blob_size(b), f);
-    std::fclose(f);
-}
 
 // the head of <base>.docs: one sequence of one element, the number of documents
 static uint64_t read_num_docs(tool::binary_sequences& docs) {
@@ -69,34 +60,9 @@ struct csr_collection {
     }
 };
 
-static void hip_ok(int rc, const char* what) {
-    if (rc) throw std::runtime_error(std::string(what) + " failed: " + ds2i_hip_last_error());
-}
-
 // the index file against the collection: the line on stdout, and the exit code
 static int check_file(int device, int kind, const char* path, csr_collection const& c) {
-    tool::mapped_file img(path);
-    ds2i_hip_verify_report r;
-    hip_ok(ds2i_hip_verify_collection(device, kind, img.data, img.size, c.num_docs, c.lists(), c.offsets.data(), c.docs.data(),
-                                      c.freqs.data(), &r, nullptr), "ds2i_hip_verify_collection");
-    switch (r.what) {
-    case DS2I_VERIFY_OK:
-        std::cout << "OK lists=" << c.lists() << " postings=" << r.postings_checked << std::endl;
-        return 0;
-    case DS2I_VERIFY_NUM_DOCS:
-        std::cout << "MISMATCH num_docs got=" << r.got << " expected=" << r.expected << std::endl;
-        return 1;
-    case DS2I_VERIFY_LISTS:
-        std::cout << "MISMATCH lists got=" << r.got << " expected=" << r.expected << std::endl;
-        return 1;
-    case DS2I_VERIFY_LENGTH:
-        std::cout << "MISMATCH length list=" << r.list << " got=" << r.got << " expected=" << r.expected << std::endl;
-        return 1;
-    default:
-        std::cout << "MISMATCH " << (r.what == DS2I_VERIFY_DOCID ? "docid" : "freq") << " list=" << r.list << " position=" << r.position
-                  << " got=" << r.got << " expected=" << r.expected << " length=" << (c.offsets[r.list + 1] - c.offsets[r.list]) << std::endl;
-        return 1;
-    }
+    return tool::check_index_file(device, kind, path, c.num_docs, c.lists(), c.offsets.data(), c.docs.data(), c.freqs.data());
 }
 
 int main(int argc, const char** argv) {
@@ -153,19 +119,19 @@ int main(int argc, const char** argv) {
             }
             ds2i_blob *img = nullptr, *wi = nullptr;
             if (out_wand)
-                hip_ok(ds2i_hip_build_collection(device, kind, s, csr->num_docs, csr->lists(), csr->offsets.data(), csr->docs.data(),
-                                                 csr->freqs.data(), &img, &wi, nullptr), "ds2i_hip_build_collection");
+                tool::hip_ok(ds2i_hip_build_collection(device, kind, s, csr->num_docs, csr->lists(), csr->offsets.data(), csr->docs.data(),
+                                                       csr->freqs.data(), &img, &wi, nullptr), "ds2i_hip_build_collection");
             else
-                hip_ok(ds2i_hip_encode_index(device, kind, csr->num_docs, csr->lists(), csr->offsets.data(), csr->docs.data(),
-                                             csr->freqs.data(), &img, nullptr), "ds2i_hip_encode_index");
-            write_blob(out_index, img);
+                tool::hip_ok(ds2i_hip_encode_index(device, kind, csr->num_docs, csr->lists(), csr->offsets.data(), csr->docs.data(),
+                                                   csr->freqs.data(), &img, nullptr), "ds2i_hip_encode_index");
+            tool::write_blob(out_index, img);
             std::ostringstream os;
             os << csr->lists() << " sequences, " << csr->offsets.back() << " postings, " << ds2i_blob_size(img) << " bytes ("
                << (8.0 * ds2i_blob_size(img) / csr->offsets.back()) << " bits/posting)";
             tool::logger(os.str());
             ds2i_blob_free(img);
             if (wi) {
-                write_blob(out_wand, wi);
+                tool::write_blob(out_wand, wi);
                 ds2i_blob_free(wi);
             }
             return check ? check_file(device, kind, out_index, *csr) : 0;
@@ -198,7 +164,7 @@ int main(int argc, const char** argv) {
         }
         ds2i_blob* img = nullptr;
         if (ds2i_builder_freeze(b, &img)) throw std::runtime_error("freeze failed");
-        write_blob(out_index, img);
+        tool::write_blob(out_index, img);
         std::ostringstream os;
         os << lists << " sequences, " << postings << " postings, " << ds2i_blob_size(img) << " bytes ("
            << (8.0 * ds2i_blob_size(img) / postings) << " bits/posting)";
@@ -208,7 +174,7 @@ int main(int argc, const char** argv) {
         if (w) {
             ds2i_blob* wi = nullptr;
             if (ds2i_wand_freeze(w, &wi)) throw std::runtime_error("wand freeze failed");
-            write_blob(out_wand, wi);
+            tool::write_blob(out_wand, wi);
             ds2i_blob_free(wi);
             ds2i_wand_free(w);
         }

@@ -353,6 +353,37 @@ int ds2i_hip_verify_collection(int device, int index_kind, const void* image, si
  * comparison (ds2i_hip_verify_collection only), seconds[1] its bare upload (likewise), seconds[2] the staging of the postings. */
 void ds2i_hip_verify_host_seconds(double seconds[3]);
 
+/* Extraction: the postings back out of an index, and an image of one kind turned into an image of another. The decode is the
+ * verification's -- ONE launch over all blocks (chunks) of the lists asked for, one wavefront per block -- with stores instead of
+ * compares: the postings land in CSR form (the form of ds2i_hip_encode_index) in two device buffers of exactly the postings' size,
+ * 8 bytes per posting beside the index; what does not fit is DS2I_ENOMEM (there is no chunked form). device_ms (may be NULL): the
+ * hipEvent time of the kernels; 0 when none ran. An index holds neither the document sizes nor wand data: they do not come back.
+ *
+ * ds2i_hip_index_extract: lists [list_begin, list_end) of an open index as queries read it (the transcoded image when the upload
+ * transcoded; the decoder choice of ds2i_hip_index_verify). list_offsets receives list_end - list_begin + 1 offsets, from 0;
+ * *postings their last. docs == NULL and freqs == NULL is the size query: offsets and *postings only, nothing is launched (one of
+ * the two NULL is DS2I_EINVAL). list_begin > list_end or list_end > size is DS2I_EINVAL; a capacity (in postings) below *postings
+ * is DS2I_EINVAL with *postings set to what is needed. */
+int ds2i_hip_index_extract(ds2i_hip_index* idx, uint64_t list_begin, uint64_t list_end, uint64_t* list_offsets, uint32_t* docs,
+                           uint32_t* freqs, uint64_t capacity, uint64_t* postings, double* device_ms);
+/* The whole collection out of the caller's bytes with the on-disk decoders of that kind (all nine kinds), in the order of
+ * ds2i_hip_verify_collection: argument checks, the image parsed on the host (a bad image is ds2i_hip_index_open's DS2I_EFORMAT), only
+ * then the device: a bare upload (no tables, no transcoding), the kernel, close. list_offsets: u64[*nlists + 1]; docs / freqs:
+ * u32[postings]; free each with ds2i_blob_free. On an error no output is written. */
+int ds2i_hip_extract_collection(int device, int index_kind, const void* image, size_t bytes, uint64_t* num_docs, uint64_t* nlists,
+                                ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs, double* device_ms);
+/* An image of from_kind (any of the nine) as an image of to_kind, byte-identical to what the host builder writes for the same
+ * postings. to_kind: a kind ds2i_hip_encode_index writes (DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL, checked before the
+ * image is read), with that function's input rules (the Elias-Fano layouts: doc-ids strictly increasing, freqs >= 1). Bare upload,
+ * extraction into device buffers, the source image closed, then the encoder over the postings where they lie: for the block
+ * codecs they never leave the device, for the Elias-Fano layouts they come down once, for the host planner. device_ms: the
+ * extraction kernel plus the encoder's kernels. */
+int ds2i_hip_convert_index(int device, int from_kind, const void* image, size_t bytes, int to_kind, ds2i_blob** out_image,
+                           double* device_ms);
+/* Diagnostic: the host seconds of this thread's last ds2i_hip_extract_collection: seconds[0] the host parse of the image,
+ * seconds[1] its bare upload, seconds[2] the copy of the postings to the host. */
+void ds2i_hip_extract_host_seconds(double seconds[3]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
