@@ -147,6 +147,13 @@ def lib():
         L.ds2i_hip_encode_index.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_encode_host_seconds.argtypes = [C.POINTER(C.c_double)]
         L.ds2i_hip_encode_host_seconds.restype = None
+        L.ds2i_hip_encode_index_with.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint32, C.POINTER(vp),
+                                                 C.POINTER(C.c_double)]
+        L.ds2i_hip_encode_plan_ms.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_encode_plan_ms.restype = None
+        L.ds2i_hip_opt_partition.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64, C.POINTER(vp), C.POINTER(vp),
+                                             C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_opt_partition.argtypes = [C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.ds2i_hip_build_wand.argtypes = [C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_build_collection.argtypes = [C.c_int, C.c_int, vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(vp),
                                                 C.POINTER(C.c_double)]
@@ -289,16 +296,54 @@ def _csr(lists):
     return len(lists), offs, docs, freqs
 
 
-def gpu_encode_index(num_docs, lists, device=0, codec="block_optpfor"):
-    """The index image of `lists` (iterable of (docs, freqs)) encoded ON THE GPU (ds2i_hip_encode_index): byte-identical
+ENCODE_PLANS = {None: 0, "host": 1, "device": 2}  # DS2I_ENCODE_PLAN_* of ds2i_hip.h
+
+
+def gpu_encode_index(num_docs, lists, device=0, codec="block_optpfor", plan=None):
+    """The index image of `lists` (iterable of (docs, freqs)) encoded ON THE GPU (ds2i_hip_encode_index_with): byte-identical
     to build_index(codec, num_docs, lists). codec: "block_optpfor", "block_varint", "block_interpolative", or one of the
     Elias-Fano layouts "opt", "ef", "single", "uniform" (default global_parameters; doc-ids strictly increasing and
-    < num_docs, freqs >= 1, checked on the host). Returns (image bytes, device milliseconds of the kernels)."""
+    < num_docs, freqs >= 1, checked on the host). plan: who plans the partitions of "opt" -- "host", "device" (the partition
+    DP as HIP kernels) or None for the library's default; the image is the same, and the other codecs ignore it.
+    Returns (image bytes, device milliseconds of the kernels)."""
     n, offs, docs, freqs = _csr(lists)
     h, ms = C.c_void_p(), C.c_double()
-    _check(lib().ds2i_hip_encode_index(device, _codec(codec), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs),
-                                       C.byref(h), C.byref(ms)))
+    _check(lib().ds2i_hip_encode_index_with(device, _codec(codec), num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), ENCODE_PLANS[plan],
+                                            C.byref(h), C.byref(ms)))
     return _take_blob(h), ms.value
+
+
+def encode_plan_ms():
+    """hipEvent milliseconds of the partition kernels in this thread's last GPU encode call (ds2i_hip_encode_plan_ms): 0.0 when the
+    host planned or the codec has no partition DP."""
+    ms = C.c_double()
+    lib().ds2i_hip_encode_plan_ms(C.byref(ms))
+    return ms.value
+
+
+def _take_partitions(hs):
+    de, do, fe, fo = (np.frombuffer(_take_blob(h), dtype=t) for h, t in zip(hs, (np.uint32, np.uint64, np.uint32, np.uint64)))
+    return de, do, fe, fo
+
+
+def opt_partition(num_docs, lists):
+    """The partition end points the "opt" builder chooses for every list, planned ON THE HOST (ds2i_opt_partition): per side (docs:
+    the doc-ids; freqs: the strict prefix sums of the freqs) the exclusive end index of every partition of every list back to back
+    and len(lists) + 1 offsets into them. Returns (docs_ends uint32, docs_offs uint64, freqs_ends uint32, freqs_offs uint64)."""
+    n, offs, docs, freqs = _csr(lists)
+    hs = [C.c_void_p() for _ in range(4)]
+    _check(lib().ds2i_opt_partition(num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), *[C.byref(h) for h in hs]))
+    return _take_partitions(hs)
+
+
+def gpu_opt_partition(num_docs, lists, device=0, scratch_bytes=0):
+    """opt_partition planned ON THE GPU (ds2i_hip_opt_partition): the same four arrays, element for element. scratch_bytes: the DP
+    scratch one group of consecutive lists may take (12 bytes per posting and side; 0 = the library's default)."""
+    n, offs, docs, freqs = _csr(lists)
+    hs = [C.c_void_p() for _ in range(4)]
+    _check(lib().ds2i_hip_opt_partition(device, num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), scratch_bytes, *[C.byref(h) for h in hs],
+                                        None))
+    return _take_partitions(hs)
 
 
 def gpu_build_wand(doc_sizes, lists, device=0):

@@ -15,7 +15,8 @@ ARCH = "gfx950"
 # kernels.hip is compiled six times: once per list-count class (-DDS2I_TU_TMAX=n: the query kernels of that class; 0 = the long
 # class) and once for everything else; ranked_stream.hip holds the pipelined ranked_and kernels of the benchmark configuration,
 # union_stream.hip those of wand / maxscore / ranked_or (each once more for k > 64: _bigk); encode_kernels.hip holds the index
-# encoder, wand_kernels.hip the wand_data builder, freq_encode_kernels.hip the encoder of the Elias-Fano layouts.
+# encoder, wand_kernels.hip the wand_data builder, freq_encode_kernels.hip the encoder of the Elias-Fano layouts, partition_kernels.hip the
+# partition DP of the opt layout.
 RANKED_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [
     ("ranked_stream.hip", "ranked_stream.hip", []),
     ("ranked_stream.hip", "ranked_stream_bigk.hip", ["-DDS2I_RS_BIGK_TU"]),
@@ -27,7 +28,8 @@ RANKED_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]
 DOCS_UNITS = [(src, name.replace(".hip", "_docs.hip"), ["-DDS2I_DOCS_TU"] + defs) for src, name, defs in RANKED_UNITS]
 DEVICE_UNITS = RANKED_UNITS + [("kernels.hip", "kernels.hip", []), ("freq_stream.hip", "freq_stream.hip", []),
                                ("encode_kernels.hip", "encode_kernels.hip", []), ("wand_kernels.hip", "wand_kernels.hip", []),
-                               ("freq_encode_kernels.hip", "freq_encode_kernels.hip", [])] + DOCS_UNITS
+                               ("freq_encode_kernels.hip", "freq_encode_kernels.hip", []),
+                               ("partition_kernels.hip", "partition_kernels.hip", [])] + DOCS_UNITS
 HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "capi_build.cpp", "capi_encode.cpp", "capi_verify.cpp", "capi_extract.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-but-set-variable"]

@@ -418,4 +418,30 @@ struct FreqEncArgs {
     uint64_t nbits;
 };
 
+// ---- partition_kernels.hip: the partition DP of the opt layout, one wavefront per (list, side)
+// One item's scratch is n + 1 slots of `dist` and of `parent` from `base` on (slot p = "the first p elements are partitioned").
+struct PartItem {
+    uint32_t list;
+    uint32_t side; // 0 = docs (doc-ids over num_docs), 1 = freqs (strict prefix sums over occurrences + 1)
+    uint64_t base;
+};
+constexpr uint32_t PART_MAX_CLASSES = 64; // cost classes are lanes
+struct PartArgs {
+    const uint32_t* docs;
+    const uint64_t* cum;      // per posting: inclusive prefix sum of its list's freqs
+    const uint64_t* list_in;  // nlists + 1 posting offsets
+    uint64_t nlists;
+    uint64_t num_docs;
+    const PartItem* items;    // the group's items, longest first
+    uint32_t nitems;
+    const uint64_t* budget;   // the cost classes' budgets, ascending (computed on the host: the DP's only floating point)
+    uint32_t nbudgets;        // <= PART_MAX_CLASSES
+    uint64_t fix_cost;
+    unsigned long long* dist; // scratch; after the DP an item's end points lie, ascending, in the LAST count u32 of its dist slots
+    uint32_t* parent;         // scratch
+    uint32_t* count;          // [side * nlists + list]: number of partitions
+    const uint64_t* out_offs; // gather: [side * (nlists + 1) + list]: where the list's end points go in out_ends[side]
+    uint32_t* out_ends[2];
+};
+
 } // namespace ds2i_dev

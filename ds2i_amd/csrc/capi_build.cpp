@@ -9,6 +9,7 @@
 #include "capi_blob.hpp"
 #include "capi_error.hpp"
 #include "capi_hybrid.hpp"
+#include "capi_partition.hpp"
 #include "host_encode.hpp"
 #include "host_index.hpp"
 #include "host_pef.hpp"
@@ -157,6 +158,20 @@ int ds2i_encode_posting_list(int codec, uint32_t n, const uint32_t* docs, const 
     auto* blob = new ds2i_blob;
     write_posting_list(codec, blob->data, n, docs, freqs);
     *out = blob;
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_opt_partition(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                       ds2i_blob** docs_ends, ds2i_blob** docs_offs, ds2i_blob** freqs_ends, ds2i_blob** freqs_offs) {
+    if (!list_offsets || !docs || !freqs || !docs_ends || !docs_offs || !freqs_ends || !freqs_offs)
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_opt_partition: null argument");
+    DS2I_TRY
+    const std::string fault = freq_postings_fault("ds2i_opt_partition", num_docs, nlists, list_offsets, docs, freqs);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    opt_partitions parts;
+    host_opt_partitions(num_docs, nlists, list_offsets, docs, freqs, parts);
+    partition_blobs(parts, docs_ends, docs_offs, freqs_ends, freqs_offs);
     return 0;
     DS2I_CATCH
 }

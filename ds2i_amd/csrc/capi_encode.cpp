@@ -21,6 +21,7 @@
 #include "../../include/ds2i_build.h"
 #include "capi_blob.hpp"
 #include "capi_hybrid.hpp"
+#include "capi_partition.hpp"
 #include "capi_util.hpp"
 #include "host_freq_plan.hpp"
 #include "host_index.hpp"
@@ -174,26 +175,159 @@ int encode_staged(EncStage& st, int codec, uint64_t num_docs, ds2i_blob** image,
 }
 
 // ---- the Elias-Fano layouts (freq_index: opt, ef, single, uniform) over a staged collection
-constexpr int FREQ_PLAN_THREADS = 16; // the planning pool's cap: never the whole machine's CPU count
 
-// Plan on the host (for opt: optimal_partition, list-parallel), prefix sums and base sequences on the device, headers ORed into
-// the downloaded vectors, opt_index_builder::freeze around them. ms accumulates the hipEvent time of the kernels; the host's two
-// phases are left in freq_host_s for ds2i_hip_encode_host_seconds.
+// ---- the partition end points of the opt layout, planned on the device (partition_kernels.hip)
+// Which planner an opt encode takes when the caller does not say: the device's. The images are equal, so this is a question of time
+// alone, and on the configs[1] collection the whole call is a quarter shorter with it.
+constexpr bool OPT_PLAN_ON_DEVICE_BY_DEFAULT = true;
+// Bytes of DP scratch (12 per posting and side) one group of lists may take when the caller does not say. Lists are planned in
+// groups of consecutive lists whose scratch fits; a group holds at least one list, however long.
+constexpr uint64_t PART_SCRATCH_DEFAULT = 2ull << 30;
+
+// Every list's end points, both sides, over a staged collection whose prefix sums are in d_cum. ms accumulates the hipEvent time of
+// the kernels. Inside a group the items are launched longest first: list lengths are Zipf, and the DP of one list is a chain of n
+// dependent steps, so the longest list of a group is its critical path and must not start behind the short ones.
+int plan_partitions_staged(EncStage& st, uint64_t num_docs, const uint64_t* d_cum, uint64_t scratch_bytes, ds2i_host::opt_partitions& out,
+                           double& ms) {
+    using namespace ds2i_host;
+    const uint64_t nlists = st.nlists;
+    const uint64_t* offs = st.list_offsets;
+    for (int side = 0; side < 2; ++side) {
+        out.offs[side].assign(nlists + 1, 0);
+        out.ends[side].clear();
+    }
+    if (!nlists) return DS2I_OK;
+    if (nlists >= (1ull << 30)) return ds2i_set_error(DS2I_EINVAL, "more than 2^30 lists");
+    if (!scratch_bytes) scratch_bytes = PART_SCRATCH_DEFAULT;
+    const partition_config conf;
+    const global_parameters params;
+    // the budgets of the cost classes: the DP's only floating point, by the host planner's own expression (both sides cost one
+    // element the same: fix_cost)
+    const std::vector<uint64_t> budget = partition_budgets(partition_cost<false>(params, 1, 1, conf.fix_cost), ~uint64_t(0), conf.eps1, conf.eps2);
+    if (budget.size() > ds2i_dev::PART_MAX_CLASSES) return ds2i_set_error(DS2I_EINVAL, "too many cost classes for the device planner");
+    auto slots_of = [&](uint64_t t) { return 2 * (offs[t + 1] - offs[t] + 1); }; // dist / parent slots of list t, both sides
+    std::vector<uint64_t> group_end;
+    uint64_t max_slots = 0, max_lists = 0;
+    for (uint64_t t = 0; t < nlists;) {
+        uint64_t slots = slots_of(t), t1 = t + 1;
+        while (t1 < nlists && (slots + slots_of(t1)) * 12 <= scratch_bytes) slots += slots_of(t1++);
+        group_end.push_back(t1);
+        max_slots = std::max(max_slots, slots);
+        max_lists = std::max(max_lists, t1 - t);
+        t = t1;
+    }
+    ds2i_dev::PartArgs a{};
+    ds2i_dev::PartItem* d_items = nullptr;
+    uint64_t *d_budget = nullptr, *d_out_offs = nullptr;
+    HIP_OK(st.dev.alloc(&a.dist, 8 * max_slots));
+    HIP_OK(st.dev.alloc(&a.parent, 4 * max_slots));
+    HIP_OK(st.dev.alloc(&d_items, sizeof(ds2i_dev::PartItem) * 2 * max_lists));
+    HIP_OK(st.dev.alloc(&d_budget, 8 * budget.size()));
+    HIP_OK(st.dev.alloc(&a.count, 4 * 2 * nlists));
+    HIP_OK(st.dev.alloc(&d_out_offs, 8 * 2 * (nlists + 1)));
+    HIP_OK(st.dev.alloc(&a.out_ends[0], 4 * offs[nlists])); // (a list of n postings has at most n partitions)
+    HIP_OK(st.dev.alloc(&a.out_ends[1], 4 * offs[nlists]));
+    HIP_OK(hipMemcpy(d_budget, budget.data(), 8 * budget.size(), hipMemcpyHostToDevice));
+    a.docs = st.a.docs;
+    a.cum = d_cum;
+    a.list_in = st.a.list_in;
+    a.nlists = nlists;
+    a.num_docs = num_docs;
+    a.items = d_items;
+    a.budget = d_budget;
+    a.nbudgets = (uint32_t)budget.size();
+    a.fix_cost = conf.fix_cost;
+    a.out_offs = d_out_offs;
+    std::vector<ds2i_dev::PartItem> items;
+    std::vector<uint64_t> order;
+    std::vector<uint32_t> count;
+    for (uint64_t t0 = 0, g = 0; g < group_end.size(); t0 = group_end[g++]) {
+        const uint64_t t1 = group_end[g], nl = t1 - t0;
+        order.resize(nl);
+        for (uint64_t k = 0; k < nl; ++k) order[k] = t0 + k;
+        std::stable_sort(order.begin(), order.end(), [&](uint64_t x, uint64_t y) { return offs[x + 1] - offs[x] > offs[y + 1] - offs[y]; });
+        items.clear();
+        uint64_t base = 0;
+        for (uint64_t t : order)
+            for (uint32_t side = 0; side < 2; ++side) {
+                items.push_back(ds2i_dev::PartItem{(uint32_t)t, side, base});
+                base += offs[t + 1] - offs[t] + 1;
+            }
+        HIP_OK(hipMemcpy(d_items, items.data(), sizeof(ds2i_dev::PartItem) * items.size(), hipMemcpyHostToDevice));
+        a.nitems = (uint32_t)items.size();
+        HIP_OK(timed_span(nullptr, ms, [&] { return ds2i_launch_partition_plan(a, nullptr); }));
+        // the counts of the group's lists -> where their end points go
+        count.resize(nl);
+        for (int side = 0; side < 2; ++side) {
+            HIP_OK(hipMemcpy(count.data(), a.count + side * nlists + t0, 4 * nl, hipMemcpyDeviceToHost));
+            for (uint64_t k = 0; k < nl; ++k) {
+                if (!count[k] || count[k] > offs[t0 + k + 1] - offs[t0 + k]) return ds2i_set_error(DS2I_EFORMAT, "the device planner returned an impossible partition count");
+                out.offs[side][t0 + k + 1] = out.offs[side][t0 + k] + count[k];
+            }
+            HIP_OK(hipMemcpy(d_out_offs + side * (nlists + 1) + t0, out.offs[side].data() + t0, 8 * (nl + 1), hipMemcpyHostToDevice));
+        }
+        HIP_OK(timed_span(nullptr, ms, [&] { return ds2i_launch_partition_gather(a, nullptr); }));
+    }
+    for (int side = 0; side < 2; ++side) {
+        out.ends[side].resize(out.offs[side][nlists]);
+        HIP_OK(hipMemcpy(out.ends[side].data(), a.out_ends[side], 4 * out.ends[side].size(), hipMemcpyDeviceToHost));
+    }
+    return DS2I_OK;
+}
+
+// the 64-bit prefix sums of every list's freqs (positive_sequence), left in *d_cum
+int prefix_sums_staged(EncStage& st, uint64_t** d_cum, double& ms) {
+    uint64_t* d_blk_base = nullptr;
+    HIP_OK(st.dev.alloc(&d_blk_base, 8 * st.nblocks));
+    HIP_OK(st.dev.alloc(d_cum, 8 * st.list_offsets[st.nlists]));
+    HIP_OK(timed_span(nullptr, ms, [&] {
+        return st.nblocks ? ds2i_launch_freq_prefix_sums(st.a, st.nlists, d_blk_base, *d_cum, st.grid, nullptr) : hipSuccess;
+    }));
+    return DS2I_OK;
+}
+
+// how an opt encode plans its partitions: DS2I_ENCODE_PLAN_* of ds2i_hip.h, 0 = the default
+int plan_on_device(const char* who, uint32_t flags, bool& device) {
+    if ((flags & DS2I_ENCODE_PLAN_HOST) && (flags & DS2I_ENCODE_PLAN_DEVICE))
+        return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": both planners asked for").c_str());
+    device = (flags & DS2I_ENCODE_PLAN_DEVICE) || (!(flags & DS2I_ENCODE_PLAN_HOST) && OPT_PLAN_ON_DEVICE_BY_DEFAULT);
+    return DS2I_OK;
+}
+
+// Plan (for opt: the partition end points, by optimal_partition list-parallel on the host or by the device planner; then headers
+// and jobs on the host), prefix sums and base sequences on the device, headers ORed into the downloaded vectors,
+// opt_index_builder::freeze around them. ms accumulates the hipEvent time of the kernels; the host's two phases are left in
+// freq_host_s for ds2i_hip_encode_host_seconds, the partition kernels' time in freq_plan_ms for ds2i_hip_encode_plan_ms.
 thread_local double freq_host_s[2] = {0.0, 0.0}; // seconds of {planning, download + headers + freeze} of this thread's last call
-int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image,
-                       double& ms) {
+thread_local double freq_plan_ms = 0.0;          // hipEvent time of the partition kernels of this thread's last call
+int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32_t* docs, const uint32_t* freqs, bool device_plan,
+                       ds2i_blob** image, double& ms) {
     using namespace ds2i_host;
     const auto t0 = std::chrono::steady_clock::now();
     const uint64_t nlists = st.nlists;
     const uint64_t* offs = st.list_offsets;
     const uint64_t postings = offs[nlists];
     const global_parameters params;
+    // ---- device: the prefix sums of the freqs, which the device planner and the writer share
+    uint64_t* d_cum = nullptr;
+    double plan_phase_ms = 0.0; // kernel time inside the planning phase: not the host's
+    STAGE_OK(prefix_sums_staged(st, &d_cum, plan_phase_ms));
+    opt_partitions parts;
+    device_plan = device_plan && layout == LAYOUT_OPT;
+    if (device_plan) {
+        STAGE_OK(plan_partitions_staged(st, num_docs, d_cum, 0, parts, freq_plan_ms));
+        plan_phase_ms += freq_plan_ms;
+    }
+    ms += plan_phase_ms;
     std::vector<freq_list_plan> plans(nlists);
-    // (the calling thread and up to FREQ_PLAN_THREADS - 1 more, never more threads than lists)
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned threads = (unsigned)std::min<uint64_t>(std::min<unsigned>(hw, FREQ_PLAN_THREADS), std::max<uint64_t>(nlists, 1));
+    const unsigned threads = plan_threads(nlists);
     parallel_for(nlists, threads, [&](uint64_t t, unsigned) {
-        plan_list(layout, num_docs, params, offs[t], offs[t + 1] - offs[t], docs + offs[t], freqs + offs[t], plans[t]);
+        if (device_plan) {
+            const std::vector<uint32_t> de = parts.of(0, t), fe = parts.of(1, t);
+            plan_list(layout, num_docs, params, offs[t], offs[t + 1] - offs[t], docs + offs[t], freqs + offs[t], plans[t], &de, &fe);
+        } else {
+            plan_list(layout, num_docs, params, offs[t], offs[t + 1] - offs[t], docs + offs[t], freqs + offs[t], plans[t]);
+        }
     }, true);
     // where every list starts in the two bit vectors; the jobs move to their final offsets
     std::vector<uint64_t> ends[2], head_at[2];
@@ -217,10 +351,7 @@ int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32
         }
     }
     const auto t1 = std::chrono::steady_clock::now();
-    // ---- device: prefix sums of the freqs, then the base sequences of both sides
-    uint64_t *d_blk_base = nullptr, *d_cum = nullptr;
-    HIP_OK(st.dev.alloc(&d_blk_base, 8 * st.nblocks));
-    HIP_OK(st.dev.alloc(&d_cum, 8 * postings));
+    // ---- device: the base sequences of both sides
     ds2i_dev::FreqEncArgs fa[2];
     uint64_t words[2];
     for (int side = 0; side < 2; ++side) {
@@ -242,8 +373,7 @@ int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32
     }
     HIP_OK(timed_span(nullptr, ms, [&] {
         if (!st.nblocks) return hipSuccess;
-        hipError_t e = ds2i_launch_freq_prefix_sums(st.a, nlists, d_blk_base, d_cum, st.grid, nullptr);
-        if (e == hipSuccess) e = ds2i_launch_freq_write(0, fa[0], st.grid, nullptr);
+        hipError_t e = ds2i_launch_freq_write(0, fa[0], st.grid, nullptr);
         if (e == hipSuccess) e = ds2i_launch_freq_write(1, fa[1], st.grid, nullptr);
         return e;
     }));
@@ -263,7 +393,7 @@ int freq_encode_staged(EncStage& st, int layout, uint64_t num_docs, const uint32
     builder.freeze(blob->data);
     *image = blob.release();
     DS2I_CATCH
-    freq_host_s[0] = std::chrono::duration<double>(t1 - t0).count();
+    freq_host_s[0] = std::chrono::duration<double>(t1 - t0).count() - 1e-3 * plan_phase_ms;
     freq_host_s[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count();
     return DS2I_OK;
 }
@@ -291,13 +421,16 @@ int wand_max_staged(EncStage& st, const std::vector<float>& norm_lens, std::vect
 // `norm_lens` (wand_image non-null), from ONE upload. Neither output is touched unless both succeed.
 int build_images(const char* who, int device, int codec, uint64_t num_docs, const std::vector<float>* norm_lens, uint64_t nlists,
                  const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs, ds2i_blob** index_image,
-                 ds2i_blob** wand_image, double* device_ms) {
+                 ds2i_blob** wand_image, double* device_ms, uint32_t plan_flags = 0) {
+    bool device_plan = false;
+    STAGE_OK(plan_on_device(who, plan_flags, device_plan));
+    freq_plan_ms = 0.0;
     EncStage st;
     STAGE_OK(st.upload(who, device, nlists, list_offsets, docs, freqs));
     double ms = 0.0;
     ds2i_blob* ib = nullptr;
     if (index_image)
-        STAGE_OK(ds2i_host::is_freq_layout(codec) ? freq_encode_staged(st, codec, num_docs, docs, freqs, &ib, ms)
+        STAGE_OK(ds2i_host::is_freq_layout(codec) ? freq_encode_staged(st, codec, num_docs, docs, freqs, device_plan, &ib, ms)
                                                   : encode_staged(st, codec, num_docs, &ib, ms));
     std::unique_ptr<ds2i_blob> index_blob(ib), wand_blob;
     if (wand_image) {
@@ -339,32 +472,60 @@ int check_postings(const char* who, uint64_t num_docs, uint64_t nlists, const ui
     }
     return DS2I_OK;
 }
-// what the Elias-Fano layouts rely on, checked before anything is staged: no empty list, doc-ids strictly increasing and below
-// num_docs (the sequences are sorted sets over that universe), every freq >= 1 (a zero makes the prefix sums non-strict)
+// what the Elias-Fano layouts rely on (host_freq_plan.hpp: freq_postings_fault), checked before anything is staged
 int check_freq_postings(const char* who, uint64_t num_docs, uint64_t nlists, const uint64_t* offs, const uint32_t* docs,
                         const uint32_t* freqs) {
-    const std::string w(who);
-    for (uint64_t t = 0; t < nlists; ++t) {
-        if (offs[t + 1] <= offs[t]) return ds2i_set_error(DS2I_EINVAL, "List must be nonempty");
-        if (offs[t + 1] - offs[t] > 0xFFFFFFFFull) return ds2i_set_error(DS2I_EINVAL, "posting list longer than 2^32");
-        for (uint64_t i = offs[t]; i < offs[t + 1]; ++i) {
-            if (i > offs[t] && docs[i] <= docs[i - 1]) return ds2i_set_error(DS2I_EINVAL, (w + ": doc ids not strictly increasing").c_str());
-            if (docs[i] >= num_docs) return ds2i_set_error(DS2I_EINVAL, (w + ": doc id out of range").c_str());
-            if (!freqs[i]) return ds2i_set_error(DS2I_EINVAL, (w + ": zero freq").c_str());
-        }
-    }
-    return DS2I_OK;
+    const std::string fault = ds2i_host::freq_postings_fault(who, num_docs, nlists, offs, docs, freqs);
+    return fault.empty() ? DS2I_OK : ds2i_set_error(DS2I_EINVAL, fault.c_str());
+}
+} // namespace
+
+namespace {
+int encode_index(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                 const uint32_t* docs, const uint32_t* freqs, uint32_t flags, ds2i_blob** image, double* device_ms) {
+    if (!list_offsets || !docs || !freqs || !image) return ds2i_set_error(DS2I_EINVAL, (std::string(who) + ": null argument").c_str());
+    bool device_plan = false;
+    STAGE_OK(plan_on_device(who, flags, device_plan));
+    int codec = 0;
+    STAGE_OK(encoder_kind_of(who, index_kind, codec));
+    if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings(who, num_docs, nlists, list_offsets, docs, freqs));
+    DS2I_TRY
+    return build_images(who, device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms, flags);
+    DS2I_CATCH
 }
 } // namespace
 
 extern "C" int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                                      const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms) {
-    if (!list_offsets || !docs || !freqs || !image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_encode_index: null argument");
-    int codec = 0;
-    STAGE_OK(encoder_kind_of("ds2i_hip_encode_index", index_kind, codec));
-    if (ds2i_host::is_freq_layout(codec)) STAGE_OK(check_freq_postings("ds2i_hip_encode_index", num_docs, nlists, list_offsets, docs, freqs));
+    return encode_index("ds2i_hip_encode_index", device, index_kind, num_docs, nlists, list_offsets, docs, freqs, 0, image, device_ms);
+}
+
+extern "C" int ds2i_hip_encode_index_with(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                                          const uint32_t* docs, const uint32_t* freqs, uint32_t flags, ds2i_blob** image, double* device_ms) {
+    return encode_index("ds2i_hip_encode_index_with", device, index_kind, num_docs, nlists, list_offsets, docs, freqs, flags, image, device_ms);
+}
+
+extern "C" void ds2i_hip_encode_plan_ms(double* ms) {
+    if (ms) *ms = freq_plan_ms;
+}
+
+extern "C" int ds2i_hip_opt_partition(int device, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs,
+                                      const uint32_t* freqs, uint64_t scratch_bytes, ds2i_blob** docs_ends, ds2i_blob** docs_offs,
+                                      ds2i_blob** freqs_ends, ds2i_blob** freqs_offs, double* device_ms) {
+    if (!list_offsets || !docs || !freqs || !docs_ends || !docs_offs || !freqs_ends || !freqs_offs)
+        return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_opt_partition: null argument");
+    STAGE_OK(check_freq_postings("ds2i_hip_opt_partition", num_docs, nlists, list_offsets, docs, freqs));
     DS2I_TRY
-    return build_images("ds2i_hip_encode_index", device, codec, num_docs, nullptr, nlists, list_offsets, docs, freqs, image, nullptr, device_ms);
+    EncStage st;
+    STAGE_OK(st.upload("ds2i_hip_opt_partition", device, nlists, list_offsets, docs, freqs));
+    double prefix_ms = 0.0, ms = 0.0;
+    uint64_t* d_cum = nullptr;
+    STAGE_OK(prefix_sums_staged(st, &d_cum, prefix_ms));
+    ds2i_host::opt_partitions parts;
+    STAGE_OK(plan_partitions_staged(st, num_docs, d_cum, scratch_bytes, parts, ms));
+    partition_blobs(parts, docs_ends, docs_offs, freqs_ends, freqs_offs);
+    if (device_ms) *device_ms = prefix_ms + ms;
+    return DS2I_OK;
     DS2I_CATCH
 }
 
@@ -377,6 +538,7 @@ int ds2i_check_encoder_kind(const char* who, int index_kind) {
 int ds2i_encode_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                                 uint32_t* d_docs, uint32_t* d_freqs, ds2i_blob** image, double* device_ms) {
     DS2I_TRY
+    freq_plan_ms = 0.0;
     EncStage st;
     const int adopted = st.adopt(who, device, nlists, list_offsets, d_docs, d_freqs);
     int codec = 0;
@@ -385,13 +547,13 @@ int ds2i_encode_device_postings(const char* who, int device, int index_kind, uin
     double ms = 0.0;
     ds2i_blob* ib = nullptr;
     if (ds2i_host::is_freq_layout(codec)) {
-        // the host planner reads the postings: they come down once, and the base sequences are written from the device copy
+        // the host writes the headers from the postings: they come down once, and the base sequences are written from the device copy
         const uint64_t total = list_offsets[nlists];
         std::vector<uint32_t> docs(total ? total : 1), freqs(total ? total : 1);
         HIP_OK(hipMemcpy(docs.data(), d_docs, 4 * total, hipMemcpyDeviceToHost));
         HIP_OK(hipMemcpy(freqs.data(), d_freqs, 4 * total, hipMemcpyDeviceToHost));
         STAGE_OK(check_freq_postings(who, num_docs, nlists, list_offsets, docs.data(), freqs.data()));
-        STAGE_OK(freq_encode_staged(st, codec, num_docs, docs.data(), freqs.data(), &ib, ms));
+        STAGE_OK(freq_encode_staged(st, codec, num_docs, docs.data(), freqs.data(), OPT_PLAN_ON_DEVICE_BY_DEFAULT, &ib, ms));
     } else {
         STAGE_OK(encode_staged(st, codec, num_docs, &ib, ms));
     }

@@ -10,12 +10,11 @@
 #include <cstring>
 #include <vector>
 
+#include "seq_cost.hpp" // msb64, ceil_log2
+
 namespace ds2i_host {
 
-inline uint32_t msb64(uint64_t x) { assert(x); return 63u - (uint32_t)__builtin_clzll(x); }
 inline uint32_t msb32(uint32_t x) { assert(x); return 31u - (uint32_t)__builtin_clz(x); }
-// util.hpp:30-33
-inline uint64_t ceil_log2(uint64_t x) { return x > 1 ? msb64(x - 1) + 1 : 0; }
 template <class A, class B> inline A ceil_div(A a, B b) { return (a + b - 1) / b; }
 
 // Growable LSB-first bit string (the role of succinct::bit_vector_builder).

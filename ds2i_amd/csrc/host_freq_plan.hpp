@@ -5,10 +5,14 @@
 // list's HEADER alone (gamma / delta codes, first value, the EF of the bounds and inner ends, the end offsets), which always
 // precedes the list's base sequences. A list side = header | base sequences back to back.
 #pragma once
+#include <algorithm>
 #include <cstdint>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "abi_structs.hpp"
+#include "host_parallel.hpp"
 #include "host_pef.hpp"
 
 namespace ds2i_host {
@@ -108,14 +112,86 @@ struct freq_list_plan {
     std::vector<ds2i_dev::FreqJob> jobs[2];  // offsets relative to the end of the header
 };
 
-// opt_index_builder::encode_list with the base sequences planned instead of written (for opt this runs optimal_partition)
+// opt_index_builder::encode_list with the base sequences planned instead of written. For opt this runs optimal_partition, unless
+// the end points of the two sides are given (docs_ends, freqs_ends: the device planner's)
 inline void plan_list(int layout, uint64_t num_docs, global_parameters const& params, uint64_t first_posting, uint64_t n,
-                      const uint32_t* docs, const uint32_t* freqs, freq_list_plan& out) {
+                      const uint32_t* docs, const uint32_t* freqs, freq_list_plan& out, const std::vector<uint32_t>* docs_ends = nullptr,
+                      const std::vector<uint32_t>* freqs_ends = nullptr) {
     planned_bodies<false> db(params, first_posting, out.jobs[0]);
     planned_bodies<true> fb(params, first_posting, out.jobs[1]);
-    opt_index_builder::encode_list(num_docs, params, n, docs, freqs, out.head[0], out.head[1], layout, db, fb);
+    opt_index_builder::encode_list(num_docs, params, n, docs, freqs, out.head[0], out.head[1], layout, db, fb, docs_ends, freqs_ends);
     out.body_bits[0] = db.size();
     out.body_bits[1] = fb.size();
+}
+
+// What the Elias-Fano layouts rely on: no empty list, doc-ids strictly increasing and below num_docs (the sequences are sorted sets
+// over that universe), every freq >= 1 (a zero makes the prefix sums non-strict). Empty, or the message of the first violation.
+inline std::string freq_postings_fault(const char* who, uint64_t num_docs, uint64_t nlists, const uint64_t* offs, const uint32_t* docs,
+                                       const uint32_t* freqs) {
+    const std::string w(who);
+    for (uint64_t t = 0; t < nlists; ++t) {
+        if (offs[t + 1] <= offs[t]) return "List must be nonempty";
+        if (offs[t + 1] - offs[t] > 0xFFFFFFFFull) return "posting list longer than 2^32";
+        for (uint64_t i = offs[t]; i < offs[t + 1]; ++i) {
+            if (i > offs[t] && docs[i] <= docs[i - 1]) return w + ": doc ids not strictly increasing";
+            if (docs[i] >= num_docs) return w + ": doc id out of range";
+            if (!freqs[i]) return w + ": zero freq";
+        }
+    }
+    return std::string();
+}
+
+// The partition end points of the opt layout for every list of a CSR collection: ends[side] holds every list's end points back to
+// back, offs[side][t] .. offs[side][t + 1] those of list t (side 0 = docs over num_docs, 1 = the prefix sums over occurrences + 1)
+struct opt_partitions {
+    std::vector<uint32_t> ends[2];
+    std::vector<uint64_t> offs[2];
+    std::vector<uint32_t> of(int side, uint64_t t) const {
+        return std::vector<uint32_t>(ends[side].begin() + offs[side][t], ends[side].begin() + offs[side][t + 1]);
+    }
+};
+// ... of one list, planned on the host (what partitioned_write plans for the two sides of encode_list)
+inline void host_list_partitions(uint64_t num_docs, global_parameters const& params, uint64_t n, const uint32_t* docs,
+                                 const uint32_t* freqs, std::vector<uint32_t> ends[2]) {
+    std::vector<uint64_t> d(n), cum(n);
+    uint64_t occurrences = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        d[i] = docs[i];
+        occurrences += freqs[i];
+        cum[i] = occurrences;
+    }
+    ends[0] = partition_ends<false>(d.data(), num_docs, n, params);
+    ends[1] = partition_ends<true>(cum.data(), occurrences + 1, n, params);
+}
+
+// the planning pool: the calling thread and up to FREQ_PLAN_THREADS - 1 more -- never the whole machine's CPU count, never more
+// threads than lists
+constexpr unsigned FREQ_PLAN_THREADS = 16;
+inline unsigned plan_threads(uint64_t nlists) {
+    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
+    return (unsigned)std::min<uint64_t>(std::min(hw, FREQ_PLAN_THREADS), std::max<uint64_t>(nlists, 1));
+}
+// ... of every list of a collection, list-parallel: the reference of the device planner
+inline void host_opt_partitions(uint64_t num_docs, uint64_t nlists, const uint64_t* offs, const uint32_t* docs, const uint32_t* freqs,
+                                opt_partitions& out) {
+    const global_parameters params;
+    std::vector<std::vector<uint32_t>> ends[2];
+    ends[0].resize(nlists);
+    ends[1].resize(nlists);
+    parallel_for(nlists, plan_threads(nlists), [&](uint64_t t, unsigned) {
+        std::vector<uint32_t> e[2];
+        host_list_partitions(num_docs, params, offs[t + 1] - offs[t], docs + offs[t], freqs + offs[t], e);
+        ends[0][t] = std::move(e[0]);
+        ends[1][t] = std::move(e[1]);
+    }, true);
+    for (int side = 0; side < 2; ++side) {
+        out.ends[side].clear();
+        out.offs[side].assign(nlists + 1, 0);
+        for (uint64_t t = 0; t < nlists; ++t) {
+            out.ends[side].insert(out.ends[side].end(), ends[side][t].begin(), ends[side][t].end());
+            out.offs[side][t + 1] = out.ends[side].size();
+        }
+    }
 }
 
 // ORs the `n` bits of `src` into `dst` at bit `pos`, touching only the words they cover

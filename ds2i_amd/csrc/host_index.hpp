@@ -19,10 +19,7 @@
 
 namespace ds2i_host {
 
-struct global_parameters {
-    uint8_t ef_log_sampling0 = 9, ef_log_sampling1 = 8, rb_log_rank1_sampling = 9, rb_log_sampling1 = 8,
-            log_partition_size = 7;
-};
+// global_parameters and ef_offsets (the layout of compact_elias_fano): seq_cost.hpp
 
 // ------------------------------------------------------------ posting list (A2)
 // vbyte(n) | u32 block_max[nb] | u32 block_endpoint[nb-1] | block0 docs | block0 freqs | ...
@@ -55,25 +52,6 @@ inline void write_posting_list(int codec, bytes_t& out, uint32_t n, const uint32
 }
 
 // ------------------------------------------------------------ Elias-Fano (a13)
-struct ef_offsets {
-    uint64_t universe, n, log_sampling0, log_sampling1, lower_bits, mask, higher_bits_length, pointer_size,
-        pointers0, pointers1, pointers0_offset, pointers1_offset, higher_bits_offset, lower_bits_offset, end;
-    ef_offsets(uint64_t base, uint64_t u, uint64_t n_, global_parameters const& p)
-        : universe(u), n(n_), log_sampling0(p.ef_log_sampling0), log_sampling1(p.ef_log_sampling1) {
-        lower_bits = u > n ? msb64(u / n) : 0;
-        mask = (uint64_t(1) << lower_bits) - 1;
-        higher_bits_length = n + (u >> lower_bits) + 2;
-        pointer_size = ceil_log2(higher_bits_length);
-        pointers0 = (higher_bits_length - n) >> log_sampling0;
-        pointers1 = n >> log_sampling1;
-        pointers0_offset = base;
-        pointers1_offset = pointers0_offset + pointers0 * pointer_size;
-        higher_bits_offset = pointers1_offset + pointers1 * pointer_size;
-        lower_bits_offset = higher_bits_offset + higher_bits_length;
-        end = lower_bits_offset + n * lower_bits;
-    }
-};
-
 // Sampled positions of a finished 0/1 array, straight from their definition (SURVEY.md Appendix A6, and what
 // test_compact_elias_fano.cpp:45-80 / test_compact_ranked_bitvector.cpp:36-68 check by a direct scan): the `len` bits at
 // `first` are walked 64 at a time; on_chunk(pos, bits, nbits, ones_before) gets the chunk that starts at relative

@@ -44,25 +44,7 @@ inline void write_delta(bitvec_builder& bvb, uint64_t n) {
     bvb.append_bits(nn ^ hb, (unsigned)l);
 }
 
-// ---------------------------------------------------------------- ranked bitvector
-struct rb_offsets {
-    uint64_t universe, n, log_rank1_sampling, log_sampling1, rank1_sample_size, pointer_size, rank1_samples, pointers1,
-        rank1_samples_offset, pointers1_offset, bits_offset, end;
-    rb_offsets(uint64_t base, uint64_t u, uint64_t n_, global_parameters const& p)
-        : universe(u), n(n_), log_rank1_sampling(p.rb_log_rank1_sampling), log_sampling1(p.rb_log_sampling1) {
-        rank1_sample_size = ceil_log2(n + 1);
-        pointer_size = ceil_log2(u);
-        rank1_samples = log_rank1_sampling >= 64 ? 0 : (u >> log_rank1_sampling);
-        pointers1 = n >> log_sampling1;
-        rank1_samples_offset = base;
-        pointers1_offset = rank1_samples_offset + rank1_samples * rank1_sample_size;
-        bits_offset = pointers1_offset + pointers1 * pointer_size;
-        end = bits_offset + u;
-    }
-};
-inline uint64_t rb_bitsize(global_parameters const& p, uint64_t u, uint64_t n) { return rb_offsets(0, u, n, p).end; }
-inline uint64_t ef_bitsize(global_parameters const& p, uint64_t u, uint64_t n) { return ef_offsets(0, u, n, p).end; }
-
+// ---------------------------------------------------------------- ranked bitvector (rb_offsets, rb_bitsize, ef_bitsize: seq_cost.hpp)
 // compact_ranked_bitvector image (layout: `rb_offsets`): rank1_samples | pointers1 | the `universe`-bit characteristic
 // vector. As for Elias-Fano the auxiliary arrays are written from their meaning, in a second pass over the finished
 // vector: rank1_samples[k-1] = number of ones before position k * 2^r (k >= 1), pointers1[k-1] = position of the one
@@ -102,29 +84,7 @@ inline void rb_write(bitvec_builder& bvb, It begin, uint64_t universe, uint64_t 
 }
 
 // ---------------------------------------------------------------- indexed / strict sequences
-enum seq_type : int { SEQ_EF = 0, SEQ_RB = 1, SEQ_ALL_ONES = 2 };
-static const uint64_t SEQ_TYPE_BITS = 1;
-
-inline global_parameters strict_params(global_parameters p) {
-    p.ef_log_sampling0 = 63;
-    p.rb_log_rank1_sampling = 63;
-    return p;
-}
-
-template <bool STRICT>
-inline uint64_t seq_bitsize(global_parameters const& params, uint64_t universe, uint64_t n, int* type_out = nullptr) {
-    uint64_t best = (universe == n) ? 0 : uint64_t(-1);
-    int type = SEQ_ALL_ONES;
-    if (best) {
-        const global_parameters sp = STRICT ? strict_params(params) : params;
-        uint64_t ef = (STRICT ? ef_bitsize(sp, universe - n + 1, n) : ef_bitsize(sp, universe, n)) + SEQ_TYPE_BITS;
-        if (ef < best) { best = ef; type = SEQ_EF; }
-        uint64_t rb = rb_bitsize(sp, universe, n) + SEQ_TYPE_BITS;
-        if (rb < best) { best = rb; type = SEQ_RB; }
-    }
-    if (type_out) *type_out = type;
-    return best;
-}
+// seq_type, strict_params, seq_bitsize -- which of Elias-Fano, ranked bitvector and all-ones a base sequence takes, and its bits: seq_cost.hpp
 
 // values: sorted (strictly increasing for STRICT / ranked bitvector), < universe
 template <bool STRICT>
@@ -199,6 +159,17 @@ struct partition_config { double eps1 = 0.03, eps2 = 0.3; uint64_t fix_cost = 64
 // Parameters, edge order and the strict `<` of the relaxation match the reference builder
 // (optimal_partition.hpp:67-121, eps1 = 0.03, eps2 = 0.3, configuration.hpp), so the chosen end points -- and with
 // them the image -- are the ones ds2i's create_freq_index would choose.
+// the budgets of the cost classes, cheapest first: the only floating point of the DP. The list breaks off at the first budget that
+// covers `whole`; with whole = UINT64_MAX it is the full list every sequence's own list is a prefix of (eps1 > 0).
+inline std::vector<uint64_t> partition_budgets(uint64_t c_min, uint64_t whole, double eps1, double eps2) {
+    std::vector<uint64_t> budget;
+    for (uint64_t bnd = c_min; eps1 == 0 || bnd < c_min / eps1; bnd = (uint64_t)(bnd * (1 + eps2))) {
+        budget.push_back(bnd);
+        if (bnd >= whole) break;
+    }
+    return budget;
+}
+
 template <class CostFun>
 inline std::vector<uint32_t> optimal_partition(const uint64_t* seq, uint64_t universe, uint64_t size, CostFun cost_fun,
                                                double eps1, double eps2) {
@@ -206,12 +177,8 @@ inline std::vector<uint32_t> optimal_partition(const uint64_t* seq, uint64_t uni
     std::vector<uint64_t> dist(size + 1, whole); // cheapest known cost of partitioning the first p elements
     std::vector<uint32_t> parent(size + 1, 0);
     dist[0] = 0;
-    std::vector<uint64_t> budget, reach, reach_top;
-    const uint64_t c_min = cost_fun(1, 1);
-    for (uint64_t bnd = c_min; eps1 == 0 || bnd < c_min / eps1; bnd = (uint64_t)(bnd * (1 + eps2))) {
-        budget.push_back(bnd);
-        if (bnd >= whole) break;
-    }
+    const std::vector<uint64_t> budget = partition_budgets(cost_fun(1, 1), whole, eps1, eps2);
+    std::vector<uint64_t> reach, reach_top;
     reach.assign(budget.size(), 0);
     reach_top.assign(budget.size(), 0);
     for (uint64_t i = 0; i < size; ++i) {
@@ -286,11 +253,17 @@ inline void write_partition_table(bitvec_builder& out, const uint64_t* seq, uint
 }
 
 // partitioned_sequence: end points from the (1+eps)-approximate shortest path (optimal_partition above)
+template <bool STRICT>
+inline std::vector<uint32_t> partition_ends(const uint64_t* seq, uint64_t universe, uint64_t n, global_parameters const& params,
+                                            partition_config const& conf = partition_config()) {
+    auto cost_fun = [&](uint64_t u, uint64_t m) { return partition_cost<STRICT>(params, u, m, conf.fix_cost); };
+    return optimal_partition(seq, universe, n, cost_fun, conf.eps1, conf.eps2);
+}
+// `given_ends`: the end points somebody else planned (the device planner, partition_kernels.hip); null = plan them here
 template <bool STRICT, class Bodies>
 inline void partitioned_write(bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n,
-                              global_parameters const& params, Bodies& bodies, partition_config const& conf = partition_config()) {
-    auto cost_fun = [&](uint64_t u, uint64_t m) { return seq_bitsize<STRICT>(params, u, m) + conf.fix_cost; };
-    write_partition_table<STRICT>(bvb, seq, universe, n, optimal_partition(seq, universe, n, cost_fun, conf.eps1, conf.eps2),
+                              global_parameters const& params, Bodies& bodies, const std::vector<uint32_t>* given_ends = nullptr) {
+    write_partition_table<STRICT>(bvb, seq, universe, n, given_ends ? *given_ends : partition_ends<STRICT>(seq, universe, n, params),
                                   true, params, bodies);
 }
 
@@ -330,9 +303,9 @@ inline bool is_freq_layout(int kind) { return kind >= LAYOUT_OPT && kind <= LAYO
 // `bodies` holds the sequence (bodies.seq == seq) and receives its base sequences
 template <bool STRICT, class Bodies>
 inline void layout_write(int layout, bitvec_builder& bvb, const uint64_t* seq, uint64_t universe, uint64_t n,
-                         global_parameters const& params, Bodies& bodies) {
+                         global_parameters const& params, Bodies& bodies, const std::vector<uint32_t>* opt_ends = nullptr) {
     switch (layout) {
-    case LAYOUT_OPT: partitioned_write<STRICT>(bvb, seq, universe, n, params, bodies); break;
+    case LAYOUT_OPT: partitioned_write<STRICT>(bvb, seq, universe, n, params, bodies, opt_ends); break;
     case LAYOUT_UNIFORM: uniform_write<STRICT>(bvb, seq, universe, n, params, bodies); break;
     case LAYOUT_SINGLE:
         bodies.whole(universe, n);
@@ -362,11 +335,12 @@ public:
         encode_list(num_docs, params, n, docs, freqs, docs_bits, freqs_bits, layout, db, fb);
     }
     // ... with the base sequences handed to db (docs) / fb (freqs): docs_bits / freqs_bits receive the headers and what
-    // append_to puts behind them
+    // append_to puts behind them. docs_ends / freqs_ends: LAYOUT_OPT's partition end points when they are planned elsewhere
     template <class DocsBodies, class FreqsBodies>
     static void encode_list(uint64_t num_docs, global_parameters const& params, uint64_t n, const uint32_t* docs,
                             const uint32_t* freqs, bitvec_builder& docs_bits, bitvec_builder& freqs_bits, int layout,
-                            DocsBodies& db, FreqsBodies& fb) {
+                            DocsBodies& db, FreqsBodies& fb, const std::vector<uint32_t>* docs_ends = nullptr,
+                            const std::vector<uint32_t>* freqs_ends = nullptr) {
         if (!n) throw std::invalid_argument("List must be nonempty");
         uint64_t occurrences = 0;
         std::vector<uint64_t> d(n), cum(n);
@@ -379,8 +353,8 @@ public:
         fb.seq = cum.data();
         write_gamma_nonzero(docs_bits, occurrences);
         if (occurrences > 1) docs_bits.append_bits(n, (unsigned)ceil_log2(occurrences + 1));
-        layout_write<false>(layout, docs_bits, d.data(), num_docs, n, params, db);
-        layout_write<true>(layout, freqs_bits, cum.data(), occurrences + 1, n, params, fb);
+        layout_write<false>(layout, docs_bits, d.data(), num_docs, n, params, db, docs_ends);
+        layout_write<true>(layout, freqs_bits, cum.data(), occurrences + 1, n, params, fb, freqs_ends);
     }
     void add_posting_list(uint64_t n, const uint32_t* docs, const uint32_t* freqs) {
         bitvec_builder db, fb;

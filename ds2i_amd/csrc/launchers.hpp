@@ -67,4 +67,9 @@ hipError_t ds2i_launch_wand_list_max(const uint32_t* docs, const uint32_t* freqs
 hipError_t ds2i_launch_freq_prefix_sums(const ds2i_dev::EncArgs& st, uint64_t nlists, uint64_t* blk_base, uint64_t* cum, unsigned max_groups,
                                         hipStream_t s);
 hipError_t ds2i_launch_freq_write(int freqs_side, const ds2i_dev::FreqEncArgs& a, unsigned max_groups, hipStream_t s);
+// ---- partition_kernels.hip: the opt layout's partition end points (optimal_partition of host_pef.hpp) for a.nitems (list, side)
+// items, one wavefront each. plan: the DP and the walk back (a.count, the end points in the item's scratch); gather: the end points
+// to a.out_ends at a.out_offs
+hipError_t ds2i_launch_partition_plan(const ds2i_dev::PartArgs& a, hipStream_t s);
+hipError_t ds2i_launch_partition_gather(const ds2i_dev::PartArgs& a, hipStream_t s);
 }

@@ -81,6 +81,14 @@ enum ds2i_sequence_kind {
 int ds2i_write_sequence(int seq_kind, const uint64_t* values, uint64_t n, uint64_t universe, const uint8_t params[5],
                         ds2i_blob** bits, uint64_t* nbits);
 
+/* The partition end points the DS2I_OPT builder chooses (optimal_partition, the (1+eps)-approximate shortest path) for every
+ * list of a collection in CSR form (list t = docs / freqs [list_offsets[t], list_offsets[t+1]); doc-ids strictly increasing and
+ * < num_docs, freqs >= 1, lists nonempty, else DS2I_EINVAL). Per side -- docs: the doc-ids over num_docs; freqs: the strict prefix
+ * sums of the freqs over occurrences + 1 -- *_ends = the exclusive end index of every partition of every list back to back (u32),
+ * *_offs = nlists + 1 u64 offsets into it. List-parallel on at most 16 threads. The reference of ds2i_hip_opt_partition. */
+int ds2i_opt_partition(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                       ds2i_blob** docs_ends, ds2i_blob** docs_offs, ds2i_blob** freqs_ends, ds2i_blob** freqs_offs);
+
 /* The chunk directory ds2i_hip_index_open builds for one list of an opt image (inspection / test hook):
  * cmax = u32[nchunks] last doc-id per chunk, chunks = nchunks x 12 dwords (ds2i_amd/csrc/device_pef.hpp),
  * info = {n, docs_bit0, freqs_bit0, docs bit-vector byte offset in the image, freqs bit-vector byte offset} */

@@ -259,8 +259,8 @@ void ds2i_hip_pipeline_destroy(ds2i_hip_pipeline* p);
  * ds2i_builder_create(kind, num_docs) / ds2i_builder_add_posting_list x nlists / ds2i_builder_freeze return, byte for
  * byte, with the default global_parameters (sampling 9 / 8 / 9 / 8, log_partition_size 7). Every size of these layouts
  * is an integer in closed form of (universe, n), so the host plans -- type, length and final bit offset of every base
- * sequence, the headers, for DS2I_OPT the partition end points (optimal_partition, list-parallel on at most 16 host
- * threads) -- and HIP kernels form the prefix sums of the freqs and write every base sequence (Elias-Fano, ranked
+ * sequence, the headers -- and, for DS2I_OPT, takes the partition end points from the device planner
+ * (ds2i_hip_encode_index_with below chooses between it and optimal_partition on at most 16 host threads); HIP kernels form the prefix sums of the freqs and write every base sequence (Elias-Fano, ranked
  * bitvector, their sampled arrays) into the two bit vectors, one thread per posting. For these kinds the input is
  * checked on the host before anything is staged: an empty list ("List must be nonempty"), doc-ids not strictly
  * increasing or >= num_docs, and a zero freq are DS2I_EINVAL; no output is written on an error. */
@@ -268,8 +268,33 @@ typedef struct ds2i_blob ds2i_blob;
 int ds2i_hip_encode_index(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                           const uint32_t* docs, const uint32_t* freqs, ds2i_blob** image, double* device_ms);
 /* Diagnostic: the host seconds of this thread's last ds2i_hip_encode_index / ds2i_hip_build_collection of an Elias-Fano kind:
- * seconds[0] planning (DS2I_OPT: the partition DP), seconds[1] download, headers and freeze. */
+ * seconds[0] planning on the host (DS2I_OPT: the partition DP when the host plans it; headers and jobs either way),
+ * seconds[1] download, headers and freeze. */
 void ds2i_hip_encode_host_seconds(double seconds[2]);
+
+/* ds2i_hip_encode_index with a choice of who plans the partitions of DS2I_OPT (the (1+eps)-approximate shortest path of
+ * optimal_partition, per list and side): DS2I_ENCODE_PLAN_HOST -- list-parallel on at most 16 host threads;
+ * DS2I_ENCODE_PLAN_DEVICE -- HIP kernels, one wavefront per list and side over the staged postings (cost classes are lanes; the
+ * classes' budgets, the DP's only floating point, come from the host). flags == 0 takes the default, which is what
+ * ds2i_hip_encode_index, ds2i_hip_build_collection and ds2i_hip_convert_index take: the device planner. Both bits set is
+ * DS2I_EINVAL. The end points are the same either way, so the image is the same, byte for byte. Kinds without a DP ignore
+ * the two bits. Everything else is ds2i_hip_encode_index. */
+enum { DS2I_ENCODE_PLAN_HOST = 1u, DS2I_ENCODE_PLAN_DEVICE = 2u };
+int ds2i_hip_encode_index_with(int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                               const uint32_t* docs, const uint32_t* freqs, uint32_t flags, ds2i_blob** image, double* device_ms);
+/* Diagnostic: the hipEvent milliseconds of the partition kernels in this thread's last encode call (ds2i_hip_encode_index[_with],
+ * ds2i_hip_build_collection, ds2i_hip_convert_index); 0.0 when the host planned or the kind has no DP. */
+void ds2i_hip_encode_plan_ms(double* ms);
+/* The device planner alone: the partition end points DS2I_OPT takes for every list of a collection (CSR form and input checks of
+ * ds2i_hip_encode_index's Elias-Fano kinds, made before anything is staged). Per side -- docs: the doc-ids over num_docs; freqs:
+ * the strict prefix sums of the freqs over occurrences + 1 -- *_ends receives the exclusive end index of every partition of every
+ * list back to back (u32; a list's last one is its length) and *_offs nlists + 1 u64 offsets into it. The same four blobs as
+ * ds2i_opt_partition (ds2i_build.h), the host DP, element for element. scratch_bytes: the DP scratch (12 bytes per posting and
+ * side) one group of consecutive lists may take, 0 = the default (2 GiB); a group holds at least one list. device_ms (may be
+ * NULL): the hipEvent time of the kernels. No output is written on an error. */
+int ds2i_hip_opt_partition(int device, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs,
+                           const uint32_t* freqs, uint64_t scratch_bytes, ds2i_blob** docs_ends, ds2i_blob** docs_offs,
+                           ds2i_blob** freqs_ends, ds2i_blob** freqs_offs, double* device_ms);
 
 /* wand_data on the GPU (build side; create_wand_data.cpp:8-29, wand_data.hpp:20-52): the image ds2i_wand_create(doc_sizes,
  * num_docs) / ds2i_wand_add_list x nlists / ds2i_wand_freeze of ds2i_build.h return for the same input, byte for byte.
