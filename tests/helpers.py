@@ -196,6 +196,65 @@ def topk64(coll, terms, k, conjunctive):
     return s[:k], len(s)
 
 
+def check_pruning_tables(gidx, coll, terms, codec, G=4, hints=True, bitmaps=True, where=""):
+    """The upload-time tables of the lists `terms` of the device index gidx (an upload of `coll` as `codec`) against numpy on the raw
+    lists: bmw[b] is exactly the largest doc_term_weight of block b; every byte of the level-1 doc-id-range table is 0 iff its range
+    holds no posting, else an upper bound (<= 1/255 of the list maximum above) of the largest weight in the range -- its last entry, the
+    partial range, included; the list has G entries per posting at least (or one per doc-id); levels 2 and 3 are maxima of 64 entries of
+    the level below; a list holding one document in 64 or more carries its exact bitmap (every byte of it, the last, partial one too);
+    the hints are 0 for an empty range, 255 for several postings, else 1 + offset % 254. G / hints / bitmaps: what the upload was asked
+    for (DS2I_RMW_G, DS2I_NO_RMH, DS2I_NO_BITMAPS)."""
+    for t in terms:
+        docs, freqs = coll.lists[t]
+        w = doc_term_weight(freqs, coll.norm_lens[docs])
+        bw = gidx.block_weights(t)
+        if codec in d.BLOCK_CODECS:
+            nb = (len(docs) + 127) // 128
+            assert len(bw) == nb
+            exp = np.array([w[b * 128:(b + 1) * 128].max() for b in range(nb)], dtype=np.float32)
+            assert np.array_equal(bw, exp), (where, codec, t)
+        else:  # chunks of <= 128 postings cut at partition boundaries: the maxima of consecutive runs, in order
+            assert len(bw) >= (len(docs) + 127) // 128 and np.float32(bw.max()) == np.float32(w.max()), (where, codec, t)
+        tab, sh, mx = gidx.range_table(t)
+        assert len(tab) == (coll.num_docs >> sh) + 1 and np.float32(mx) == np.float32(w.max()), (where, codec, t)
+        rmax = np.zeros(len(tab), dtype=np.float32)
+        np.maximum.at(rmax, docs >> sh, w)
+        occupied = np.zeros(len(tab), dtype=bool)
+        occupied[docs >> sh] = True
+        assert np.array_equal(tab != 0, occupied), (where, codec, t, np.flatnonzero((tab != 0) != occupied)[:4].tolist())
+        bound = tab.astype(np.float32) * np.float32(mx / 255.0)
+        assert np.all(bound[occupied] * np.float32(1 + 2 ** -17) >= rmax[occupied]), (where, codec, t)
+        assert np.all(bound[occupied] <= rmax[occupied] + np.float32(mx) * np.float32(1.01 / 255.0)), (where, codec, t)
+        assert G * len(docs) <= len(tab) or sh == 0, (where, codec, t)  # DS2I_RMW_G entries per posting at least (or one per doc-id)
+        bm, _, _ = gidx.range_table(t, 0)  # dense lists (>= one document in 64) carry their exact bitmap
+        if bitmaps and 64 * len(docs) >= coll.num_docs:
+            assert len(bm) == (coll.num_docs + 7) // 8, (where, codec, t)
+            bits = np.unpackbits(bm, bitorder="little")
+            assert not bits[coll.num_docs:].any(), (where, codec, t)  # (the last byte's spare bits)
+            assert np.array_equal(np.flatnonzero(bits[:coll.num_docs]).astype(np.uint32), docs), (where, codec, t)
+        else:
+            assert len(bm) == 0
+        prev = tab
+        for level in (2, 3):  # the coarser levels: maxima of 64 entries of the level below
+            up, shl, _ = gidx.range_table(t, level)
+            assert shl == sh + 6 * (level - 1) and len(up) == (len(prev) + 63) // 64
+            padded = np.zeros(len(up) * 64, dtype=np.uint8)
+            padded[:len(prev)] = prev
+            assert np.array_equal(up, padded.reshape(-1, 64).max(axis=1)), (where, codec, t, level)
+            prev = up
+        hint, hsh, _ = gidx.range_table(t, 4)  # membership hints: 0 empty, 255 several postings, else 1 + offset % 254
+        if hints:  # (every index kind carries them since the ranked / and / wand kernels of all kinds consult them)
+            assert hsh == sh and len(hint) == len(tab)
+            cnt = np.bincount(docs >> sh, minlength=len(tab))
+            exp = np.zeros(len(tab), dtype=np.uint8)
+            exp[cnt > 1] = 255
+            single = cnt[docs >> sh] == 1
+            exp[(docs >> sh)[single]] = (1 + (docs[single] & ((1 << sh) - 1)) % 254).astype(np.uint8)
+            assert np.array_equal(hint, exp), (where, codec, t, np.flatnonzero(hint != exp)[:4].tolist())
+        else:
+            assert len(hint) == 0
+
+
 # ---------------------------------------------------------------- a crafted collection whose result-set sizes are known exactly
 BOUNDARY_SIZES = (1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1023, 1024, 1025, 3000)
 

@@ -9,7 +9,7 @@ import pytest
 
 import ds2i_amd as d
 import oracle as o
-from helpers import Collection, brute_and, brute_ranked, mixed_block_type_counts, queries_for, small_params
+from helpers import Collection, brute_and, brute_ranked, check_pruning_tables, mixed_block_type_counts, queries_for, small_params
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-5
@@ -336,53 +336,8 @@ def test_pruning_tables_are_exact_maxima(coll, images, codec):
     exactly the largest bm25::doc_term_weight of block b (bit for bit: it is computed with the scoring arithmetic), and
     every byte of the doc-id-range table is 0 iff its range holds no posting of the list, else an upper bound (<= 1/255
     of the list maximum above) of the largest weight in the range."""
-    from helpers import doc_term_weight
     gidx = d.Index(codec, images[0][codec], images[1])
-    for t in list(range(0, 40)) + list(range(40, len(coll.lists), 7)):
-        docs, freqs = coll.lists[t]
-        w = doc_term_weight(freqs, coll.norm_lens[docs])
-        bw = gidx.block_weights(t)
-        if codec in d.BLOCK_CODECS:
-            nb = (len(docs) + 127) // 128
-            assert len(bw) == nb
-            exp = np.array([w[b * 128:(b + 1) * 128].max() for b in range(nb)], dtype=np.float32)
-            assert np.array_equal(bw, exp), (codec, t)
-        else:  # chunks of <= 128 postings cut at partition boundaries: the maxima of consecutive runs, in order
-            assert len(bw) >= (len(docs) + 127) // 128 and np.float32(bw.max()) == np.float32(w.max()), (codec, t)
-        tab, sh, mx = gidx.range_table(t)
-        assert len(tab) == (coll.num_docs >> sh) + 1 and np.float32(mx) == np.float32(w.max())
-        rmax = np.zeros(len(tab), dtype=np.float32)
-        np.maximum.at(rmax, docs >> sh, w)
-        occupied = np.zeros(len(tab), dtype=bool)
-        occupied[docs >> sh] = True
-        assert np.array_equal(tab != 0, occupied), (codec, t)
-        bound = tab.astype(np.float32) * np.float32(mx / 255.0)
-        assert np.all(bound[occupied] * np.float32(1 + 2 ** -17) >= rmax[occupied]), (codec, t)
-        assert np.all(bound[occupied] <= rmax[occupied] + np.float32(mx) * np.float32(1.01 / 255.0)), (codec, t)
-        assert 4 * len(docs) <= len(tab) or sh == 0   # DS2I_RMW_G = 4 entries per posting at least (or one per doc-id)
-        bm, _, _ = gidx.range_table(t, 0)  # dense lists (>= one document in 64) carry their exact bitmap
-        if 64 * len(docs) >= coll.num_docs:
-            bits = np.unpackbits(bm, bitorder="little")[:coll.num_docs]
-            assert np.array_equal(np.flatnonzero(bits).astype(np.uint32), docs), (codec, t)
-        else:
-            assert len(bm) == 0
-        prev = tab
-        for level in (2, 3):  # the coarser levels: maxima of 64 entries of the level below
-            up, shl, _ = gidx.range_table(t, level)
-            assert shl == sh + 6 * (level - 1) and len(up) == (len(prev) + 63) // 64
-            padded = np.zeros(len(up) * 64, dtype=np.uint8)
-            padded[:len(prev)] = prev
-            assert np.array_equal(up, padded.reshape(-1, 64).max(axis=1)), (codec, t, level)
-            prev = up
-        hints, hsh, _ = gidx.range_table(t, 4)  # membership hints (block_optpfor): 0 empty, 255 several postings, else 1 + offset % 254
-        if True:  # (every index kind carries them since the ranked / and / wand kernels of all kinds consult them)
-            assert hsh == sh and len(hints) == len(tab)
-            cnt = np.bincount(docs >> sh, minlength=len(tab))
-            exp = np.zeros(len(tab), dtype=np.uint8)
-            exp[cnt > 1] = 255
-            single = cnt[docs >> sh] == 1
-            exp[(docs >> sh)[single]] = (1 + (docs[single] & ((1 << sh) - 1)) % 254).astype(np.uint8)
-            assert np.array_equal(hints, exp), (codec, t)
+    check_pruning_tables(gidx, coll, list(range(0, 40)) + list(range(40, len(coll.lists), 7)), codec)
 
 
 def test_block_mixed_image_holds_all_three_block_types(images):
