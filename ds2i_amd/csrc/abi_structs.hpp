@@ -142,6 +142,20 @@ struct BatchArgs {
     uint32_t* unit_topk_docs;
 };
 
+// What a decode of an index's lists reads, whichever kernel does it (the host fills it in one place: capi_internal.hpp,
+// ds2i_index_view; the device makes the decoders' BatchArgs of it in one place: kernels_upload.inc, view_batch_args)
+struct IndexView {
+    const uint8_t* arena;    // as BatchArgs
+    const uint8_t* bits0;
+    const uint8_t* bits1;
+    int codec;
+    uint32_t num_docs;
+    const void* skip;        // the side-slot decode (side_decode_block): the interleaved skip table, the slots, their overflow area, the tail table
+    const uint32_t* xslots;
+    const uint32_t* xovf;
+    const uint32_t* tails;
+};
+
 // upload-time pass computing bmw[] (k_block_max_weights): one wave per item = <=64 consecutive blocks of one list
 struct BmwItem {
     uint32_t list, blk_begin;
@@ -172,15 +186,11 @@ struct RmwLevels {
     static __host__ __device__ bool bitmap_first(uint32_t n, uint32_t num_docs, uint32_t shift) { return has_bitmap(n, num_docs) && shift <= 3u; }
 };
 struct BmwArgs {
-    const uint8_t* arena;
-    const uint8_t* bits0;
-    const uint8_t* bits1;
+    IndexView v;
     const float* norm_lens;
     const QTerm* lists; // one per list of the index
     const BmwItem* items;
     uint32_t nitems;
-    int codec;
-    uint32_t num_docs;
     float* bmw;             // out: one per block
     unsigned int* list_bmw; // out: per list max (float bits; weights are >= 0 so the bit patterns order like the values)
     uint8_t* rmw;           // second pass (k_range_max_weights): the range tables; lists[].max_weight = the list maximum of pass 1
@@ -270,67 +280,44 @@ struct MergeArgs {
 };
 
 struct DecodeArgs {
-    const uint8_t* arena;
-    const uint8_t* bits0;
-    const uint8_t* bits1;
+    IndexView v;
     QTerm term;
-    int codec;
-    uint32_t num_docs;
     uint32_t* out_docs;
     uint32_t* out_freqs;
-    Stats* stats;
-    const void* skip;        // side-slot decode (k_decode_list_side): the interleaved skip table, the slots, their overflow area, the tail table
-    const uint32_t* xslots;
-    const uint32_t* xovf;
-    const uint32_t* tails;
 };
 
-// Whole-index decode-and-compare (k_verify_index / k_verify_index_side): every block (chunk) of every list of the index against a
-// collection staged in CSR form. Block g of the index belongs to the list l with lists[l].blk_base <= g < lists[l].blk_base +
-// lists[l].nblocks; its posting i is compared with exp_docs / exp_freqs [list_first[l] + (position of the block in its list) + i].
+// The whole-index walk (walk_index / walk_index_side, kernels_upload.inc): every block (chunk) of the index-wide block numbers
+// [block_begin, block_end) -- the blocks of `nlists` consecutive lists, `lists` holding those lists only (their blk_base stay
+// index-wide). Block g belongs to the list l with lists[l].blk_base <= g < lists[l].blk_base + lists[l].nblocks; its posting i has
+// the place list_first[l] + (position of the block in its list) + i in a collection in CSR form. list_first starts at 0 for the
+// first list of the range. The host stages all of it once for every kernel that walks (capi_util.hpp, WalkStaging).
+struct WalkArgs {
+    IndexView v;
+    const QTerm* lists;         // one per list of the range (ds2i_make_qterm)
+    uint32_t nlists;
+    uint32_t block_begin, block_end;
+    const uint64_t* list_first; // nlists + 1 posting offsets
+};
+
+// Whole-index decode-and-compare (k_verify_index / k_verify_index_side): the walk over every list of the index against a collection
+// staged in CSR form: a posting is compared with exp_docs / exp_freqs at its place.
 // The host has compared the list lengths before the launch: list_first[l + 1] - list_first[l] == lists[l].n for every list.
 // first_bad receives (atomicMin; preset to VERIFY_NONE) the smallest key (global posting index << 1) | (1: the doc-id matched and
 // the freq differs) over all differences -- the first one in (list, position) order, doc-id before freq, whatever the scheduling.
 static constexpr unsigned long long VERIFY_NONE = ~0ull;
 struct VerifyArgs {
-    const uint8_t* arena;
-    const uint8_t* bits0;
-    const uint8_t* bits1;
-    const QTerm* lists;        // one per list of the index (ds2i_make_qterm)
-    uint32_t nlists;
-    uint32_t total_blocks;
-    int codec;
-    uint32_t num_docs;
+    WalkArgs w;
     const uint32_t* exp_docs;
     const uint32_t* exp_freqs;
-    const uint64_t* list_first; // nlists + 1 posting offsets of the collection
     unsigned long long* first_bad;
-    const void* skip;          // k_verify_index_side: as DecodeArgs
-    const uint32_t* xslots;
-    const uint32_t* xovf;
-    const uint32_t* tails;
 };
 
-// Whole-index decode-and-store (k_extract_index / k_extract_index_side): the walk of the verification over the index-wide block
-// numbers [block_begin, block_end) -- the blocks of `nlists` consecutive lists, `lists` holding those lists only (their blk_base
-// stay index-wide). Posting i of a block of list l goes to out_docs / out_freqs [list_first[l] + (position of the block in its
-// list) + i]; list_first starts at 0 for the first list of the range, and the two buffers hold exactly list_first[nlists] postings.
+// Whole-index decode-and-store (k_extract_index / k_extract_index_side): the walk over a range of lists; a posting goes to out_docs /
+// out_freqs at its place, and the two buffers hold exactly list_first[nlists] postings.
 struct ExtractArgs {
-    const uint8_t* arena;
-    const uint8_t* bits0;
-    const uint8_t* bits1;
-    const QTerm* lists;         // one per list of the range (ds2i_make_qterm)
-    uint32_t nlists;
-    uint32_t block_begin, block_end;
-    int codec;
-    uint32_t num_docs;
+    WalkArgs w;
     uint32_t* out_docs;
     uint32_t* out_freqs;
-    const uint64_t* list_first; // nlists + 1 posting offsets of the output
-    const void* skip;           // k_extract_index_side: as DecodeArgs
-    const uint32_t* xslots;
-    const uint32_t* xovf;
-    const uint32_t* tails;
 };
 
 // wand / maxscore / ranked_or of a ONE-term query are exactly its ranked_and result: copied from the seed pass (k_copy_seed)

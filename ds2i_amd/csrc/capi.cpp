@@ -98,15 +98,11 @@ int build_block_max_weights(ds2i_hip_index* x) {
     HIP_OK(hipMemcpy(d_items, items.data(), sizeof(ds2i_dev::BmwItem) * items.size(), hipMemcpyHostToDevice));
     HIP_OK(hipMemset(d_lmax, 0, 4 * V));
     ds2i_dev::BmwArgs a{};
-    a.arena = x->d_arena;
-    a.bits0 = x->d_bits0;
-    a.bits1 = x->d_bits1;
+    a.v = ds2i_index_view(x);
     a.norm_lens = x->d_norm_lens;
     a.lists = d_lists;
     a.items = d_items;
     a.nitems = (uint32_t)items.size();
-    a.codec = x->kind >= DS2I_OPT ? (int)DS2I_OPT : x->kind;
-    a.num_docs = (uint32_t)x->num_docs;
     a.bmw = x->d_bmw;
     a.list_bmw = d_lmax;
     a.rmw = nullptr;
@@ -450,6 +446,14 @@ int ds2i_hip_device_count(void) {
 static int index_open_impl(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, bool bare,
                            const Ds2iKnobs& kn, ds2i_hip_index** out, size_t budget_base_bytes = 0);
 
+// Every way in passes here first (index_open_impl, and index_open_transcoded before it reads the image): the arguments are checked
+// here and nowhere else.
+static int open_check_args(int device, int kind, const void* index_image, ds2i_hip_index** out) {
+    if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
+    if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
+    return check_device("ds2i_hip_index_open", device);
+}
+
 // block_mixed, the default upload: the image is TRANSCODED to the block codec this device decodes fastest. The mixed
 // image is uploaded bare (no tables), every list decoded by the mixed-block kernels (mixed_block.hpp:198-217: OptPFor /
 // VarInt-G8IU / interpolative by type byte), the postings re-encoded by the GPU index encoder as block_optpfor
@@ -460,84 +464,39 @@ static int index_open_impl(int device, int kind, const void* index_image, size_t
 // mixed-codec kernels (k_ranked_stream_mixed, the CODEC_MIXED instantiations).
 // The freq_index layouts (opt / ef / single / uniform) take the same way: partitioned Elias-Fano is the space-optimal form for
 // disk and for a CPU's caches; on a device with 288 GB behind 8 TB/s the form to query is the one whose block is one wave's
-// worth of work with its skip entry, block weight, range-table bytes and side slot beside it. Their chunk directory is built
-// (it is what the decode pass walks), every list decoded by the partitioned-sequence kernels (partitioned_sequence.hpp:198-326,
-// compact_elias_fano.hpp:184-214, compact_ranked_bitvector.hpp, positive / strict sequences), and the postings re-encoded as
-// above. DS2I_PEF_NATIVE=1 keeps the bit vectors and runs the CODEC_PEF kernels over the chunk directory.
+// worth of work with its skip entry, block weight, range-table bytes and side slot beside it. DS2I_PEF_NATIVE=1 keeps the bit
+// vectors and runs the CODEC_PEF kernels over the chunk directory.
+// How: the transcoding IS the conversion of ds2i_hip_convert_index (capi_extract.cpp, ds2i_convert_image) -- the image uploaded bare
+// (a freq_index with the chunk directory the decoders walk), every list decoded by ONE launch of the extraction kernel (the
+// mixed-block decoders, mixed_block.hpp:198-217; the partitioned-sequence decoders, partitioned_sequence.hpp:198-326,
+// compact_elias_fano.hpp:184-214, compact_ranked_bitvector.hpp, positive / strict sequences) into two device buffers, the bare
+// image closed, the postings re-encoded where they lie. They never visit the host.
 static int index_open_transcoded(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes,
                                  const Ds2iKnobs& kn, ds2i_hip_index** out) {
-    ds2i_hip_index* raw = nullptr;
-    int rc = index_open_impl(device, kind, index_image, index_bytes, nullptr, 0, true, kn, &raw);
+    int rc = open_check_args(device, kind, index_image, out);
     if (rc) return rc;
-    std::unique_ptr<ds2i_hip_index, void (*)(ds2i_hip_index*)> guard(raw, free_index);
-    const uint64_t V = raw->size;
-    std::vector<uint64_t> offs(V + 1, 0);
-    uint32_t longest = 1;
-    for (uint64_t t = 0; t < V; ++t) {
-        offs[t + 1] = offs[t] + raw->list_n[t];
-        longest = std::max(longest, raw->list_n[t]);
-    }
     // Transcoding is a choice, not an obligation: what a transcoded index needs at the very least -- ~2 bytes per posting of
     // block_optpfor image, a side slot per block, its skip table and block weights -- is several times a partitioned Elias-Fano image.
-    // Under a DS2I_TABLE_BUDGET it does not fit, or when the host cannot hold the decoded postings (8 bytes each), the image is
-    // uploaded AS IT IS and queried by its own kernels (DS2I_PEF_NATIVE / DS2I_MIXED_NATIVE behaviour), with the tables the budget allows.
+    // Under a DS2I_TABLE_BUDGET it does not fit (known from the image's header and list lengths, before anything is uploaded), or when
+    // the device cannot hold the decoded postings beside the image (8 bytes each), the image is uploaded AS IT IS and queried by its own
+    // kernels (DS2I_PEF_NATIVE / DS2I_MIXED_NATIVE behaviour), with the tables the budget allows.
     auto native = [&](const char* why) {
         std::fprintf(stderr, "ds2i_hip: %s: the %s image is uploaded as it is (native kernels)\n", why, kind == DS2I_BLOCK_MIXED ? "block_mixed" : "freq_index");
-        guard.reset();
         return index_open_impl(device, kind, index_image, index_bytes, wand_image, wand_bytes, false, kn, out);
     };
-    const uint64_t budget = table_budget_bytes(kn, index_bytes);
-    const uint64_t least = 2 * offs[V] + (4ull * ds2i_dev::XSLOT_DW + 8 + 4) * ((offs[V] + 127) / 128) + 4 * raw->num_docs;
-    if (budget && least > budget) return native("DS2I_TABLE_BUDGET is below what a transcoded index needs");
-    std::vector<uint32_t> docs, freqs;
-    try {
-        docs.resize(offs[V]);
-        freqs.resize(offs[V]);
-    } catch (std::bad_alloc const&) {
-        std::vector<uint32_t>().swap(docs);
-        return native("not enough host memory to hold the decoded postings");
+    if (const uint64_t budget = table_budget_bytes(kn, index_bytes)) {
+        uint64_t num_docs = 0, nlists = 0, total = 0;
+        std::vector<uint32_t> len;
+        if ((rc = ds2i_parse_image(kind, index_image, index_bytes, num_docs, nlists, &len))) return rc;
+        for (uint32_t n : len) total += n;
+        const uint64_t least = 2 * total + (4ull * ds2i_dev::XSLOT_DW + 8 + 4) * ((total + 127) / 128) + 4 * num_docs;
+        if (least > budget) return native("DS2I_TABLE_BUDGET is below what a transcoded index needs");
     }
-    {
-        // lists are decoded a CHUNK at a time: every list of the chunk by a launch of its own into its place in two device buffers
-        // (no host synchronisation in between), then one copy per buffer -- not a launch, two copies and a synchronisation per list
-        // (a collection has millions of lists, most of them a few postings long)
-        DevTemps tmp;
-        uint32_t *d_docs = nullptr, *d_freqs = nullptr;
-        const uint64_t chunk_cap = std::max<uint64_t>((uint64_t)longest + 128, 64ull << 20); // postings per chunk (256 MB per buffer)
-        if (tmp.alloc(&d_docs, 4 * (size_t)chunk_cap) != hipSuccess || tmp.alloc(&d_freqs, 4 * (size_t)chunk_cap) != hipSuccess) {
-            (void)hipGetLastError();
-            return native("not enough device memory for the decode buffers");
-        }
-        for (uint64_t t0 = 0; t0 < V;) {
-            uint64_t t1 = t0, fill = 0;
-            while (t1 < V && fill + raw->list_n[t1] + 128 <= chunk_cap) { // (+128: the decode kernels write whole blocks)
-                DecodeArgs a{};
-                a.arena = raw->d_arena;
-                a.bits0 = raw->d_bits0;
-                a.bits1 = raw->d_bits1;
-                a.skip = raw->d_skip;
-                a.term = ds2i_make_qterm(raw, (uint32_t)t1);
-                a.codec = kind >= DS2I_OPT ? (int)DS2I_OPT : kind; // (every freq_index layout decodes through the chunk directory)
-                a.num_docs = (uint32_t)raw->num_docs;
-                a.out_docs = d_docs + fill;
-                a.out_freqs = d_freqs + fill;
-                HIP_OK(ds2i_launch_decode_list(a, (unsigned)std::min<uint64_t>(raw->list_nb[t1], uint64_t(raw->num_cus) * 16), raw->stream[0]));
-                fill += raw->list_n[t1];
-                ++t1;
-            }
-            HIP_OK(hipMemcpyAsync(docs.data() + offs[t0], d_docs, 4 * (size_t)fill, hipMemcpyDeviceToHost, raw->stream[0]));
-            HIP_OK(hipMemcpyAsync(freqs.data() + offs[t0], d_freqs, 4 * (size_t)fill, hipMemcpyDeviceToHost, raw->stream[0]));
-            HIP_OK(hipStreamSynchronize(raw->stream[0])); // (the two device buffers are reused by the next chunk)
-            t0 = t1;
-        }
-    }
-    const uint64_t num_docs = raw->num_docs;
-    guard.reset(); // the mixed image leaves the device before the transcoded one arrives
     ds2i_blob* img = nullptr;
-    rc = ds2i_hip_encode_index(device, DS2I_BLOCK_OPTPFOR, num_docs, V, offs.data(), docs.data(), freqs.data(), &img, nullptr);
+    bool no_room = false;
+    rc = ds2i_convert_image("ds2i_hip_index_open", device, kind, index_image, index_bytes, DS2I_BLOCK_OPTPFOR, &img, nullptr, &no_room);
+    if (no_room) return native("not enough device memory to hold the decoded postings beside the image"); // (every device buffer of the attempt is released by now)
     if (rc) return rc;
-    std::vector<uint32_t>().swap(docs);
-    std::vector<uint32_t>().swap(freqs);
     rc = index_open_impl(device, DS2I_BLOCK_OPTPFOR, ds2i_blob_data(img), ds2i_blob_size(img), wand_image, wand_bytes, false, kn, out, index_bytes);
     ds2i_blob_free(img);
     if (rc == DS2I_OK) (*out)->kind_on_disk = kind;
@@ -546,7 +505,7 @@ static int index_open_transcoded(int device, int kind, const void* index_image, 
 
 int ds2i_hip_index_open(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image,
                         size_t wand_bytes, ds2i_hip_index** out) {
-    // (the arguments are checked by index_open_impl, which every way in passes first)
+    // (the arguments are checked by open_check_args, which every way in passes first)
     const Ds2iKnobs kn = ds2i_knobs(); // (every upload reads the knobs once: the index that serves the queries carries them)
     const bool transcode = (kind == DS2I_BLOCK_MIXED && !kn.mixed_native) || (kind >= DS2I_OPT && kind <= DS2I_UNIFORM && !kn.pef_native);
     if (transcode) {
@@ -795,13 +754,10 @@ static int open_build_tables(ds2i_hip_index* x, bool bare, size_t budget_base_by
     return DS2I_OK;
 }
 
-// Every way in passes here first (ds2i_hip_index_open directly or through index_open_transcoded, ds2i_index_open_bare): the arguments
-// are checked here and nowhere else.
+// The upload itself (ds2i_hip_index_open directly or through index_open_transcoded, ds2i_index_open_bare)
 static int index_open_impl(int device, int kind, const void* index_image, size_t index_bytes, const void* wand_image, size_t wand_bytes, bool bare,
                            const Ds2iKnobs& kn, ds2i_hip_index** out, size_t budget_base_bytes) {
-    if (!out || !index_image) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: null argument");
-    if (kind < DS2I_BLOCK_OPTPFOR || kind > DS2I_UNIFORM) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_open: unknown index kind");
-    int rc = check_device("ds2i_hip_index_open", device);
+    int rc = open_check_args(device, kind, index_image, out);
     if (rc) return rc;
     std::unique_ptr<ds2i_hip_index, void (*)(ds2i_hip_index*)> x(new ds2i_hip_index, free_index);
     x->device = device;
@@ -862,28 +818,16 @@ int ds2i_hip_decode_list(ds2i_hip_index* idx, uint32_t term, uint32_t* docs, uin
     *n = len;
     if (capacity < len) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_decode_list: capacity too small");
     HIP_OK(hipSetDevice(idx->device));
-    const uint64_t nb = idx->list_nb[term];
     uint32_t *d_docs = nullptr, *d_freqs = nullptr;
     HIP_OK(hipMalloc((void**)&d_docs, 4 * (len + 128)));
     HIP_OK(hipMalloc((void**)&d_freqs, 4 * (len + 128)));
     DecodeArgs a{};
-    a.arena = idx->d_arena;
-    a.bits0 = idx->d_bits0;
-    a.bits1 = idx->d_bits1;
+    a.v = ds2i_index_view(idx);
     a.term = ds2i_make_qterm(idx, term);
-    a.codec = idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; // every freq_index layout decodes through the chunk directory
-    a.num_docs = (uint32_t)idx->num_docs;
     a.out_docs = d_docs;
     a.out_freqs = d_freqs;
-    a.stats = nullptr;
-    a.skip = idx->d_skip;
-    a.xslots = idx->d_xslots;
-    a.xovf = idx->d_xovf;
-    a.tails = idx->d_tails;
-    unsigned grid = (unsigned)std::min<uint64_t>(nb, uint64_t(idx->num_cus) * 16);
-    // block_optpfor with side tables: through the stream kernels' decoder (DS2I_DECODE_GENERAL=1: the general decoders)
-    const bool side = idx->side_tables() && !idx->knobs.decode_general;
-    hipError_t e = side ? ds2i_launch_decode_list_side(a, grid, idx->stream[0]) : ds2i_launch_decode_list(a, grid, idx->stream[0]);
+    const unsigned grid = ds2i_walk_grid(idx, idx->list_nb[term]);
+    hipError_t e = (idx->decode_through_side_tables() ? ds2i_launch_decode_list_side : ds2i_launch_decode_list)(a, grid, idx->stream[0]);
     if (e == hipSuccess) e = hipStreamSynchronize(idx->stream[0]);
     if (e == hipSuccess) e = hipMemcpy(docs, d_docs, 4 * len, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(freqs, d_freqs, 4 * len, hipMemcpyDeviceToHost);

@@ -1141,7 +1141,7 @@ BatchArgs batch_args(const ds2i_hip_batch* b, bool seed_feeds) {
     a.units = b->d_up.at<Unit>(b->o_units);
     a.num_docs = (uint32_t)idx->num_docs;
     a.k = b->k;
-    a.codec = idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; // every freq_index layout decodes through the chunk directory
+    a.codec = ds2i_decode_codec(idx);
     a.unit_clock = (idx->knobs.unit_clock && b->instrument) ? (unsigned long long*)b->d_clk.p : nullptr;
     a.out_count = b->d_out.at<unsigned long long>(b->o_count);
     a.out_topk = b->d_out.at<float>(b->o_topk);

@@ -120,6 +120,9 @@ struct ds2i_hip_index {
     // block_optpfor with its exception side slots, tail table and skip table: what the stream kernels decode a block through
     // (build_side_tables allocates and frees d_xslots and d_tails together, and builds them only over a skip table)
     bool side_tables() const { return kind == DS2I_BLOCK_OPTPFOR && d_xslots && d_tails && d_skip; }
+    // the list decode, the verification and the extraction go through them where they exist -- the stream kernels' decoder
+    // (DS2I_DECODE_GENERAL=1: the general decoders of the on-disk bytes although side tables exist)
+    bool decode_through_side_tables() const { return side_tables() && !knobs.decode_general; }
     // block-max weights and doc-id-range tables: what the pruned kernels bound a block and a doc-id range by
     bool bound_tables() const { return d_bmw && d_rmw; }
     bool has_bitmaps = false;       // dense lists carry an exact bitmap behind their range-table levels
@@ -185,4 +188,28 @@ static inline ds2i_dev::QTerm ds2i_make_qterm(const ds2i_hip_index* idx, uint32_
     qt.rmw_scale = 0.f;
     qt.nblocks = idx->list_nb[term];
     return qt;
+}
+
+// The codec the kernels decode an index by: every freq_index layout decodes through the chunk directory
+static inline int ds2i_decode_codec(const ds2i_hip_index* idx) { return idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; }
+
+// What a decode of the index's lists reads (abi_structs.hpp, IndexView): the image as uploaded and, where the upload built them, the
+// side tables. Filled here for every kernel that decodes lists outside a query batch.
+static inline ds2i_dev::IndexView ds2i_index_view(const ds2i_hip_index* idx) {
+    ds2i_dev::IndexView v{};
+    v.arena = idx->d_arena;
+    v.bits0 = idx->d_bits0;
+    v.bits1 = idx->d_bits1;
+    v.codec = ds2i_decode_codec(idx);
+    v.num_docs = (uint32_t)idx->num_docs;
+    v.skip = idx->d_skip;
+    v.xslots = idx->d_xslots;
+    v.xovf = idx->d_xovf;
+    v.tails = idx->d_tails;
+    return v;
+}
+
+// The grid of a kernel that takes one wave per block and strides: a wave per block up to 16 per compute unit
+static inline unsigned ds2i_walk_grid(const ds2i_hip_index* idx, uint64_t blocks) {
+    return (unsigned)(blocks < uint64_t(idx->num_cus) * 16 ? blocks : uint64_t(idx->num_cus) * 16);
 }

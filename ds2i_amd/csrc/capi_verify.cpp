@@ -11,11 +11,7 @@
 #include <vector>
 
 #include "capi_util.hpp"
-#include "host_index.hpp"
-#include "host_pef.hpp"
 #include "launchers.hpp"
-
-using ds2i_dev::QTerm;
 
 namespace {
 
@@ -66,53 +62,25 @@ int verify_postings(ds2i_hip_index* idx, const uint64_t* offs, const uint32_t* d
     const uint64_t V = idx->size, total = offs[V];
     r->postings_checked = total;
     if (!V || !total || !idx->total_blocks) return DS2I_OK;
-    if (idx->total_blocks >= (1ull << 32)) return ds2i_set_error(DS2I_EINVAL, "index verification: more than 2^32 blocks");
     const auto t0 = std::chrono::steady_clock::now();
-    HIP_OK(hipSetDevice(idx->device));
-    std::vector<QTerm> lists;
-    DS2I_TRY
-    lists.resize(V);
-    DS2I_CATCH
-    for (uint64_t t = 0; t < V; ++t) lists[t] = ds2i_make_qterm(idx, (uint32_t)t);
-    DevTemps dev;
-    QTerm* d_lists = nullptr;
+    WalkStaging st("index verification", "the collection does not fit");
+    int rc = st.stage(idx, 0, V, offs);
+    if (rc != DS2I_OK) return rc;
     uint32_t *d_docs = nullptr, *d_freqs = nullptr;
-    uint64_t* d_first = nullptr;
     unsigned long long* d_bad = nullptr;
-    if (dev.alloc(&d_lists, sizeof(QTerm) * V) != hipSuccess || dev.alloc(&d_docs, 4 * total) != hipSuccess ||
-        dev.alloc(&d_freqs, 4 * total) != hipSuccess || dev.alloc(&d_first, 8 * (V + 1)) != hipSuccess || dev.alloc(&d_bad, 8) != hipSuccess) {
-        (void)hipGetLastError();
-        return ds2i_set_error(DS2I_ENOMEM, "index verification: the collection does not fit beside the index (8 bytes per posting)");
-    }
+    if (st.dev.alloc(&d_docs, 4 * total) != hipSuccess || st.dev.alloc(&d_freqs, 4 * total) != hipSuccess || st.dev.alloc(&d_bad, 8) != hipSuccess) return st.nomem();
     unsigned long long key = ds2i_dev::VERIFY_NONE;
-    HIP_OK(hipMemcpy(d_lists, lists.data(), sizeof(QTerm) * V, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_docs, docs, 4 * total, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_freqs, freqs, 4 * total, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_first, offs, 8 * (V + 1), hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_bad, &key, 8, hipMemcpyHostToDevice));
     verify_host_s[2] = seconds_since(t0);
     ds2i_dev::VerifyArgs a{};
-    a.arena = idx->d_arena;
-    a.bits0 = idx->d_bits0;
-    a.bits1 = idx->d_bits1;
-    a.lists = d_lists;
-    a.nlists = (uint32_t)V;
-    a.total_blocks = (uint32_t)idx->total_blocks;
-    a.codec = idx->kind >= DS2I_OPT ? (int)DS2I_OPT : idx->kind; // every freq_index layout decodes through the chunk directory
-    a.num_docs = (uint32_t)idx->num_docs;
     a.exp_docs = d_docs;
     a.exp_freqs = d_freqs;
-    a.list_first = d_first;
     a.first_bad = d_bad;
-    a.skip = idx->d_skip;
-    a.xslots = idx->d_xslots;
-    a.xovf = idx->d_xovf;
-    a.tails = idx->d_tails;
-    const unsigned grid = (unsigned)std::min<uint64_t>(idx->total_blocks, uint64_t(idx->num_cus) * 16);
-    // block_optpfor with side tables: through the stream kernels' decoder (DS2I_DECODE_GENERAL=1: the general decoders)
-    const bool side = idx->side_tables() && !idx->knobs.decode_general;
     double ms = 0.0;
-    HIP_OK(timed_span(idx->stream[0], ms, [&] { return side ? ds2i_launch_verify_index_side(a, grid, idx->stream[0]) : ds2i_launch_verify_index(a, grid, idx->stream[0]); }));
+    rc = st.launch(idx, a, ds2i_launch_verify_index, ds2i_launch_verify_index_side, ms);
+    if (rc != DS2I_OK) return rc;
     if (device_ms) *device_ms = ms;
     HIP_OK(hipMemcpy(&key, d_bad, 8, hipMemcpyDeviceToHost));
     if (key == ds2i_dev::VERIFY_NONE) return DS2I_OK;
@@ -131,7 +99,7 @@ int verify_postings(ds2i_hip_index* idx, const uint64_t* offs, const uint32_t* d
     lf.resize(idx->list_n[t]);
     DS2I_CATCH
     uint64_t n = 0;
-    const int rc = ds2i_hip_decode_list(idx, (uint32_t)t, ld.data(), lf.data(), ld.size(), &n);
+    rc = ds2i_hip_decode_list(idx, (uint32_t)t, ld.data(), lf.data(), ld.size(), &n);
     if (rc != DS2I_OK) return rc;
     r->got = (key & 1) ? lf[r->position] : ld[r->position];
     return DS2I_OK;
@@ -165,29 +133,8 @@ int ds2i_hip_verify_collection(int device, int index_kind, const void* image, si
     const auto t0 = std::chrono::steady_clock::now();
     uint64_t img_docs = 0, img_lists = 0;
     std::vector<uint32_t> img_len;
-    DS2I_TRY
-    if (ds2i_host::is_freq_layout(index_kind)) {
-        ds2i_host::opt_index_view v;
-        v.layout = index_kind;
-        v.parse(image, bytes);
-        img_docs = v.num_docs;
-        img_lists = v.size;
-        img_len.resize(v.size);
-        for (uint64_t t = 0; t < v.size; ++t) img_len[t] = (uint32_t)v.list_length(t);
-    } else {
-        ds2i_host::block_index_view v;
-        v.parse(image, bytes);
-        img_docs = v.num_docs;
-        img_lists = v.size;
-        img_len.resize(v.size);
-        for (uint64_t t = 0; t < v.size; ++t) {
-            uint32_t n = 0;
-            if (!ds2i_host_vbyte(v.lists + v.list_offsets[t], v.list_offsets[t + 1] - v.list_offsets[t], n) || !n)
-                return ds2i_set_error(DS2I_EFORMAT, "posting list header is corrupt");
-            img_len[t] = n;
-        }
-    }
-    DS2I_CATCH
+    rc = ds2i_parse_image(index_kind, image, bytes, img_docs, img_lists, &img_len);
+    if (rc != DS2I_OK) return rc;
     std::memset(report, 0, sizeof *report);
     if (device_ms) *device_ms = 0.0;
     const bool differs = structure_differs(img_docs, img_lists, img_len.data(), num_docs, nlists, list_offsets, report);
@@ -196,14 +143,13 @@ int ds2i_hip_verify_collection(int device, int index_kind, const void* image, si
     // ---- the device: a bare upload (no tables, no transcoding), the kernel, close
     rc = check_device("ds2i_hip_verify_collection", device);
     if (rc != DS2I_OK) return rc;
-    ds2i_hip_index* idx = nullptr;
+    ds2i_hip_index* raw = nullptr;
     const auto t1 = std::chrono::steady_clock::now();
-    rc = ds2i_index_open_bare(device, index_kind, image, bytes, &idx);
+    rc = ds2i_index_open_bare(device, index_kind, image, bytes, &raw);
     if (rc != DS2I_OK) return rc;
+    IndexHandle idx(raw); // (closed on every path out, an exception's included)
     verify_host_s[1] = seconds_since(t1);
-    rc = verify_postings(idx, list_offsets, docs, freqs, report, device_ms);
-    ds2i_hip_index_close(idx);
-    return rc;
+    return verify_postings(idx.get(), list_offsets, docs, freqs, report, device_ms);
 }
 
 void ds2i_hip_verify_host_seconds(double seconds[3]) {

@@ -10,7 +10,9 @@
 //                             (DS2I_OP_REFERENCE_ORDER; > 16 terms; k > 64)
 //   kernels_disjunctive.inc   k_disjunctive, k_union_topk  wand / maxscore / ranked_or (queries.hpp:200-319, 404-476, 478-591) without
 //                             side slots / range tables; k_union  or / or_freq (queries.hpp:88-131) as a stream
-//   kernels_upload.inc        k_decode_list[_side], k_verify_index[_side], k_extract_index[_side], k_block_max_weights, k_build_side_tables, k_list_top_bmw, self-tests
+//   kernels_upload.inc        view_batch_args (the decoders' BatchArgs of an IndexView), k_decode_list[_side], the whole-index walk (walk_index[_side]
+//                             over WalkArgs) under k_verify_index[_side] and k_extract_index[_side], k_block_max_weights, k_build_side_tables,
+//                             k_list_top_bmw, self-tests
 // Compiled once per list-count class (-DDS2I_TU_TMAX=2|4|8|16: launch_t<TMAX> and the kernels it instantiates; =0: launch_long, the
 // class of more than 16 terms) and once without the macro (the entry points and everything else): six translation units that
 // build.py compiles in parallel -- the kernel templates are by far the slowest part of the build. The five class units are

@@ -2,16 +2,22 @@
 // (part of kernels.hip -- included inside its anonymous namespace, once per translation unit of the list-count classes; not a
 // stand-alone header)
 // ------------------------------------------------------------------ list decode
+// The general decoders' BatchArgs of an index view (IndexView, abi_structs.hpp). They read the on-disk bytes: the skip table and the
+// side tables of the view stay out (side_decode_block takes those).
+DS2I_DEV BatchArgs view_batch_args(const IndexView& v) {
+    BatchArgs ba{};
+    ba.arena = v.arena;
+    ba.bits0 = v.bits0;
+    ba.bits1 = v.bits1;
+    ba.codec = v.codec;
+    ba.num_docs = v.num_docs;
+    return ba;
+}
+
 // One wave per 128-posting block of ONE list; writes absolute doc-ids and freqs.
 __global__ void __launch_bounds__(64) k_decode_list(DecodeArgs a) {
     __shared__ Lds<1> L;
-    BatchArgs ba{};
-    ba.arena = a.arena;
-    ba.bits0 = a.bits0;
-    ba.bits1 = a.bits1;
-    ba.codec = a.codec;
-    ba.num_docs = a.num_docs;
-    Ctx cx = make_ctx<-1, MetaLds>(L, ba);
+    Ctx cx = make_ctx<-1, MetaLds>(L, view_batch_args(a.v));
     const uint32_t lane = lane_id();
     cx.bind(0, a.term);
     const uint32_t nb = cx.m(0, M_NB);
@@ -26,26 +32,24 @@ __global__ void __launch_bounds__(64) k_decode_list(DecodeArgs a) {
         }
         wave_sync();
     }
-    cx.flush_stats(a.stats);
 }
 
 // Block b of list t of a block_optpfor index through the exception side slots + tail table (BatchArgs::xslots): the decoder of the
 // stream kernels (optpfor_decode_side). Value i of the block's sz postings in lane i & 63: d0 / f0 hold i = lane, d1 / f1
 // i = lane + 64 (absolute doc-ids, freqs). st / xs: STAGE_DW / XSLOT_DW dwords of LDS of the wave.
 struct SideBlock { uint32_t sz, d0, d1, f0, f1; };
-DS2I_DEV SideBlock side_decode_block(const uint8_t* arena, const void* skip, const uint32_t* xslots, const uint32_t* xovf, const uint32_t* tails,
-                                     const QTerm& t, uint32_t b, uint32_t* st, uint32_t* xs) {
+DS2I_DEV SideBlock side_decode_block(const IndexView& v, const QTerm& t, uint32_t b, uint32_t* st, uint32_t* xs) {
     const uint32_t lane = lane_id();
     const uint32_t n = t.n, nb = (n + 127u) >> 7;
     const uint32_t vl = 1u + (n >= (1u << 7)) + (n >= (1u << 14)) + (n >= (1u << 21)) + (n >= (1u << 28));
-    const uint8_t* const data = arena + t.list_off + vl + 4ull * nb + 4ull * (nb - 1);
-    const uint2* const tab = (const uint2*)skip + t.blk_base;
+    const uint8_t* const data = v.arena + t.list_off + vl + 4ull * nb + 4ull * (nb - 1);
+    const uint2* const tab = (const uint2*)v.skip + t.blk_base;
     const uint32_t sz = ((b + 1) * 128u <= n) ? 128u : (n & 127u);
     const uint32_t base = b ? tab[b - 1].x + 1u : 0u, ep = b ? tab[b - 1].y : 0u;
     uint32_t v0, v1, f0, f1;
     if (sz == 128u) {
         const uint32_t* const g = (const uint32_t*)(data + ep);
-        const uint32_t* const gx = xslots + (size_t)XSLOT_DW * (t.blk_base + b);
+        const uint32_t* const gx = v.xslots + (size_t)XSLOT_DW * (t.blk_base + b);
         st[lane] = g[lane];
         st[lane + 64] = g[lane + 64];
         xs[lane] = gx[lane];
@@ -56,12 +60,12 @@ DS2I_DEV SideBlock side_decode_block(const uint8_t* arena, const void* skip, con
             optpfor_decode_pair(st, xs, h, v0, v1, f0, f1, cd, cf);
         } else {
             uint32_t nd = 0;
-            const uint32_t cons = optpfor_decode_side(st, STAGE_DW, xs, data + ep, xovf, 0u, 0u, v0, v1, &nd);
+            const uint32_t cons = optpfor_decode_side(st, STAGE_DW, xs, data + ep, v.xovf, 0u, 0u, v0, v1, &nd);
             const uint32_t skip_dw = cons >> 2;
-            optpfor_decode_side(st + skip_dw, skip_dw < STAGE_DW ? STAGE_DW - skip_dw : 0u, xs, data + ep + cons, xovf, 1u, nd, f0, f1);
+            optpfor_decode_side(st + skip_dw, skip_dw < STAGE_DW ? STAGE_DW - skip_dw : 0u, xs, data + ep + cons, v.xovf, 1u, nd, f0, f1);
         }
     } else {
-        const uint32_t* const tl = tails + t.aux1;
+        const uint32_t* const tl = v.tails + t.aux1;
         v0 = lane < sz ? tl[lane] : 0u;
         v1 = lane + 64 < sz ? tl[lane + 64] : 0u;
         f0 = lane < sz ? tl[sz + lane] : 0u;
@@ -80,7 +84,7 @@ __global__ void __launch_bounds__(64) k_decode_list_side(DecodeArgs a) {
     const uint32_t lane = lane_id();
     const uint32_t nb = (a.term.n + 127u) >> 7;
     for (uint32_t b = blockIdx.x; b < nb; b += gridDim.x) {
-        const SideBlock k = side_decode_block(a.arena, a.skip, a.xslots, a.xovf, a.tails, a.term, b, st, xs);
+        const SideBlock k = side_decode_block(a.v, a.term, b, st, xs);
         const size_t gpos = (size_t)b * 128u;
         if (lane < k.sz) { a.out_docs[gpos + lane] = k.d0; a.out_freqs[gpos + lane] = k.f0; }
         if (lane + 64 < k.sz) { a.out_docs[gpos + lane + 64] = k.d1; a.out_freqs[gpos + lane + 64] = k.f1; }
@@ -120,23 +124,17 @@ DS2I_DEV void verify_compare(const VerifyArgs& a, uint64_t at, uint32_t sz, uint
 }
 
 // The walk, stated once for the kernels that compare (k_verify_index[_side]) and those that store (k_extract_index[_side]): the wave
-// takes the index-wide block numbers blockIdx.x + [g_begin, g_end) in grid strides, decodes each and hands it to
+// takes the index-wide block numbers blockIdx.x + [a.block_begin, a.block_end) in grid strides, decodes each and hands it to
 // sink(at, left, sz, d0, d1, f0, f1): `at` = the block's first posting in the CSR arrays (a.list_first[l] + its position in the
 // list), `left` = the postings of its list from that position on, value i of its sz postings in lane i & 63 (d0 / f0: i = lane,
-// d1 / f1: i = lane + 64). a.lists holds the lists of the range; their blk_base stay index-wide.
-template <class Args, class Sink>
-DS2I_DEV void walk_index(const Args& a, unsigned long long g_begin, unsigned long long g_end, Lds<1>& L, Sink sink) {
-    BatchArgs ba{};
-    ba.arena = a.arena;
-    ba.bits0 = a.bits0;
-    ba.bits1 = a.bits1;
-    ba.codec = a.codec;
-    ba.num_docs = a.num_docs;
-    Ctx cx = make_ctx<-1, MetaLds>(L, ba);
+// d1 / f1: i = lane + 64). a.lists holds the lists of the range; their blk_base stay index-wide (WalkArgs, abi_structs.hpp).
+template <class Sink>
+DS2I_DEV void walk_index(const WalkArgs& a, Lds<1>& L, Sink sink) {
+    Ctx cx = make_ctx<-1, MetaLds>(L, view_batch_args(a.v));
     const uint32_t lane = lane_id();
     uint32_t l = 0, n = 0;
     unsigned long long base = 0, end = 0, first = 0; // the bound list: its blocks [base, end) and its first posting in the collection
-    for (unsigned long long g = g_begin + blockIdx.x; g < g_end; g += gridDim.x) {
+    for (unsigned long long g = (unsigned long long)a.block_begin + blockIdx.x; g < a.block_end; g += gridDim.x) {
         if (g >= end) {
             l = verify_list_of(a.lists, a.nlists, (uint32_t)g, l);
             const QTerm t = a.lists[l];
@@ -155,12 +153,12 @@ DS2I_DEV void walk_index(const Args& a, unsigned long long g_begin, unsigned lon
 }
 
 // The same through the exception side slots + tail table (side_decode_block, the decode of k_decode_list_side)
-template <class Args, class Sink>
-DS2I_DEV void walk_index_side(const Args& a, unsigned long long g_begin, unsigned long long g_end, uint32_t* st, uint32_t* xs, Sink sink) {
+template <class Sink>
+DS2I_DEV void walk_index_side(const WalkArgs& a, uint32_t* st, uint32_t* xs, Sink sink) {
     uint32_t l = 0;
     unsigned long long base = 0, end = 0, first = 0;
     QTerm t{};
-    for (unsigned long long g = g_begin + blockIdx.x; g < g_end; g += gridDim.x) {
+    for (unsigned long long g = (unsigned long long)a.block_begin + blockIdx.x; g < a.block_end; g += gridDim.x) {
         if (g >= end) {
             l = verify_list_of(a.lists, a.nlists, (uint32_t)g, l);
             t = a.lists[l];
@@ -169,7 +167,7 @@ DS2I_DEV void walk_index_side(const Args& a, unsigned long long g_begin, unsigne
             first = a.list_first[l];
         }
         const uint32_t b = (uint32_t)(g - base);
-        const SideBlock k = side_decode_block(a.arena, a.skip, a.xslots, a.xovf, a.tails, t, b, st, xs);
+        const SideBlock k = side_decode_block(a.v, t, b, st, xs);
         sink(first + (unsigned long long)b * 128u, t.n - b * 128u, k.sz, k.d0, k.d1, k.f0, k.f1);
         wave_sync();
     }
@@ -184,13 +182,13 @@ struct VerifySink {
 
 __global__ void __launch_bounds__(64) k_verify_index(VerifyArgs a) {
     __shared__ Lds<1> L;
-    walk_index(a, 0ull, a.total_blocks, L, VerifySink{a});
+    walk_index(a.w, L, VerifySink{a});
 }
 
 __global__ void __launch_bounds__(64) k_verify_index_side(VerifyArgs a) {
     __shared__ uint32_t st[STAGE_DW];
     __shared__ uint32_t xs[XSLOT_DW];
-    walk_index_side(a, 0ull, a.total_blocks, st, xs, VerifySink{a});
+    walk_index_side(a.w, st, xs, VerifySink{a});
 }
 
 // ------------------------------------------------------------------ whole-index extraction
@@ -210,13 +208,13 @@ struct ExtractSink {
 
 __global__ void __launch_bounds__(64) k_extract_index(ExtractArgs a) {
     __shared__ Lds<1> L;
-    walk_index(a, a.block_begin, a.block_end, L, ExtractSink{a});
+    walk_index(a.w, L, ExtractSink{a});
 }
 
 __global__ void __launch_bounds__(64) k_extract_index_side(ExtractArgs a) {
     __shared__ uint32_t st[STAGE_DW];
     __shared__ uint32_t xs[XSLOT_DW];
-    walk_index_side(a, a.block_begin, a.block_end, st, xs, ExtractSink{a});
+    walk_index_side(a.w, st, xs, ExtractSink{a});
 }
 
 // ------------------------------------------------------------------ upload-time block-max weights
@@ -256,19 +254,13 @@ DS2I_DEV void rmh_mark(uint8_t* tab, uint32_t entry, uint32_t code) {
 
 __global__ void __launch_bounds__(64) k_block_max_weights(BmwArgs a) {
     __shared__ Lds<1> L;
-    BatchArgs ba{};
-    ba.arena = a.arena;
-    ba.bits0 = a.bits0;
-    ba.bits1 = a.bits1;
-    ba.codec = a.codec;
-    ba.num_docs = a.num_docs;
-    Ctx cx = make_ctx<-1, MetaLds>(L, ba);
+    Ctx cx = make_ctx<-1, MetaLds>(L, view_batch_args(a.v));
     const uint32_t lane = lane_id();
     for (uint32_t item = blockIdx.x; item < a.nitems; item += gridDim.x) {
         const BmwItem it = a.items[item];
         const QTerm t = a.lists[it.list];
         if (a.rmw && a.rmw_level) { // coarser levels of the range table: entry e = max of the 64 entries below it
-            const RmwLevels g(a.num_docs, t.rmw_shift);
+            const RmwLevels g(a.v.num_docs, t.rmw_shift);
             const uint8_t* src = a.rmw + 64ull * t.rmw_off64 + g.off[a.rmw_level - 1];
             uint8_t* dst = a.rmw + 64ull * t.rmw_off64 + g.off[a.rmw_level];
             const uint32_t end = it.blk_begin + 4096u < g.e[a.rmw_level] ? it.blk_begin + 4096u : g.e[a.rmw_level];
@@ -300,8 +292,8 @@ __global__ void __launch_bounds__(64) k_block_max_weights(BmwArgs a) {
         uint8_t* const rtab = a.rmw ? a.rmw + 64ull * t.rmw_off64 : nullptr;
         uint8_t* const htab = (a.rmw && a.rmh) ? a.rmh + 64ull * t.rmw_off64 : nullptr;
         const float rinv = t.max_weight > 0.f ? 255.0f / t.max_weight : 0.f; // second pass: max_weight = the list's largest weight
-        unsigned int* const bm = (a.rmw && a.bitmaps && RmwLevels::has_bitmap(t.n, a.num_docs))
-                                     ? (unsigned int*)(a.rmw + 64ull * t.rmw_off64 + RmwLevels(a.num_docs, t.rmw_shift).bytes()) : nullptr;
+        unsigned int* const bm = (a.rmw && a.bitmaps && RmwLevels::has_bitmap(t.n, a.v.num_docs))
+                                     ? (unsigned int*)(a.rmw + 64ull * t.rmw_off64 + RmwLevels(a.v.num_docs, t.rmw_shift).bytes()) : nullptr;
         for (uint32_t b = it.blk_begin; b < end; ++b) {
             cx.decode_docs(0, b);
             cx.decode_freqs(0);

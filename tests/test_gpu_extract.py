@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import ds2i_amd as d
+import oracle as o
 from ds2i_amd.api import _csr
 import verify_cases as cases
 from helpers import queries_for
@@ -65,11 +66,11 @@ HANDLES = [("block_optpfor", None, dict(has_side_tables=1)),
            ("block_mixed", "DS2I_MIXED_NATIVE", dict(transcoded_from=-1))]
 
 
-def open_with(kind, option, image, wand=None):
+def open_with(kind, option, image, wand=None, value=1):
     """the knobs are read once by the upload and kept in the handle: the option is reset as soon as the index is open"""
     try:
         if option:
-            d.set_option(option, 1)
+            d.set_option(option, value)
         return d.Index(kind, image, wand)
     finally:
         if option:
@@ -215,6 +216,58 @@ def test_a_converted_image_answers_queries(built_lib):
     finally:
         converted.close()
         built.close()
+
+
+# ---------------------------------------------------------------- the transcoding upload is the conversion
+TRANSCODED_KINDS = ("opt", "ef", "single", "uniform", "block_mixed")
+
+
+@pytest.mark.parametrize("kind", TRANSCODED_KINDS)
+def test_transcoding_upload_is_the_conversion(built_lib, kind):
+    """the default upload of an image that is transcoded, and a plain block_optpfor upload of the image gpu_convert_index makes of
+    it, are the same index: the same info() but for transcoded_from, and both give the collection back"""
+    coll = cases.small_collection()
+    image, wand = cases.image(coll, kind), coll.wand_image()
+    converted, _ = d.gpu_convert_index(kind, image, "block_optpfor")
+    default, direct = d.Index(kind, image, wand), d.Index("block_optpfor", converted, wand)
+    try:
+        a, b = default.info(), direct.info()
+        assert a.pop("transcoded_from") == d.CODECS[kind] and b.pop("transcoded_from") == -1
+        assert a == b and a["has_side_tables"] and a["has_range_tables"]
+        for idx in (default, direct):
+            check_equal(idx.extract()[:3], coll.lists)
+    finally:
+        default.close()
+        direct.close()
+
+
+@pytest.mark.parametrize("kind", ["opt", "block_mixed"])
+def test_budget_below_a_transcoded_index_keeps_the_image(built_lib, kind):
+    """DS2I_TABLE_BUDGET = one byte per posting: a transcoded index needs more than two (its block_optpfor image alone), so the
+    upload keeps the image as it is -- decided from the image on the host, before anything is uploaded -- and the native kernels
+    answer: every list decodes to the raw list, ranked_and and `and` equal the oracle (counts exactly, scores within 1e-5
+    relative: float32 sums in the same order)"""
+    coll = cases.small_collection()
+    image, wand = cases.image(coll, kind), coll.wand_image()
+    queries = queries_for(coll, nq=48)
+    idx = open_with(kind, "DS2I_TABLE_BUDGET", image, wand, value=cases.postings(coll))
+    try:
+        info = idx.info()
+        assert info["transcoded_from"] == -1 and info["table_budget_bytes"] == cases.postings(coll)
+        for t, (docs, freqs) in enumerate(coll.lists):
+            dd, ff = idx[t]
+            assert np.array_equal(dd, docs) and np.array_equal(ff, freqs), t
+        oidx = o.Index(kind, image, wand)
+        count, topk, tlen, _ = idx.query_batch("ranked_and", queries, k=10)
+        ocount, otopk, otlen, _, _ = oidx.query_batch("ranked_and", queries, k=10)
+        assert np.array_equal(count, ocount) and np.array_equal(tlen, otlen) and int(tlen.sum()) > 0
+        for i in range(len(queries)):
+            np.testing.assert_allclose(topk[i, :tlen[i]], otopk[i, :otlen[i]], rtol=1e-5, err_msg=str(queries[i]))
+            assert np.all(np.isneginf(topk[i, tlen[i]:]))
+        acount = idx.query_batch("and", queries)[0]
+        assert np.array_equal(acount, oidx.query_batch("and", queries)[0]) and int(acount.sum()) > 0
+    finally:
+        idx.close()
 
 
 # ---------------------------------------------------------------- the tool
