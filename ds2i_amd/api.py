@@ -168,6 +168,15 @@ def lib():
         L.ds2i_hip_convert_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, C.c_int, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_extract_host_seconds.argtypes = [C.POINTER(C.c_double)]
         L.ds2i_hip_extract_host_seconds.restype = None
+        L.ds2i_check_doc_map.argtypes = [vp, C.c_uint64]
+        L.ds2i_remap_postings.argtypes = [C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_int]
+        L.ds2i_remap_wand.argtypes = [vp, C.c_size_t, vp, C.c_uint64, C.POINTER(vp)]
+        L.ds2i_hip_remap_class_bounds.argtypes = [u32p]
+        L.ds2i_hip_remap_class_bounds.restype = None
+        L.ds2i_hip_remap_postings.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_double)]
+        L.ds2i_hip_remap_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_remap_ms.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_remap_ms.restype = None
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -408,6 +417,80 @@ def gpu_convert_index(from_kind, image, to_kind, device=0):
     h, ms = C.c_void_p(), C.c_double()
     _check(lib().ds2i_hip_convert_index(device, _codec(from_kind), image, len(image), _codec(to_kind), C.byref(h), C.byref(ms)))
     return _take_blob(h), {"device_ms": ms.value}
+
+
+def check_doc_map(doc_map, num_docs=None):
+    """Raises Ds2iError (-1) naming the first offending old doc-id unless `doc_map` is a permutation of [0, num_docs)
+    (ds2i_check_doc_map; num_docs=None: of its own length)."""
+    m = _u32(doc_map)
+    _check(lib().ds2i_check_doc_map(_ptr(m), len(m) if num_docs is None else num_docs))
+
+
+def _split(lists, offs, docs, freqs):
+    return [(docs[int(offs[t]):int(offs[t + 1])], freqs[int(offs[t]):int(offs[t + 1])]) for t in range(len(lists))]
+
+
+def remap_postings(num_docs, lists, doc_map, threads=0):
+    """`lists` (iterable of (docs, freqs)) with the documents renumbered ON THE HOST (ds2i_remap_postings): new doc-id =
+    doc_map[old doc-id], every list sorted again by its new doc-ids with its freqs. The host twin of gpu_remap_postings.
+    Returns the new lists, in the same order."""
+    lists = list(lists)
+    m = _u32(doc_map)
+    if len(m) != num_docs:
+        raise ValueError("doc_map holds %d entries for %d documents" % (len(m), num_docs))
+    n, offs, docs, freqs = _csr(lists)
+    docs, freqs = docs.copy(), freqs.copy()
+    _check(lib().ds2i_remap_postings(num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), _ptr(m), threads))
+    return _split(lists, offs, docs, freqs)
+
+
+def remap_class_bounds():
+    """(W, L, T) as compiled (ds2i_hip_remap_class_bounds): gpu_remap_postings sorts a list of up to W postings in one wavefront, one
+    of up to L in one workgroup, and the longer ones together in tiles of T postings."""
+    b = (C.c_uint32 * 3)()
+    lib().ds2i_hip_remap_class_bounds(b)
+    return tuple(b)
+
+
+def _remap_info(ms):
+    parts = (C.c_double * 6)()
+    lib().ds2i_hip_remap_ms(parts)
+    return {"device_ms": ms.value, "map_ms": parts[0], "sort_ms": (parts[1], parts[2], parts[3]), "extract_ms": parts[4],
+            "encode_ms": parts[5]}
+
+
+def gpu_remap_postings(num_docs, lists, doc_map, device=0):
+    """remap_postings ON THE GPU (ds2i_hip_remap_postings): a map kernel and a segmented sort in three classes by list length; the
+    same lists, element for element. Returns (new lists, dict(device_ms, map_ms, sort_ms per class, ...))."""
+    lists = list(lists)
+    m = _u32(doc_map)
+    if len(m) != num_docs:
+        raise ValueError("doc_map holds %d entries for %d documents" % (len(m), num_docs))
+    n, offs, docs, freqs = _csr(lists)
+    od, of, ms = np.empty_like(docs), np.empty_like(freqs), C.c_double()
+    _check(lib().ds2i_hip_remap_postings(device, num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), _ptr(m), _ptr(od), _ptr(of), C.byref(ms)))
+    return _split(lists, offs, od, of), _remap_info(ms)
+
+
+def gpu_remap_index(kind, image, doc_map, to_kind=None, device=0):
+    """An index image of `kind` (any of the nine) as the image of `to_kind` (a kind gpu_encode_index writes; None: `kind`) of the
+    collection with its documents renumbered, ON THE GPU (ds2i_hip_remap_index): extracted, mapped, sorted and encoded where the
+    postings lie; byte-identical to build_index(to_kind, ...) over remap_postings' lists. An index holds no wand data: remap_wand
+    renumbers that. Returns (image bytes, dict(device_ms, extract_ms, map_ms, sort_ms per class, encode_ms))."""
+    m = _u32(doc_map)
+    h, ms = C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_remap_index(device, _codec(kind), image, len(image), _ptr(m), len(m), _codec(kind if to_kind is None else to_kind),
+                                      C.byref(h), C.byref(ms)))
+    return _take_blob(h), _remap_info(ms)
+
+
+def remap_wand(wand_image, doc_map):
+    """The wand_data image of the collection with its documents renumbered (ds2i_remap_wand): norm_lens permuted, max_term_weight
+    copied, no pass over the postings; byte-identical to build_wand over the renumbered collection."""
+    m = _u32(doc_map)
+    h = C.c_void_p()
+    _check(lib().ds2i_remap_wand(wand_image, len(wand_image), _ptr(m), len(m), C.byref(h)))
+    return _take_blob(h)
 
 
 def synth_build_gpu(p, device=0, threads=0):
@@ -778,6 +861,8 @@ class Index:
     def __init__(self, kind, index_image, wand_image=None, device=0):
         self._h = C.c_void_p()
         self.kind = _codec(kind)
+        self.device = device
+        self._image = index_image  # (a reference, for remap(): the handle holds no copy of the caller's bytes)
         wi = wand_image if wand_image is not None else None
         _check(lib().ds2i_hip_index_open(device, self.kind, index_image, len(index_image), wi,
                                          len(wand_image) if wand_image is not None else 0, C.byref(self._h)))
@@ -831,6 +916,11 @@ class Index:
         freqs = np.empty(max(total.value, 1), dtype=np.uint32)
         _check(L.ds2i_hip_index_extract(self._h, begin, end, _ptr(offs), _ptr(docs), _ptr(freqs), total.value, C.byref(total), C.byref(ms)))
         return offs, docs[:total.value], freqs[:total.value], {"device_ms": ms.value}
+
+    def remap(self, doc_map, to_kind=None):
+        """The image this index was opened from with its documents renumbered, as an image of `to_kind` (None: the same kind), on
+        this index's device (gpu_remap_index). Returns (image bytes, dict(device_ms, ...)); open it with remap_wand's wand data."""
+        return gpu_remap_index(self.kind, self._image, doc_map, to_kind, device=self.device)
 
     def calibration_read(self):
         n = C.c_uint64()

@@ -431,4 +431,39 @@ struct PartArgs {
     uint32_t* out_ends[2];
 };
 
+// ---- remap_kernels.hip: doc-ids sent through a doc-id map, and every list sorted again by its new doc-ids with the freqs beside them.
+// The host plans the sort from the list lengths (capi_remap.cpp): class 1 lists (<= REMAP_W postings) a wavefront each, class 2
+// lists (<= REMAP_L) a workgroup each, the longer ones cut into tiles of at most REMAP_T postings of ONE list, radix-sorted together.
+constexpr uint32_t REMAP_W = 64;     // class 1: one posting per lane
+constexpr uint32_t REMAP_L = 4096;   // class 2: 8 bytes of LDS per posting, 32 KiB a workgroup (five fit a compute unit's 160 KiB)
+constexpr uint32_t REMAP_T = 4096;   // class 3: postings per tile
+constexpr uint32_t REMAP_DIGIT = 8;  // class 3: key bits per radix pass
+struct RemapTile {
+    uint64_t first;   // the tile's first posting
+    uint32_t count;   // 1 .. REMAP_T
+    uint32_t list3;   // its list, numbered among the class 3 lists
+};
+struct RemapLong {
+    uint64_t first;   // the list's first posting
+    uint32_t tile0;   // its first tile
+    uint32_t ntiles;
+};
+struct RemapArgs {
+    const uint32_t* doc_map;
+    uint64_t num_docs;
+    uint64_t postings;
+    uint32_t *docs, *freqs;         // the postings as extracted; the map kernel rewrites docs in place
+    uint32_t *docs_b, *freqs_b;     // class 3's second buffer pair (null without class 3 lists)
+    uint32_t *out_docs, *out_freqs; // where the sorted lists end up: the first pair, or the second when class 3 takes an odd number of passes
+    const uint64_t* list_first;     // nlists + 1 posting offsets
+    const uint32_t* lists1;         // the class 1 lists
+    const uint32_t* lists2;         // the class 2 lists
+    uint32_t nlists1, nlists2;
+    const RemapTile* tiles;
+    const RemapLong* longs;
+    uint32_t ntiles, nlongs;
+    uint32_t* hist;                 // class 3: (1 << REMAP_DIGIT) words per tile: digit counts, then (after the scan) where each digit's run goes within the list
+    uint32_t* flag;                 // set by the map kernel when a doc-id lies outside the map
+};
+
 } // namespace ds2i_dev

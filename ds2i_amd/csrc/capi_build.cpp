@@ -15,6 +15,7 @@
 #include "host_pef.hpp"
 #include "host_hybrid.hpp"
 #include "host_parallel.hpp"
+#include "host_remap.hpp"
 #include "host_synth.hpp"
 
 using namespace ds2i_host;
@@ -172,6 +173,45 @@ int ds2i_opt_partition(uint64_t num_docs, uint64_t nlists, const uint64_t* list_
     opt_partitions parts;
     host_opt_partitions(num_docs, nlists, list_offsets, docs, freqs, parts);
     partition_blobs(parts, docs_ends, docs_offs, freqs_ends, freqs_offs);
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_check_doc_map(const uint32_t* doc_map, uint64_t num_docs) {
+    if (!doc_map && num_docs) return ds2i_set_error(DS2I_EINVAL, "ds2i_check_doc_map: null argument");
+    DS2I_TRY
+    const std::string fault = doc_map_fault(doc_map, num_docs);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, ("ds2i_check_doc_map: " + fault).c_str());
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_remap_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, uint32_t* docs, uint32_t* freqs, const uint32_t* doc_map,
+                        int threads) {
+    if (!list_offsets || !docs || !freqs || !doc_map) return ds2i_set_error(DS2I_EINVAL, "ds2i_remap_postings: null argument");
+    if (list_offsets[0] != 0) return ds2i_set_error(DS2I_EINVAL, "ds2i_remap_postings: list_offsets must start at 0");
+    for (uint64_t t = 0; t < nlists; ++t)
+        if (list_offsets[t + 1] < list_offsets[t]) return ds2i_set_error(DS2I_EINVAL, "ds2i_remap_postings: list_offsets decrease");
+    const int rc = ds2i_check_doc_map(doc_map, num_docs);
+    if (rc != 0) return rc;
+    DS2I_TRY
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    remap_postings(num_docs, nlists, list_offsets, docs, freqs, doc_map, (unsigned)threads);
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_remap_wand(const void* wand_image, size_t bytes, const uint32_t* doc_map, uint64_t num_docs, ds2i_blob** out) {
+    if (!wand_image || !doc_map || !out) return ds2i_set_error(DS2I_EINVAL, "ds2i_remap_wand: null argument");
+    DS2I_TRY
+    wand_view w;
+    w.parse(wand_image, bytes);
+    if (w.num_docs != num_docs) return ds2i_set_error(DS2I_EINVAL, "ds2i_remap_wand: the map's length is not the wand data's number of documents");
+    const int rc = ds2i_check_doc_map(doc_map, num_docs);
+    if (rc != 0) return rc;
+    std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
+    remap_wand(w, doc_map, blob->data);
+    *out = blob.release();
     return 0;
     DS2I_CATCH
 }

@@ -2,7 +2,8 @@
 // argument checks, the host parse of an image before any device is touched, ONE launch of k_extract_index[_side]
 // (kernels_upload.inc: the verifier's whole-index walk with stores instead of compares) over the blocks of a range of lists, and
 // what is done with the postings: copied to the caller, or handed to the index encoder where they lie (capi_encode.cpp,
-// ds2i_encode_device_postings), so that a conversion between kinds never sends them over the bus. The host parse, the extraction
+// ds2i_encode_device_postings), so that a conversion between kinds never sends them over the bus -- renumbered on the way through a doc-id map when one is given
+// (capi_remap.cpp: ds2i_remap_device_postings, the step ds2i_hip_remap_index adds to a conversion). The host parse, the extraction
 // into device buffers and the conversion of an image are declared in capi_util.hpp: the verification and the transcoding upload
 // (capi.cpp, index_open_transcoded) use them too.
 #include <hip/hip_runtime.h>
@@ -78,7 +79,7 @@ int ds2i_extract_to_device(ds2i_hip_index* idx, uint64_t begin, uint64_t end, co
 }
 
 int ds2i_convert_image(const char* who, int device, int from_kind, const void* image, size_t bytes, int to_kind, ds2i_blob** out_image, double* device_ms,
-                       bool* no_room) {
+                       bool* no_room, const uint32_t* doc_map, double* remap_ms) {
     ds2i_hip_index* raw = nullptr;
     int rc = ds2i_index_open_bare(device, from_kind, image, bytes, &raw);
     if (rc != DS2I_OK) return rc;
@@ -92,12 +93,22 @@ int ds2i_convert_image(const char* who, int device, int from_kind, const void* i
     rc = ds2i_extract_to_device(idx.get(), 0, V, offs.data(), dp, ms_extract);
     if (no_room) *no_room = rc == DS2I_ENOMEM;
     if (rc != DS2I_OK) return rc;
-    idx.reset(); // the source image leaves the device before the encoder's tables and output arrive
+    idx.reset(); // the source image leaves the device before the sort's second buffers or the encoder's tables and output arrive
+    double ms_remap[4] = {0.0, 0.0, 0.0, 0.0};
+    if (doc_map) { // the documents renumbered where the postings lie (capi_remap.cpp); its temporaries are gone when it returns
+        rc = ds2i_remap_device_postings(who, device, num_docs, V, offs.data(), dp, doc_map, ms_remap);
+        if (rc != DS2I_OK) return rc;
+    }
     uint32_t *d_docs = dp.docs, *d_freqs = dp.freqs;
     dp.release(); // (the encoder's staging owns them from here on)
     rc = ds2i_encode_device_postings(who, device, to_kind, num_docs, V, offs.data(), d_docs, d_freqs, out_image, &ms_encode);
     if (rc != DS2I_OK) return rc;
-    if (device_ms) *device_ms = ms_extract + ms_encode;
+    if (device_ms) *device_ms = ms_extract + ms_remap[0] + ms_remap[1] + ms_remap[2] + ms_remap[3] + ms_encode;
+    if (remap_ms) {
+        std::copy(ms_remap, ms_remap + 4, remap_ms);
+        remap_ms[4] = ms_extract;
+        remap_ms[5] = ms_encode;
+    }
     return DS2I_OK;
     DS2I_CATCH
 }

@@ -130,12 +130,25 @@ struct WalkStaging {
 // of a block codec target never leave the device): bare upload, extraction of every list, the source closed, the encoder. What ds2i_hip_convert_index does once its
 // arguments are checked and the image is parsed, and what the transcoding upload does (capi.cpp, index_open_transcoded). Every
 // device buffer of the attempt is released before it returns an error. no_room (may be null) is set when that error is the
-// extraction's DS2I_ENOMEM: the postings do not fit beside the source image.
+// extraction's DS2I_ENOMEM: the postings do not fit beside the source image. doc_map (null: a plain conversion): a checked permutation of
+// the image's documents; between the source's release and the encoder the postings are renumbered through it where they lie
+// (remap_device_postings). remap_ms (may be null) then receives the hipEvent milliseconds of {map kernel, sort class 1, 2, 3,
+// extraction, encoder}; device_ms is their sum.
 int ds2i_parse_image(int index_kind, const void* image, size_t bytes, uint64_t& num_docs, uint64_t& nlists, std::vector<uint32_t>* lengths);
 int ds2i_extract_to_device(ds2i_hip_index* idx, uint64_t begin, uint64_t end, const uint64_t* offs, DevPostings& out, double& ms);
 struct ds2i_blob;
 int ds2i_convert_image(const char* who, int device, int from_kind, const void* image, size_t bytes, int to_kind, ds2i_blob** out_image,
-                       double* device_ms, bool* no_room);
+                       double* device_ms, bool* no_room, const uint32_t* doc_map = nullptr, double* remap_ms = nullptr);
+
+// capi_remap.cpp. The postings of nlists lists on `device` (offs on the host, as WalkStaging::stage takes them) renumbered: every doc-id
+// through doc_map -- a permutation of [0, num_docs), checked by the caller (ds2i_check_doc_map) -- and every list sorted again by its
+// new doc-ids, the freqs with them. dp's buffers are the input and, on DS2I_OK, hold the result: they may have been exchanged for the
+// sort's second pair, and whichever pair is not the result has been freed, with every table of the sort, before this returns.
+// While it runs: 16 bytes per posting when a list is longer than a workgroup sorts (else 8), 4 per document, 8 per list.
+// A doc-id >= num_docs among the postings is DS2I_EFORMAT (nothing is read past the map). ms[0 .. 3] receive the hipEvent
+// milliseconds of the map kernel and of sort classes 1, 2 and 3.
+int ds2i_remap_device_postings(const char* who, int device, uint64_t num_docs, uint64_t nlists, const uint64_t* offs, DevPostings& dp,
+                               const uint32_t* doc_map, double ms[4]);
 
 // capi_encode.cpp, for capi_extract.cpp (ds2i_hip_convert_index). check_encoder_kind: DS2I_OK for the seven kinds the GPU encoder
 // writes, else ds2i_hip_encode_index's DS2I_EINVAL naming them. encode_device_postings: ds2i_hip_encode_index over postings that

@@ -72,4 +72,12 @@ hipError_t ds2i_launch_freq_write(int freqs_side, const ds2i_dev::FreqEncArgs& a
 // to a.out_ends at a.out_offs
 hipError_t ds2i_launch_partition_plan(const ds2i_dev::PartArgs& a, hipStream_t s);
 hipError_t ds2i_launch_partition_gather(const ds2i_dev::PartArgs& a, hipStream_t s);
+// ---- remap_kernels.hip: a staged collection renumbered through a doc-id map. grid: workgroups of 256 threads, which stride.
+// map: a.docs through a.doc_map in place (a.flag: a doc-id outside the map); sort1 / sort2: the class 1 / class 2 lists from
+// a.docs / a.freqs to a.out_docs / a.out_freqs; radix_pass: one pass of class 3 over the key bits from `shift` on, from the first
+// buffer pair to the second or (from_second) back: the histogram, scan and scatter kernels, in that order, on s
+hipError_t ds2i_launch_remap_map(const ds2i_dev::RemapArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_remap_sort1(const ds2i_dev::RemapArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_remap_sort2(const ds2i_dev::RemapArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_remap_radix_pass(const ds2i_dev::RemapArgs& a, int from_second, uint32_t shift, unsigned grid, hipStream_t s);
 }

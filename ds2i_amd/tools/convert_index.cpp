@@ -1,6 +1,7 @@
 // convert_index -- an index file of one kind turned into an index file of another, or back into a collection, on the GPU.
 //
 //   convert_index <from_type> <in_index> <to_type> <out_index> [--check] [--device <n>]
+//   convert_index <from_type> <in_index> <to_type> <out_index> --remap <map> [--wand <in.wand> <out.wand>] [--check] [--device <n>]
 //   convert_index <from_type> <in_index> --dump <collection_basename> [--device <n>]
 //
 // The first form writes the image ds2i_hip_convert_index returns: byte-identical to what create_freq_index <to_type> writes for
@@ -9,7 +10,12 @@
 //   --check       the input is extracted (ds2i_hip_extract_collection) and the written file verified against it
 //                 (ds2i_hip_verify_collection): one line on stdout, "OK lists=<V> postings=<n>" or "MISMATCH <what> ..." as
 //                 create_freq_index --check prints it.
-// The second form writes <basename>.docs and <basename>.freqs in the ds2i binary-collection form (little-endian u32 streams of
+// The second form renumbers the documents on the way (ds2i_hip_remap_index): <map> is one ds2i binary sequence, [num_docs][num_docs x u32]
+// (the layout of a .sizes file), new doc-id = map[old doc-id], a permutation. A map file that is missing, short or long is a usage
+// error, found before any device is touched. The file written is what create_freq_index <to_type> writes for the renumbered collection.
+//   --wand <in.wand> <out.wand>  the wand data renumbered too (ds2i_remap_wand): an index holds none
+//   --check       the input is extracted, renumbered on the host (ds2i_remap_postings) and the written file verified against that
+// The third form writes <basename>.docs and <basename>.freqs in the ds2i binary-collection form (little-endian u32 streams of
 // [len][len x u32] sequences, .docs led by [1][num_docs]). No <basename>.sizes is written: an index does not hold the document
 // sizes (nor wand data).
 //   --device <n>  the HIP device (default 0)
@@ -19,9 +25,26 @@
 #include <cstdlib>
 
 static const char* const USAGE =
-    " <from_type> <in_index> <to_type> <out_index> [--check] [--device <n>]\n"
+    " <from_type> <in_index> <to_type> <out_index> [--remap <map> [--wand <in.wand> <out.wand>]] [--check] [--device <n>]\n"
     "       convert_index <from_type> <in_index> --dump <collection_basename> [--device <n>]\n"
-    "  --dump writes <collection_basename>.docs and .freqs; no .sizes, because an index does not hold the document sizes\n";
+    "  --dump writes <collection_basename>.docs and .freqs; no .sizes, because an index does not hold the document sizes\n"
+    "  --remap renumbers the documents: <map> is one binary sequence [num_docs][num_docs x u32], new doc-id = map[old doc-id]\n";
+
+// the doc-id map of --remap: one binary sequence whose length word counts exactly the words behind it
+struct doc_map_file {
+    tool::mapped_file f;
+    uint64_t num_docs = 0;
+    explicit doc_map_file(const char* path) : f(path) {
+        if (f.size < 4) throw std::runtime_error(std::string("the map file ") + path + " holds no length word");
+        uint32_t n;
+        std::memcpy(&n, f.data, 4);
+        if (f.size != 4 * (uint64_t(n) + 1))
+            throw std::runtime_error(std::string("the map file ") + path + " announces " + std::to_string(n) + " documents and holds " +
+                                     std::to_string(f.size / 4 - 1) + " words");
+        num_docs = n;
+    }
+    const uint32_t* map() const { return (const uint32_t*)f.data + 1; }
+};
 
 // the collection an index file holds
 struct extracted {
@@ -69,12 +92,17 @@ static void write_sequences(std::string const& path, std::vector<uint32_t> const
 int main(int argc, const char** argv) {
     std::vector<const char*> pos;
     bool check = false, dump = false, bad_flag = false;
+    const char *map_path = nullptr, *wand_in = nullptr, *wand_out = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         if (a == "--check") check = true;
         else if (a == "--dump") dump = true;
-        else if (a == "--device" && i + 1 < argc) {
+        else if (a == "--remap" && i + 1 < argc) map_path = argv[++i];
+        else if (a == "--wand" && i + 2 < argc) {
+            wand_in = argv[++i];
+            wand_out = argv[++i];
+        } else if (a == "--device" && i + 1 < argc) {
             char* end = nullptr;
             const long v = std::strtol(argv[++i], &end, 10);
             if (end == argv[i] || *end || v < 0 || v > 1 << 20) bad_flag = true; // (not a device number)
@@ -82,7 +110,7 @@ int main(int argc, const char** argv) {
         } else if (a.rfind("--", 0) == 0) bad_flag = true;
         else pos.push_back(argv[i]);
     }
-    if (bad_flag || pos.size() != (dump ? 3u : 4u) || (dump && check)) {
+    if (bad_flag || pos.size() != (dump ? 3u : 4u) || (dump && check) || (dump && map_path) || (wand_in && !map_path)) {
         std::cerr << "usage: " << argv[0] << USAGE;
         return 2;
     }
@@ -109,8 +137,18 @@ int main(int argc, const char** argv) {
             tool::logger(std::string("ERROR: Unknown type ") + pos[2]);
             return 2;
         }
+        std::unique_ptr<doc_map_file> map;
+        if (map_path) {
+            try {
+                map.reset(new doc_map_file(map_path));
+            } catch (std::exception const& e) {
+                std::cerr << "ERROR: " << e.what() << "\nusage: " << argv[0] << USAGE;
+                return 2;
+            }
+        }
         ds2i_blob* img = nullptr;
-        tool::hip_ok(ds2i_hip_convert_index(device, from, in.data, in.size, to, &img, nullptr), "ds2i_hip_convert_index");
+        if (map) tool::hip_ok(ds2i_hip_remap_index(device, from, in.data, in.size, map->map(), map->num_docs, to, &img, nullptr), "ds2i_hip_remap_index");
+        else tool::hip_ok(ds2i_hip_convert_index(device, from, in.data, in.size, to, &img, nullptr), "ds2i_hip_convert_index");
         const size_t bytes = ds2i_blob_size(img);
         try {
             tool::write_blob(pos[3], img);
@@ -122,6 +160,25 @@ int main(int argc, const char** argv) {
         std::ostringstream os;
         os << in.size << " bytes of " << pos[0] << " -> " << bytes << " bytes of " << pos[2];
         tool::logger(os.str());
+        if (wand_in) {
+            tool::mapped_file w(wand_in);
+            ds2i_blob* wimg = nullptr;
+            tool::hip_ok(ds2i_remap_wand(w.data, w.size, map->map(), map->num_docs, &wimg), "ds2i_remap_wand");
+            try {
+                tool::write_blob(wand_out, wimg);
+            } catch (...) {
+                ds2i_blob_free(wimg);
+                throw;
+            }
+            ds2i_blob_free(wimg);
+        }
+        if (check && map) { // against the host twin over the extraction of the input
+            extracted c(device, from, in);
+            const uint64_t total = c.offs()[c.lists];
+            std::vector<uint32_t> docs(c.d(), c.d() + total), freqs(c.f(), c.f() + total);
+            tool::hip_ok(ds2i_remap_postings(c.num_docs, c.lists, c.offs(), docs.data(), freqs.data(), map->map(), 0), "ds2i_remap_postings");
+            return tool::check_index_file(device, to, pos[3], c.num_docs, c.lists, c.offs(), docs.data(), freqs.data());
+        }
         if (check) {
             extracted c(device, from, in);
             return tool::check_index_file(device, to, pos[3], c.num_docs, c.lists, c.offs(), c.d(), c.f());

@@ -89,6 +89,24 @@ int ds2i_write_sequence(int seq_kind, const uint64_t* values, uint64_t n, uint64
 int ds2i_opt_partition(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
                        ds2i_blob** docs_ends, ds2i_blob** docs_offs, ds2i_blob** freqs_ends, ds2i_blob** freqs_offs);
 
+/* Renumbering the documents of a collection: new doc-id = doc_map[old doc-id], doc_map a permutation of [0, num_docs). Deleting
+ * documents (a map that drops ids) is not offered. The device forms, ds2i_hip_remap_postings and ds2i_hip_remap_index, are in ds2i_hip.h.
+ * check_doc_map: DS2I_OK, or DS2I_EINVAL with ds2i_hip_last_error() naming the FIRST offending old doc-id: one whose value is
+ * >= num_docs, or the second document sent to an id already taken. One bit per document; every entry point that takes a map runs it
+ * before anything else is done with the map, and before any device is touched.
+ * remap_postings: the host twin of ds2i_hip_remap_postings, in place: lists in the CSR form of ds2i_opt_partition (empty lists are
+ * allowed), every doc-id through the map, then every list sorted by its new doc-ids, the freqs travelling with them; list lengths and
+ * list order do not change. Lists are spread over `threads` host threads (<= 0: up to 16). A doc-id >= num_docs among the postings
+ * is DS2I_EFORMAT, as on the device; lists already done stay remapped.
+ * remap_wand: the wand image of the renumbered collection with no pass over the postings: norm_lens permuted, max_term_weight
+ * copied. Byte-identical to ds2i_wand_create / _add_list / _freeze over the renumbered collection: the average document length is a
+ * sum of integer-valued floats in a double, which does not depend on their order, and a term's maximum is taken over the same
+ * floats. num_docs is the map's length and must be the image's. */
+int ds2i_check_doc_map(const uint32_t* doc_map, uint64_t num_docs);
+int ds2i_remap_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, uint32_t* docs, uint32_t* freqs,
+                        const uint32_t* doc_map, int threads);
+int ds2i_remap_wand(const void* wand_image, size_t bytes, const uint32_t* doc_map, uint64_t num_docs, ds2i_blob** out);
+
 /* The chunk directory ds2i_hip_index_open builds for one list of an opt image (inspection / test hook):
  * cmax = u32[nchunks] last doc-id per chunk, chunks = nchunks x 12 dwords (ds2i_amd/csrc/device_pef.hpp),
  * info = {n, docs_bit0, freqs_bit0, docs bit-vector byte offset in the image, freqs bit-vector byte offset} */

@@ -409,6 +409,39 @@ int ds2i_hip_convert_index(int device, int from_kind, const void* image, size_t 
  * seconds[1] its bare upload, seconds[2] the copy of the postings to the host. */
 void ds2i_hip_extract_host_seconds(double seconds[3]);
 
+/* Renumbering the documents on the GPU: new doc-id = doc_map[old doc-id], doc_map a permutation of [0, num_docs) (ds2i_check_doc_map,
+ * ds2i_build.h, run before any device is touched). List lengths and list order do not change; within every list the postings are
+ * sorted again by their new doc-ids and the freqs travel with them. The doc-ids of a list are distinct, so the result is unique: it
+ * is ds2i_remap_postings' (ds2i_build.h, the host twin), element for element. A map kernel sends every doc-id through the map; the
+ * sort is planned on the host from the list lengths into three classes (ds2i_hip_remap_class_bounds: W, L, T): lists of up to W
+ * postings are sorted in the registers of one wavefront each, lists of up to L in the LDS of one workgroup each, and the longer ones
+ * together, in tiles of T postings, by an LSD radix sort over the key bits num_docs needs, between two buffer pairs. No kernel
+ * waits for another workgroup; the order between the steps is the order of the launches on one stream.
+ *
+ * ds2i_hip_remap_postings: a collection in (CSR form of ds2i_hip_encode_index; empty lists are allowed), the renumbered collection
+ * out; out_docs / out_freqs hold list_offsets[nlists] words each and may be docs / freqs. Checks, in this order: null arguments and
+ * the offsets (DS2I_EINVAL), the map (DS2I_EINVAL), the device (DS2I_EDEVICE). A doc-id >= num_docs among the postings is found by
+ * the map kernel, which never reads past the map: DS2I_EFORMAT, no output written. Device memory: 16 bytes per posting, 4 per
+ * document. device_ms (may be NULL): the hipEvent time of the kernels.
+ *
+ * ds2i_hip_remap_index: an image of from_kind (any of the nine) as the image of to_kind of the renumbered collection, byte-identical
+ * to the host builder's over the host twin's lists. to_kind as ds2i_hip_convert_index takes it (DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED
+ * are DS2I_EINVAL, same message). Checks, in this order: null arguments, the kinds, the host parse of the image (DS2I_EFORMAT),
+ * map_len == the image's number of documents, the map, the device. Then ds2i_hip_convert_index's steps with one more: bare upload,
+ * extraction, the source image closed, map and sort, the sort's second buffer pair freed, the encoder over the postings where
+ * they lie. The postings never cross the bus for a block codec target. Peak device memory: the image + 8 bytes per posting while
+ * extracting, then 16 bytes per posting + 4 per document while sorting, then the encoder's. What does not fit is DS2I_ENOMEM with
+ * everything released (there is no chunked form). An index holds no wand data: ds2i_remap_wand (ds2i_build.h) renumbers that.
+ * device_ms: extraction + map + sort + encoder. */
+void ds2i_hip_remap_class_bounds(uint32_t bounds[3]);
+int ds2i_hip_remap_postings(int device, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs,
+                            const uint32_t* freqs, const uint32_t* doc_map, uint32_t* out_docs, uint32_t* out_freqs, double* device_ms);
+int ds2i_hip_remap_index(int device, int from_kind, const void* image, size_t bytes, const uint32_t* doc_map, uint64_t map_len, int to_kind,
+                         ds2i_blob** out_image, double* device_ms);
+/* Diagnostic: the hipEvent milliseconds of this thread's last ds2i_hip_remap_postings / ds2i_hip_remap_index: ms[0] the map kernel,
+ * ms[1 .. 3] sort classes 1, 2 and 3, ms[4] the extraction and ms[5] the encoder (both 0 for ds2i_hip_remap_postings). */
+void ds2i_hip_remap_ms(double ms[6]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
