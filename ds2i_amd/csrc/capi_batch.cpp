@@ -28,6 +28,7 @@
 #include "knobs.hpp"
 #include "host_index.hpp"
 #include "launchers.hpp"
+#include "unit_cut.hpp"
 
 using ds2i_dev::BatchArgs;
 using ds2i_dev::MergeArgs;
@@ -239,6 +240,7 @@ struct ds2i_hip_batch {
     bool uploaded = false, launched = false;
     float cls_ms[NCLS] = {};
     Stats cls_stats[NCLS] = {};
+    std::vector<uint32_t> empty_queries; // k > 64: the empty queries, answered without a unit (cut_units; last: the members above keep their places)
 };
 
 namespace {
@@ -642,6 +644,28 @@ void cut_union_query(ds2i_hip_batch* b, uint32_t q, int c, uint32_t ut_blocks) {
     if (total > 1) b->split_queries.push_back(q);
 }
 
+// Ranked conjunctions with range tables, batches of 1536 queries and more (cut_units): the parts of a split query taper (unit_cut.hpp) --
+// the first one (1 - taper_ratio) of the query but at most taper_cap equal parts, each next one taper_ratio times the one before, down
+// to the equal part; a part costs its share of the blocks, so that the class order (costliest first) starts a query's large parts first.
+// cap_blocks (DS2I_UNIT_CAP; 0 = none) bounds every part, the first included. Measured on the GOV2-scale batch, 4096 queries, one
+// index, four interleaved rounds of 60 pipelined steps each (median queries/s, units per batch without the two-list stream group,
+// which the listing left out): equal cut 1 071 k, 50.1 k units | ratio 1/2, cap 2: 1 122 k, 48.0 k | 1/2, 4: 1 059 k, 43.2 k |
+// 1/2, 8: 721 k, 35.5 k | 2/3, 2: 1 134 k, 48.2 k | 2/3, 4: 1 049 k, 42.6 k | 2/3, 8: 790 k, 34.1 k; the spread of a point over its
+// rounds is 1-8 k except 2/3, 4 (17 k). A first part of 4 or 8 equal parts becomes the tail of its launch group.
+static void add_tapering_units(ds2i_hip_batch* b, int c, uint32_t q, uint32_t nb0, uint32_t parts, uint32_t cap_blocks, double cost,
+                               std::vector<uint32_t>& cut) {
+    const double taper_ratio = 2.0 / 3.0, taper_cap = 2.0;
+    parts = ds2i_cut::cut_blocks(nb0, parts, taper_ratio, taper_cap, cap_blocks, cut);
+    if (parts > 1) b->split_queries.push_back(q);
+    for (uint32_t j = 0; j < parts; ++j) add_unit(b, c, q, cut[j], cut[j + 1], parts, ds2i_cut::part_cost(cost, nb0, cut[j], cut[j + 1]));
+}
+// What starting a unit costs, in the cost model's units: where the parts taper, a part's own work is never priced below it. Measured on
+// the GOV2-scale batch: 62.6 M units of cost run for 17.9 s of wave time (DS2I_UNIT_CLOCK, the sum of the unit times), 0.29 us per unit
+// of cost; unit setup is 0.8 % of a two-list unit's cycles (median unit 650 us: 5 us) and 8 % / 24 % of a three- / four-list unit's
+// (mean unit 208 us, setup 15 % of the two together: 30 us). The 256 floor is above both; beyond 8 lists (floor 48) nothing was
+// measured, and the four-list figure is taken -- at 1536 queries and more that class's target is above it as well.
+static double unit_start_cost(uint32_t nt) { return nt <= 2 ? 17.0 : 105.0; }
+
 // ---- work units: long conjunctive queries are split by block ranges of their shortest list so
 // that one giant query does not pin a single wavefront (SURVEY.md §7 "Load imbalance")
 // all_cost: the batch's cost (plan_queries), scaled here to the batches in flight
@@ -657,6 +681,7 @@ static void cut_units(ds2i_hip_batch* b, double& all_cost) {
     b->q_unit_off.assign(nq + 1, 0);
     b->split_queries.clear();
     b->single_queries.clear();
+    b->empty_queries.clear();
     for (int c = 0; c < NCLS; ++c) {
         b->cls_units[c].clear();
         b->nqcls[c] = 0;
@@ -675,8 +700,9 @@ static void cut_units(ds2i_hip_batch* b, double& all_cost) {
     const double resident = idx->num_cus * 24.0; // waves the concurrent kernels share
     // units per resident wave (tuning knob, DS2I_UNIT_FACTOR): more = better tail balance, more per-unit overhead
     // With range tables a ranked conjunction is cheap per block and the parts of a split query each pay for warming up
-    // their own heap: coarser units win (measured on the GOV2-scale batch, queries/s: factor 16: 355 k, 8: 344 k,
-    // 4 with the many-list classes cut 4x finer: 430-457 k, 2: 251 k)
+    // their own heap: coarser units win (measured on the GOV2-scale batch with the block-synchronous kernels of round 3, queries/s:
+    // factor 16: 355 k, 8: 344 k, 4 with the many-list classes cut 4x finer: 430-457 k, 2: 251 k; with the stream kernels and the tapering cut below, 4096 queries:
+    // factor 2: 930 k, 4: 1 119-1 136 k over four runs, 8: 1 146 k in its one run -- no worse than 4, not told apart from it)
     const bool rmw_units = r.ranked && r.conj && idx->d_rmw; // (and / and_freq verify every candidate the tables let through: their cost
                                                              // stays with the blocks of all lists, and they are throughput-, not tail-bound: measured)
     // (a small batch -- the per-GPU share of a batch sharded over several GPUs -- is cut coarser still: at 512 queries factor 2
@@ -685,6 +711,9 @@ static void cut_units(ds2i_hip_batch* b, double& all_cost) {
     const uint32_t and_unit_blocks = 96u; // (measured, `and`: 48: 965 k, 96: 1 068 k, 192: 1 190 k against 1 360 k of the same build, whole queries: 802 k; and_freq: 24 | 48 | 96 all 334-337 k)
     const uint32_t ut_blocks = idx->knobs.ut_blocks; // DS2I_UT_BLOCKS, default 320: blocks of the driving list per unit (k_union_topk, round 4: 96: 335 k, 128-256: 345-352 k, 384: 335 k queries/s; k_union_stream, round 6: 64: 240 k, 160: 378 k, 320: 401 k)
     const bool split_ok = r.conj && !r.reference;
+    // (ranked conjunctions with range tables, batches of 1536 queries and more: the parts of a split query taper -- add_tapering_units)
+    const bool taper_batch = rmw_units && split_ok && nq >= 1536;
+    std::vector<uint32_t> cut;
     for (uint32_t q = 0; q < nq; ++q) {
         const uint32_t nt = qoff[q + 1] - qoff[q];
         const int c = r.goes_long(nt) ? CLS_LONG : class_of(nt);
@@ -707,15 +736,19 @@ static void cut_units(ds2i_hip_batch* b, double& all_cost) {
             b->q_unit_off[q + 1] = (uint32_t)b->units.size();
             continue;
         }
-        if (c == CLS_LONG) { // > 16 terms: one unit, reference-order traversal over global scratch
+        if (c == CLS_LONG && !nt) {
+            // an empty query of a k > 64 batch (Route::goes_long(0); the seed pass of a k > 64 union batch holds thousands of them): no
+            // k_daat_long unit -- the rows are cleared before the kernels run, and an untouched row is the empty answer (count 0, length 0,
+            // doc-ids 0xFFFFFFFF) but for its scores, which copy_results pads
+            b->empty_queries.push_back(q);
+        } else if (c == CLS_LONG) { // > 16 terms: one unit, reference-order traversal over global scratch
             add_unit(b, c, q, 0, r.conj ? std::max(1u, qnb0[q]) : (uint32_t)idx->num_docs, 1, qcost[q]);
         } else if (r.conj) {
-            uint32_t parts = 1;
-            if (split_ok && nt && qnb0[q] > 1) {
-                double want = std::floor(qcost[q] / target);
-                parts = (uint32_t)std::min<double>(std::max(1.0, want), qnb0[q]);
-            }
             const uint32_t nb0 = std::max(1u, qnb0[q]);
+            const bool taper = taper_batch && nt > 1;
+            uint32_t parts = 1;
+            if (split_ok && nt && qnb0[q] > 1) parts = ds2i_cut::equal_parts(nb0, qcost[q], taper ? std::max(target, unit_start_cost(nt)) : target);
+            uint32_t cap_blocks = 0; // DS2I_UNIT_CAP: the blocks a unit may hold at most (0 = no bound)
             if (rmw_units && split_ok && nt > 1) {
                 // The cost model prices a block of the driving list at its average, but a query whose conjunction holds fewer than k
                 // documents never gets a threshold: every one of its blocks goes all the way through the other lists (10 us per
@@ -724,16 +757,23 @@ static void cut_units(ds2i_hip_batch* b, double& all_cost) {
                 // such queries; DS2I_UNIT_CAP (blocks; half of it beyond 2 lists) additionally bounds every unit -- off by
                 // default: cutting EVERY query that fine cost 20 % (each part warms up its own heap). The tests use it to split everything.
                 const uint32_t cap_env = idx->knobs.unit_cap;
-                if (cap_env) parts = std::max(parts, (nb0 + (c == 0 ? cap_env : std::max(8u, cap_env / 2)) - 1) / (c == 0 ? cap_env : std::max(8u, cap_env / 2)));
+                if (cap_env) {
+                    cap_blocks = c == 0 ? cap_env : std::max(8u, cap_env / 2);
+                    parts = std::max(parts, (nb0 + cap_blocks - 1) / cap_blocks);
+                }
             }
             // `and` through the stream pipeline has no heap to warm up -- a part costs its blocks and nothing else -- and a two-list query
             // left whole was a single wave for up to 13 ms (DS2I_UNIT_CLOCK: class 0 = 487 units, median 4.9 ms, 229 waves busy on
             // average, the span of the whole batch): at most 96 blocks of the shortest list per unit
             if (r.and_rs_units && split_ok && nt > 1 && nt <= r.stream_nt_max) parts = std::max(parts, (nb0 + and_unit_blocks - 1) / and_unit_blocks);
-            const uint32_t per = (nb0 + parts - 1) / parts;
-            parts = (nb0 + per - 1) / per;
-            if (parts > 1) b->split_queries.push_back(q);
-            for (uint32_t j = 0; j < parts; ++j) add_unit(b, c, q, j * per, std::min(nb0, (j + 1) * per), parts, qcost[q] / parts);
+            if (taper) {
+                add_tapering_units(b, c, q, nb0, parts, cap_blocks, qcost[q], cut);
+            } else { // parts of ceil(nb0 / parts) blocks each (= unit_cut.hpp's cut at ratio 1, without its boundary vector)
+                const uint32_t per = (nb0 + parts - 1) / parts;
+                parts = (nb0 + per - 1) / per;
+                if (parts > 1) b->split_queries.push_back(q);
+                for (uint32_t j = 0; j < parts; ++j) add_unit(b, c, q, j * per, std::min(nb0, (j + 1) * per), parts, qcost[q] / parts);
+            }
         } else if (r.union_stream && !nt) { // empty query: one unit of an empty virtual query writes the empty answer
             b->voff.push_back((uint32_t)b->vterms.size());
             b->vinfo.push_back(q);
@@ -1419,6 +1459,8 @@ void copy_results(const ds2i_hip_batch* b, uint64_t* out_count, float* out_topk,
     const bool ranked = (b->op & 0xFF) >= DS2I_OP_RANKED_AND;
     if (out_count) std::memcpy(out_count, h + b->o_count, 8 * nq);
     if (out_topk && ranked) std::memcpy(out_topk, h + b->o_topk, 4 * nq * b->k); // and / or have no top-k (k is ignored)
+    if (out_topk && ranked) // (rows no kernel wrote: padded like a written row, with -inf)
+        for (uint32_t q : b->empty_queries) std::fill_n(out_topk + (size_t)q * b->k, b->k, -std::numeric_limits<float>::infinity());
     if (out_topk_len) std::memcpy(out_topk_len, h + b->o_topk_len, 4 * nq);
     if (out_freq_sum) std::memcpy(out_freq_sum, h + b->o_freq_sum, 8 * nq);
 }
