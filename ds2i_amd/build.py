@@ -31,7 +31,7 @@ DEVICE_UNITS = RANKED_UNITS + [("kernels.hip", "kernels.hip", []), ("freq_stream
                                ("freq_encode_kernels.hip", "freq_encode_kernels.hip", []),
                                ("partition_kernels.hip", "partition_kernels.hip", []),
                                ("remap_kernels.hip", "remap_kernels.hip", [])] + DOCS_UNITS
-HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "capi_build.cpp", "capi_encode.cpp", "capi_verify.cpp", "capi_extract.cpp",
+HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "batch_plan.cpp", "capi_build.cpp", "capi_encode.cpp", "capi_verify.cpp", "capi_extract.cpp",
              "capi_remap.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-but-set-variable"]

@@ -1,4 +1,4 @@
-// Shared by the C-ABI translation units (capi.cpp: index handle, capi_batch.cpp: query batches and the
+// Shared by the C-ABI translation units (capi.cpp: index handle, capi_batch.cpp: batch slots and the
 // pipelined submit/wait form): the index handle, RAII device / pinned buffers, error plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 
 #include "../../include/ds2i_hip.h"
 #include "abi_structs.hpp"
+#include "batch_plan.hpp" // NCLS / CLS_LONG / class_of: the kernel classes; PlanIndex
 #include "capi_error.hpp"
 #include "knobs.hpp"
 
@@ -21,13 +22,6 @@
             return ds2i_set_error(DS2I_EDEVICE, m_.c_str());                                       \
         }                                                                                          \
     } while (0)
-
-// Kernel classes by number of distinct query terms: <=2, <=4, <=8, <=16 keep every list's current block in LDS
-// (footprint per wave grows with the class); class 4 ("long", > 16 terms -- the reference has no limit,
-// queries.hpp:35-86) keeps the per-list state in a global scratch area and runs the one-document-per-step traversal.
-static const int NCLS = 5;
-static const int CLS_LONG = 4;
-static inline int class_of(size_t nterms) { return nterms <= 2 ? 0 : nterms <= 4 ? 1 : nterms <= 8 ? 2 : nterms <= 16 ? 3 : 4; }
 
 // grow-only device allocation: a reused batch slot re-allocates only when a batch needs more than any before it
 struct DevBuf {
@@ -115,7 +109,7 @@ struct ds2i_hip_index {
     bool plan_hints = true, plan_slots = true;
     uint64_t table_budget = 0;      // bytes the upload was asked to stay under (0 = no budget)
     std::vector<uint64_t> list_tail_off; // postings in the partial last blocks of all preceding lists
-    // What the kernel families need of the upload, named once (the planner's route, capi_batch.cpp: plan_route):
+    // What the kernel families need of the upload, named once (the planner's route, batch_plan.cpp: plan_route):
     bool d_skip_or_pef() const { return d_skip != nullptr || kind >= DS2I_OPT; } // what the streaming kernels walk the driving list by
     // block_optpfor with its exception side slots, tail table and skip table: what the stream kernels decode a block through
     // (build_side_tables allocates and frees d_xslots and d_tails together, and builds them only over a skip table)
@@ -207,6 +201,28 @@ static inline ds2i_dev::IndexView ds2i_index_view(const ds2i_hip_index* idx) {
     v.xovf = idx->d_xovf;
     v.tails = idx->d_tails;
     return v;
+}
+
+// What planning a batch reads of the index (batch_plan.hpp, PlanIndex): scalars and pointers, no copy of any array
+static inline PlanIndex ds2i_plan_index(const ds2i_hip_index* idx) {
+    PlanIndex ix;
+    ix.kind = idx->kind;
+    ix.num_cus = idx->num_cus;
+    ix.size = idx->size;
+    ix.num_docs = idx->num_docs;
+    ix.has_wand = idx->has_wand;
+    ix.has_bitmaps = idx->has_bitmaps;
+    ix.skip = idx->d_skip != nullptr;
+    ix.bmw = idx->d_bmw != nullptr;
+    ix.rmw = idx->d_rmw != nullptr;
+    ix.side_tables = idx->side_tables();
+    ix.bound_tables = idx->bound_tables();
+    ix.skip_or_pef = idx->d_skip_or_pef();
+    ix.knobs = &idx->knobs;
+    ix.term_proto = idx->term_proto.data();
+    ix.list_n = idx->list_n.data();
+    ix.list_topbmw = idx->list_topbmw.data();
+    return ix;
 }
 
 // The grid of a kernel that takes one wave per block and strides: a wave per block up to 16 per compute unit

@@ -1,6 +1,6 @@
 // host_parallel.hpp -- the one host thread pool of the build side (no HIP): the index builders, the optimiser, the chunk directory of an
 // upload and the planner of the Elias-Fano encoder all run "fn for every list, lists drawn off a counter". (The query path's plan pool,
-// capi_batch.cpp, is a different kind -- persistent threads fed batch after batch -- and does not come through here.)
+// batch_plan.cpp, is a different kind -- persistent threads fed batch after batch -- and does not come through here.)
 #pragma once
 #include <atomic>
 #include <cstdint>

@@ -1,4 +1,4 @@
-// How a conjunctive query is cut into work units along the blocks of its shortest list (capi_batch.cpp, cut_units). Plain C++:
+// How a conjunctive query is cut into work units along the blocks of its shortest list (batch_plan.cpp, cut_units). Plain C++:
 // nothing here knows about HIP, the index or the batch, so that a stand-alone program can check it (tests/unit_cut_check.cpp).
 //
 // Equal cut: `parts` = floor(cost / target), at least 1 and at most one per block; every part ceil(nb0 / parts) blocks, the last one

@@ -1,5 +1,5 @@
-"""The batch dimension: one collection, about 150 distinct queries, and batches of every size at which the planner of
-ds2i_amd/csrc/capi_batch.cpp changes what it does (SIZES), up to LARGE = 36 000 queries, whose list-stream records need a second launch
+"""The batch dimension: one collection, about 150 distinct queries, and batches of every size at which the planner
+(ds2i_amd/csrc/batch_plan.cpp) or the slot (capi_batch.cpp) changes what it does (SIZES), up to LARGE = 36 000 queries, whose list-stream records need a second launch
 slice of 32768 (launch_list_streams). tests/test_batch_size_cases_cpu.py proves that the batches are what they claim,
 tests/test_gpu_batch_sizes.py runs them.
 
@@ -36,7 +36,7 @@ K_MAX = 257
 SLICE = 32768  # terms per launch of k_and_stream / k_freq_stream (launch_list_streams: grid.y is limited)
 LARGE = 36000
 
-# batch sizes, each beside the expression of capi_batch.cpp it straddles
+# batch sizes, each beside the expression of batch_plan.cpp / capi_batch.cpp it straddles
 SIZES = [
     0,     # the `nq == 0` and `nq ? nq : 1` guards (lay_out, copy_results): no query at all
     1,     # ... and the smallest batch there is
