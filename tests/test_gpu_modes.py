@@ -16,148 +16,26 @@ Two collections: a crafted one whose AND / OR sizes straddle every k boundary, w
 (helpers.boundary_collection), and the 20 000-document synthetic one of test_gpu.py with edge-shaped queries. Each runs as two
 batches: the queries of at most 16 terms (the stream kernels take them) and a small batch that adds the queries beyond 16 terms
 (they send the whole batch to the one-document-per-step kernels at k > 64). The oracle reads the block_optpfor image: its
-answers do not depend on the codec."""
+answers do not depend on the codec. The World and the checks live in modes_matrix.py; test_gpu_upload_modes.py runs them over the
+other uploads the planner tells apart."""
 import numpy as np
 import pytest
 
 import ds2i_amd as d
-import oracle as o
-from helpers import Collection, boundary_collection, boundary_queries, edge_queries, queries_for, small_params, topk64
+from modes_matrix import (COLLS, KS, MODES, NCLS, RANKED, RTOL, SEEDED, UNION, UNRANKED, _batch, _check_float64, _check_oracle,  # noqa: F401
+                          _check_structure, _run_mode, _same_bits, _within, close_devices, world)
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-5
-NCLS = 5
-COLLS = ["boundary", "synth"]
 CODECS = ["block_optpfor", "block_mixed", "opt", "block_qmx"]   # block_mixed / opt: transcoded at upload (the default)
 DEVICE_OPTPFOR = ("block_optpfor", "block_mixed", "opt")          # ... so these three run every stream path; block_qmx: M0 only
-KS = [1, 10, 64, 65, 128, 129, 256, 257, 1000, 1024]
 K64 = (1, 65, 257, 1024)
-RANKED = ["ranked_and", "wand", "maxscore", "ranked_or"]
-UNION = ["wand", "maxscore", "ranked_or"]
-UNRANKED = ["and", "and_freq", "or", "or_freq"]
-SEEDED = ("wand", "maxscore", "ranked_or")                         # a ranked_and seed pass runs first at k <= 64
-ORACLE_THREADS = 8
-
-
-class World:
-    """one collection: its query sets, device indexes per codec, and the cached answers of the oracle, of float64 and of M0"""
-
-    def __init__(self, coll, queries):
-        self.coll = coll
-        self.sets = {"short": [q for q in queries if len(set(q)) <= 16]}
-        self.sets["mixed"] = [q for q in queries if len(set(q)) > 16] + self.sets["short"][::7]
-        self.wand = coll.wand_image()
-        self.images = {c: coll.index_image(c) for c in CODECS}
-        self.oidx = o.Index("block_optpfor", self.images["block_optpfor"], self.wand)
-        self._g, self._o, self._m0 = {}, {}, {}
-        self.f64 = {}       # (set, conjunctive) -> (scores float64[nq, 1024] padded with -inf, result sizes)
-        for name, qs in self.sets.items():
-            for conj in (True, False):
-                top = np.full((len(qs), max(KS)), -np.inf)
-                n = np.zeros(len(qs), dtype=np.int64)
-                for i, q in enumerate(qs):
-                    s, n[i] = topk64(coll, q, max(KS), conj)
-                    top[i, :len(s)] = s
-                self.f64[name, conj] = (top, n)
-
-    def gidx(self, codec):
-        if codec not in self._g:
-            self._g[codec] = d.Index(codec, self.images[codec], self.wand)
-        return self._g[codec]
-
-    def oracle(self, op, k, name):
-        key = (op, k if op in RANKED else 1, name)
-        if key not in self._o:
-            self._o[key] = self.oidx.query_batch_mt(op, self.sets[name], k=key[1], threads=ORACLE_THREADS)[:4]
-        return self._o[key]
-
-    def m0(self, codec, op, k, name):
-        """(count, topk, tlen, fsum) of a one-shot Batch, checked against the oracle and the structure once"""
-        key = (codec, op, k if op in RANKED else 1, name)
-        if key not in self._m0:
-            b = _batch(self.gidx(codec), op, self.sets[name], key[2])
-            b.run()
-            got = b.fetch()
-            if op in ("and", "and_freq"):
-                _check_matches(self, b, got[0], name)
-            b.close()
-            _check_oracle(self, op, key[2], name, got)
-            self._m0[key] = got
-        return self._m0[key]
 
 
 @pytest.fixture(scope="module")
 def worlds(built_lib):
-    out = {}
-
-    def get(name):
-        if name not in out:
-            if name == "boundary":
-                coll = boundary_collection()
-                out[name] = World(coll, boundary_queries(coll))
-            else:
-                coll = Collection(small_params(num_docs=20000, num_terms=300))
-                out[name] = World(coll, queries_for(coll, 120) + edge_queries(coll.p.num_terms))
-        return out[name]
-    yield get
-    for w in out.values():
-        for g in w._g.values():
-            g.close()
-
-
-def _batch(gidx, op, qs, k, reference_order=False):
-    return d.Batch(gidx, op, qs, k=k, want_matches=op in ("and", "and_freq"), reference_order=reference_order)
-
-
-def _check_oracle(w, op, k, name, got):
-    count, topk, tlen, fsum = got
-    oc, otopk, otlen, ofsum = w.oracle(op, k, name)
-    assert np.array_equal(count, oc), (op, k, name, np.argwhere(count != oc)[:3])
-    if op.endswith("_freq"):
-        assert np.array_equal(fsum, ofsum), (op, name)
-    if op in RANKED:
-        assert np.array_equal(tlen, otlen), (op, k, name, np.argwhere(tlen != otlen)[:3])
-        f = np.isfinite(otopk)
-        assert np.array_equal(np.isfinite(topk), f) and np.all(np.isneginf(topk[~f])), (op, k, name)
-        bad = ~np.isclose(topk[f], otopk[f], rtol=RTOL, atol=0)
-        assert not bad.any(), (op, k, name, np.argwhere(f)[np.flatnonzero(bad)[:3]])
-
-
-def _check_matches(w, b, count, name):
-    got = b.fetch_matches(count)
-    for i, q in enumerate(w.sets[name]):
-        assert np.array_equal(got[i], w.oidx.query("and", q, want_matches=True)["matches"]), (name, q)
-
-
-def _check_structure(w, op, k, name, got):
-    """no reference needed: rows sorted descending, -inf past the length, length = min(result size, k)"""
-    _, topk, tlen, _ = got
-    _, n = w.f64[name, op == "ranked_and"]
-    assert np.array_equal(tlen, np.minimum(n, k)), (op, k, name, np.argwhere(tlen != np.minimum(n, k))[:3])
-    assert np.all(topk[:, 1:] <= topk[:, :-1]), (op, k, name)
-    assert np.all(np.isfinite(topk) == (np.arange(k)[None, :] < tlen[:, None])), (op, k, name)
-
-
-def _check_float64(w, op, k, name, got):
-    _, topk, tlen, _ = got
-    top, n = w.f64[name, op == "ranked_and"]
-    assert np.array_equal(tlen, np.minimum(n, k))
-    f = np.isfinite(top[:, :k])
-    assert np.array_equal(np.isfinite(topk), f)
-    bad = ~np.isclose(topk[f], top[:, :k][f], rtol=RTOL, atol=0)
-    assert not bad.any(), (op, k, name, np.argwhere(f)[np.flatnonzero(bad)[:3]])
-
-
-def _same_bits(a, b, what):
-    for i, (x, y) in enumerate(zip(a[:3], b[:3])):   # count, topk, tlen
-        assert np.array_equal(x, y), (what, ("count", "topk", "tlen")[i], np.argwhere(x != y)[:3])
-
-
-def _within(a, b, what):
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[2], b[2]), what
-    f = np.isfinite(b[1])
-    assert np.array_equal(np.isfinite(a[1]), f), what
-    assert np.allclose(a[1][f], b[1][f], rtol=RTOL, atol=0), what
+    """the World of a collection (modes_matrix.py: shared with test_gpu_upload_modes.py); this module's device indexes are closed after it"""
+    yield world
+    close_devices()
 
 
 # ---------------------------------------------------------------- M0: a one-shot Batch
@@ -231,52 +109,7 @@ def test_m0_runs_the_stream_kernels_and_m3_none(worlds, coll, k):
         _check_oracle(w, op, k, "short", got)
 
 
-# ---------------------------------------------------------------- M1, M2, M3, M5 against M0
-MODES = ["M1_rerun", "M2_uninstrumented", "M3_profile_before_run", "M3_profile_after_run", "M5_reference_order"]
-
-
-def _profile_totals(w, b, op, k, st, name):
-    """block_profile() column sums against the run's counters. finish_batch returns the counters of the batch's own kernels only
-    (the seed pass's are dropped), while the profile counts every decode -- the seed pass's too (launch_batch hands it the same
-    buffer). So: equal for the operators without a seed pass (and for wand / maxscore / ranked_or beyond 64, which have none);
-    for a seeded batch the difference is the seed pass's, and it is 0 when the seed has no query to answer -- the union kernels
-    leave it only the one-term queries -- which the batch of the multi-term queries checks exactly."""
-    prof = b.block_profile()
-    nd, nf = int(prof[:, 0].sum()), int(prof[:, 1].sum())
-    assert st.docs_blocks_decoded > 0 or not any(len(q) for q in w.sets[name])
-    if op not in SEEDED or k > 64:
-        assert (nd, nf) == (st.docs_blocks_decoded, st.freqs_blocks_decoded), (op, k, name)
-    else:
-        assert nd >= st.docs_blocks_decoded and nf >= st.freqs_blocks_decoded, (op, k, name)
-
-
-def _run_mode(w, codec, op, k, name, mode):
-    qs = w.sets[name]
-    b = _batch(w.gidx(codec), op, qs, k, reference_order=mode == "M5_reference_order")
-    if mode == "M3_profile_before_run":
-        b.enable_block_profile()
-    st = b.run()
-    first = b.fetch()
-    if mode == "M1_rerun":
-        st = b.run()
-        second = b.fetch()
-        _same_bits(second, first, (mode, op, k, name, "run 2 == run 1"))
-    elif mode == "M2_uninstrumented":
-        b.set_instrumented(False)
-        b.run()
-    elif mode == "M3_profile_after_run":
-        b.enable_block_profile()
-        st = b.run()
-    got = b.fetch()
-    if mode.startswith("M3"):
-        _profile_totals(w, b, op, k, st, name)
-        assert not any(g["pipelined_stream"] for c in range(NCLS) for g in b.class_groups(c)), (mode, op, k, name)
-    if op in ("and", "and_freq"):
-        _check_matches(w, b, got[0], name)
-    b.close()
-    return got
-
-
+# ---------------------------------------------------------------- M1, M2, M3, M5 against M0 (MODES, _run_mode: modes_matrix.py)
 @pytest.mark.parametrize("k", KS)
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("codec", DEVICE_OPTPFOR)
