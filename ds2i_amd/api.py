@@ -177,6 +177,12 @@ def lib():
         L.ds2i_hip_remap_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_remap_ms.argtypes = [C.POINTER(C.c_double)]
         L.ds2i_hip_remap_ms.restype = None
+        L.ds2i_merge_postings.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_int, u64p, u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.ds2i_hip_merge_postings.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint64, u64p, u64p, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                              C.POINTER(C.c_double)]
+        L.ds2i_hip_merge_indexes.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_merge_ms.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_merge_ms.restype = None
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -491,6 +497,94 @@ def remap_wand(wand_image, doc_map):
     h = C.c_void_p()
     _check(lib().ds2i_remap_wand(wand_image, len(wand_image), _ptr(m), len(m), C.byref(h)))
     return _take_blob(h)
+
+
+class MergeSource(C.Structure):
+    """ds2i_merge_source (include/ds2i_hip.h)"""
+    _fields_ = [("kind", C.c_int), ("image", C.c_void_p), ("bytes", C.c_size_t), ("doc_map", C.c_void_p), ("map_len", C.c_uint64),
+                ("term_map", C.c_void_p), ("terms_len", C.c_uint64)]
+
+
+class MergePostingsSource(C.Structure):
+    """ds2i_merge_postings_source (include/ds2i_build.h)"""
+    _fields_ = [("num_docs", C.c_uint64), ("nlists", C.c_uint64), ("list_offsets", C.c_void_p), ("docs", C.c_void_p), ("freqs", C.c_void_p),
+                ("doc_map", C.c_void_p), ("map_len", C.c_uint64), ("term_map", C.c_void_p), ("terms_len", C.c_uint64)]
+
+
+def _merge_maps(src, rest, keep):
+    """fills the map fields of one source from its optional (doc_map, term_map); `keep` holds the arrays while the call runs"""
+    maps = [None if m is None else _u32(m) for m in rest] + [None, None]
+    keep.extend(maps[:2])
+    for name, length, m in (("doc_map", "map_len", maps[0]), ("term_map", "terms_len", maps[1])):
+        setattr(src, name, None if m is None else m.ctypes.data)
+        setattr(src, length, 0 if m is None else len(m))
+
+
+def _merge_postings_sources(sources):
+    """sources: iterable of (num_docs, lists[, doc_map[, term_map]]) -> (array of MergePostingsSource, what it points into)"""
+    sources = list(sources)
+    arr, keep = (MergePostingsSource * max(1, len(sources)))(), []
+    for src, (num_docs, lists, *rest) in zip(arr, sources):
+        n, offs, docs, freqs = _csr(lists)
+        keep.extend((offs, docs, freqs))
+        src.num_docs, src.nlists, src.list_offsets, src.docs, src.freqs = num_docs, n, offs.ctypes.data, docs.ctypes.data, freqs.ctypes.data
+        _merge_maps(src, rest, keep)
+    return arr, len(sources), keep
+
+
+def _take_merged(n, v, ho, hd, hf):
+    offs, docs, freqs = (np.frombuffer(_take_blob(h), dtype=t) for h, t in ((ho, np.uint64), (hd, np.uint32), (hf, np.uint32)))
+    return n.value, [(docs[int(offs[t]):int(offs[t + 1])], freqs[int(offs[t]):int(offs[t + 1])]) for t in range(v.value)]
+
+
+def merge_postings(sources, num_terms=None, threads=0):
+    """Collections merged into one ON THE HOST (ds2i_merge_postings), the host twin of gpu_merge_postings. sources: iterable of
+    (num_docs, lists[, doc_map[, term_map]]); doc_map gives the merged doc-id of each of the source's documents (None: after the
+    documents of the earlier sources; all maps together a permutation of all documents), term_map the merged term of each of its lists
+    (strictly increasing; None: the same term). num_terms: the merged number of lists (None: the smallest that holds every mapped
+    term); every term must receive a list. Returns (num_docs, merged lists): each the union of the mapped postings sent to its term,
+    sorted by doc-id with the freqs."""
+    arr, nsrc, keep = _merge_postings_sources(sources)
+    n, v = C.c_uint64(), C.c_uint64()
+    ho, hd, hf = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(lib().ds2i_merge_postings(arr, nsrc, num_terms or 0, threads, C.byref(n), C.byref(v), C.byref(ho), C.byref(hd), C.byref(hf)))
+    return _take_merged(n, v, ho, hd, hf)
+
+
+def _merge_info(ms):
+    parts = (C.c_double * 8)()
+    lib().ds2i_hip_merge_ms(parts)
+    return {"device_ms": ms.value, "extract_ms": parts[0], "place_ms": parts[1], "sort_ms": parts[2], "encode_ms": parts[3]}
+
+
+def gpu_merge_postings(sources, num_terms=None, device=0):
+    """merge_postings ON THE GPU (ds2i_hip_merge_postings): every source copied up and placed among the merged postings by one kernel,
+    then, unless the doc maps together are the identity, the segmented sort of gpu_remap_postings; the same lists, element for element.
+    Returns (num_docs, merged lists, dict(device_ms, place_ms, sort_ms, ...))."""
+    arr, nsrc, keep = _merge_postings_sources(sources)
+    n, v, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+    ho, hd, hf = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    _check(lib().ds2i_hip_merge_postings(device, arr, nsrc, num_terms or 0, C.byref(n), C.byref(v), C.byref(ho), C.byref(hd), C.byref(hf),
+                                         C.byref(ms)))
+    return _take_merged(n, v, ho, hd, hf) + (_merge_info(ms),)
+
+
+def gpu_merge_indexes(sources, to_kind, num_terms=None, device=0):
+    """Index images merged into one image of `to_kind` (a kind gpu_encode_index writes) ON THE GPU (ds2i_hip_merge_indexes). sources:
+    iterable of (kind, image[, doc_map[, term_map]]), each of any of the nine kinds, the maps as merge_postings takes them. Every source
+    in turn is extracted, placed among the merged postings and freed; the merged lists are sorted unless the doc maps together are the
+    identity, and encoded where they lie: byte-identical to build_index(to_kind, ...) over merge_postings' lists. An index holds no
+    wand data and none is merged: build it from the merged document sizes (gpu_build_wand).
+    Returns (image bytes, dict(device_ms, extract_ms, place_ms, sort_ms, encode_ms))."""
+    sources = list(sources)
+    arr, keep = (MergeSource * max(1, len(sources)))(), []
+    for src, (kind, image, *rest) in zip(arr, sources):
+        keep.append(image)
+        src.kind, src.image, src.bytes = _codec(kind), C.cast(C.c_char_p(image), C.c_void_p), len(image)
+        _merge_maps(src, rest, keep)
+    h, ms = C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_merge_indexes(device, arr, len(sources), num_terms or 0, _codec(to_kind), C.byref(h), C.byref(ms)))
+    return _take_blob(h), _merge_info(ms)
 
 
 def synth_build_gpu(p, device=0, threads=0):

@@ -466,4 +466,21 @@ struct RemapArgs {
     uint32_t* flag;                 // set by the map kernel when a doc-id lies outside the map
 };
 
+// ---- merge_kernels.hip: the postings of ONE source of a merge stored where the host plan (host_merge.hpp, merge_plan) puts them among
+// the merged postings, every doc-id through the source's map or with the source's base added. A wavefront takes a window of
+// MERGE_WINDOW consecutive source postings at a time.
+constexpr uint32_t MERGE_WINDOW = 1024; // 16 postings a lane
+struct MergePlaceArgs {
+    const uint32_t *src_docs, *src_freqs; // the source as extracted: `postings` of them
+    uint32_t *dst_docs, *dst_freqs;       // the merged postings
+    const uint64_t* src_first;            // nlists + 1 posting offsets of the source, from 0
+    const uint64_t* dst_first;            // nlists: where each source list's run starts among the merged postings
+    const uint32_t* doc_map;              // map_len entries, or null: base + old doc-id
+    uint64_t map_len;                     // the source's number of documents
+    uint64_t postings;
+    uint32_t base;
+    uint32_t nlists;                      // >= 1 when there is a posting
+    uint32_t* flag;                       // set when a doc-id lies at or past map_len (that posting is not stored)
+};
+
 } // namespace ds2i_dev

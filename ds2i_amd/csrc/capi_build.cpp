@@ -14,6 +14,7 @@
 #include "host_index.hpp"
 #include "host_pef.hpp"
 #include "host_hybrid.hpp"
+#include "host_merge.hpp"
 #include "host_parallel.hpp"
 #include "host_remap.hpp"
 #include "host_synth.hpp"
@@ -212,6 +213,38 @@ int ds2i_remap_wand(const void* wand_image, size_t bytes, const uint32_t* doc_ma
     std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
     remap_wand(w, doc_map, blob->data);
     *out = blob.release();
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_merge_postings(const ds2i_merge_postings_source* src, uint32_t nsrc, uint64_t nlists, int threads, uint64_t* num_docs, uint64_t* out_nlists,
+                        ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs) {
+    if (!num_docs || !out_nlists || !list_offsets || !docs || !freqs) return ds2i_set_error(DS2I_EINVAL, "ds2i_merge_postings: null argument");
+    DS2I_TRY
+    std::vector<merge_shape> shapes;
+    merge_plan plan;
+    std::string fault = merge_csr_fault("ds2i_merge_postings", src, nsrc, shapes);
+    if (fault.empty()) fault = merge_plan_fault("ds2i_merge_postings", shapes.data(), nsrc, nlists, plan);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    threads = std::min(threads, 16);
+    std::vector<const uint32_t*> d(nsrc), f(nsrc);
+    for (uint32_t s = 0; s < nsrc; ++s) {
+        d[s] = src[s].docs;
+        f[s] = src[s].freqs;
+    }
+    const uint64_t total = plan.offs[plan.nlists];
+    std::unique_ptr<ds2i_blob> bo(new ds2i_blob), bd(new ds2i_blob), bf(new ds2i_blob);
+    bo->data.resize(8 * (plan.nlists + 1));
+    std::memcpy(bo->data.data(), plan.offs.data(), 8 * (plan.nlists + 1));
+    bd->data.resize(4 * total);
+    bf->data.resize(4 * total);
+    merge_postings(shapes.data(), d.data(), f.data(), nsrc, plan, (uint32_t*)bd->data.data(), (uint32_t*)bf->data.data(), (unsigned)threads);
+    *num_docs = plan.num_docs;
+    *out_nlists = plan.nlists;
+    *list_offsets = bo.release();
+    *docs = bd.release();
+    *freqs = bf.release();
     return 0;
     DS2I_CATCH
 }

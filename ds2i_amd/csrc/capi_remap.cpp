@@ -99,7 +99,7 @@ int ds2i_remap_device_postings(const char* who, int device, uint64_t num_docs, u
     RemapArgs a{};
     uint32_t* d_map = nullptr;
     uint64_t* d_first = nullptr;
-    if (dev.alloc(&d_map, 4 * num_docs) != hipSuccess || dev.alloc(&d_first, 8 * (nlists + 1)) != hipSuccess || dev.alloc(&a.flag, 4) != hipSuccess)
+    if ((doc_map && dev.alloc(&d_map, 4 * num_docs) != hipSuccess) || dev.alloc(&d_first, 8 * (nlists + 1)) != hipSuccess || dev.alloc(&a.flag, 4) != hipSuccess)
         return nomem();
     int rc = upload(dev, &a.lists1, plan.lists1);
     if (rc == DS2I_OK) rc = upload(dev, &a.lists2, plan.lists2);
@@ -111,7 +111,7 @@ int ds2i_remap_device_postings(const char* who, int device, uint64_t num_docs, u
     if (radix && (hipMalloc((void**)&second.docs, 4 * total) != hipSuccess || hipMalloc((void**)&second.freqs, 4 * total) != hipSuccess ||
                   dev.alloc(&a.hist, (4ull << REMAP_DIGIT) * plan.tiles.size()) != hipSuccess))
         return nomem();
-    HIP_OK(hipMemcpy(d_map, doc_map, 4 * num_docs, hipMemcpyHostToDevice));
+    if (doc_map) HIP_OK(hipMemcpy(d_map, doc_map, 4 * num_docs, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(d_first, offs, 8 * (nlists + 1), hipMemcpyHostToDevice));
     HIP_OK(hipMemset(a.flag, 0, 4));
     // class 3 sorts the key bits the largest doc-id needs, REMAP_DIGIT a pass; an odd number of passes ends in the second pair
@@ -141,10 +141,12 @@ int ds2i_remap_device_postings(const char* who, int device, uint64_t num_docs, u
     const unsigned grid1 = (unsigned)std::min<uint64_t>((a.nlists1 + 3) / 4, narrow);
     const unsigned grid2 = (unsigned)std::min<uint64_t>(a.nlists2, narrow);
     const unsigned grid3 = (unsigned)std::min<uint64_t>(a.ntiles, wide);
-    HIP_OK(timed_span(s, ms[0], [&] { return ds2i_launch_remap_map(a, grid_map, s); }));
-    uint32_t flag = 0;
-    HIP_OK(hipMemcpy(&flag, a.flag, 4, hipMemcpyDeviceToHost));
-    if (flag) return ds2i_set_error(DS2I_EFORMAT, (std::string(who) + ": a doc-id of the postings lies outside the map").c_str());
+    if (doc_map) { // (no map: the postings hold their new doc-ids already, as a merge leaves them, and only the sort runs)
+        HIP_OK(timed_span(s, ms[0], [&] { return ds2i_launch_remap_map(a, grid_map, s); }));
+        uint32_t flag = 0;
+        HIP_OK(hipMemcpy(&flag, a.flag, 4, hipMemcpyDeviceToHost));
+        if (flag) return ds2i_set_error(DS2I_EFORMAT, (std::string(who) + ": a doc-id of the postings lies outside the map").c_str());
+    }
     if (a.nlists1) HIP_OK(timed_span(s, ms[1], [&] { return ds2i_launch_remap_sort1(a, grid1, s); }));
     if (a.nlists2) HIP_OK(timed_span(s, ms[2], [&] { return ds2i_launch_remap_sort2(a, grid2, s); }));
     if (radix)

@@ -146,7 +146,8 @@ int ds2i_convert_image(const char* who, int device, int from_kind, const void* i
 // sort's second pair, and whichever pair is not the result has been freed, with every table of the sort, before this returns.
 // While it runs: 16 bytes per posting when a list is longer than a workgroup sorts (else 8), 4 per document, 8 per list.
 // A doc-id >= num_docs among the postings is DS2I_EFORMAT (nothing is read past the map). ms[0 .. 3] receive the hipEvent
-// milliseconds of the map kernel and of sort classes 1, 2 and 3.
+// milliseconds of the map kernel and of sort classes 1, 2 and 3. A null doc_map skips the map kernel and its 4 bytes per document: the
+// postings hold their new doc-ids already (all < num_docs) and only the sort runs -- what a merge asks for (capi_merge.cpp).
 int ds2i_remap_device_postings(const char* who, int device, uint64_t num_docs, uint64_t nlists, const uint64_t* offs, DevPostings& dp,
                                const uint32_t* doc_map, double ms[4]);
 

@@ -80,4 +80,7 @@ hipError_t ds2i_launch_remap_map(const ds2i_dev::RemapArgs& a, unsigned grid, hi
 hipError_t ds2i_launch_remap_sort1(const ds2i_dev::RemapArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_remap_sort2(const ds2i_dev::RemapArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_remap_radix_pass(const ds2i_dev::RemapArgs& a, int from_second, uint32_t shift, unsigned grid, hipStream_t s);
+// ---- merge_kernels.hip: one source of a merge placed among the merged postings. grid: workgroups of 256 threads whose wavefronts
+// stride over the windows of MERGE_WINDOW source postings
+hipError_t ds2i_launch_merge_place(const ds2i_dev::MergePlaceArgs& a, unsigned grid, hipStream_t s);
 }

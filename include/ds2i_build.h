@@ -107,6 +107,31 @@ int ds2i_remap_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list
                         const uint32_t* doc_map, int threads);
 int ds2i_remap_wand(const void* wand_image, size_t bytes, const uint32_t* doc_map, uint64_t num_docs, ds2i_blob** out);
 
+/* Merging collections: nsrc >= 1 sources become one. Source s holds num_docs documents and nlists lists in the CSR form of
+ * ds2i_opt_partition (empty lists are allowed) and optionally two maps. doc_map (map_len == num_docs entries) gives the merged doc-id
+ * of each of its documents; NULL: base + old doc-id, base the documents of the earlier sources. The maps, defaults filled in and
+ * concatenated in source order, must be a permutation of all documents (what ds2i_check_doc_map checks). term_map (terms_len == nlists
+ * entries, strictly increasing, < the merged number of lists) gives the merged term of each of its lists; NULL: the identity. The
+ * merged list of a term is the union of the mapped postings of every source list sent to it, sorted by doc-id, the freqs travelling
+ * with their postings; doc-ids are distinct across sources, so it is unique. Every merged term must receive a list.
+ * merge_postings: the host twin of ds2i_hip_merge_postings (ds2i_hip.h). nlists: the merged number of lists; 0: the smallest that holds
+ * every mapped term. Checks, all DS2I_EINVAL, in this order: null arguments and the offsets; no source; 2^32 documents or lists; a map
+ * of the wrong length; the concatenated doc maps; a term map that does not increase or leaves the merged lists; the first merged
+ * term that receives no list ("List must be nonempty", as the builders say). A doc-id >= num_docs among a source's postings is
+ * DS2I_EFORMAT. Out: *num_docs, list_offsets u64[*out_nlists + 1], docs / freqs u32[postings]; free each with ds2i_blob_free; on an
+ * error nothing is written. At most 16 host threads (threads <= 0: up to 16). */
+typedef struct ds2i_merge_postings_source {
+    uint64_t num_docs, nlists;
+    const uint64_t* list_offsets;
+    const uint32_t *docs, *freqs;
+    const uint32_t* doc_map;
+    uint64_t map_len;
+    const uint32_t* term_map;
+    uint64_t terms_len;
+} ds2i_merge_postings_source;
+int ds2i_merge_postings(const ds2i_merge_postings_source* src, uint32_t nsrc, uint64_t nlists, int threads, uint64_t* num_docs,
+                        uint64_t* out_nlists, ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs);
+
 /* The chunk directory ds2i_hip_index_open builds for one list of an opt image (inspection / test hook):
  * cmax = u32[nchunks] last doc-id per chunk, chunks = nchunks x 12 dwords (ds2i_amd/csrc/device_pef.hpp),
  * info = {n, docs_bit0, freqs_bit0, docs bit-vector byte offset in the image, freqs bit-vector byte offset} */

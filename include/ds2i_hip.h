@@ -442,6 +442,43 @@ int ds2i_hip_remap_index(int device, int from_kind, const void* image, size_t by
  * ms[1 .. 3] sort classes 1, 2 and 3, ms[4] the extraction and ms[5] the encoder (both 0 for ds2i_hip_remap_postings). */
 void ds2i_hip_remap_ms(double ms[6]);
 
+/* Merging indexes on the GPU: nsrc >= 1 images (any of the nine kinds, each its own) become the image of to_kind of the merged
+ * collection, byte-identical to the host builder's over ds2i_merge_postings' lists (ds2i_build.h, the host twin, which states the
+ * semantics of the two maps: doc_map NULL = base + old doc-id, term_map NULL = the identity). nlists: the merged number of lists;
+ * 0: the smallest that holds every mapped term.
+ *
+ * ds2i_hip_merge_indexes. Checks, in this order, all before a device is looked for: null arguments and nsrc == 0 (DS2I_EINVAL), the
+ * kinds (to_kind as ds2i_hip_convert_index takes it: DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL, same message, before any
+ * image is read), the host parse of every image (DS2I_EFORMAT), then the twin's checks of the maps (DS2I_EINVAL), then the device.
+ * The host plans, from the list lengths alone, where every source list's run starts inside its merged list (runs lie in source
+ * order). Then each source in turn: bare upload, extraction, the image closed, one placement kernel that reads the source's postings
+ * coalesced and stores each at its place with its doc-id mapped, the source's postings freed. A doc-id at or past a source's map
+ * is found by that kernel, which reads nothing past the map: DS2I_EFORMAT. If the concatenated doc maps are not the identity every
+ * merged list is sorted by the segmented sort of ds2i_hip_remap_postings; with all-default maps nothing is sorted and no second buffer
+ * pair is allocated. Then the encoder over the postings where they lie. Peak device memory: the merged postings (8 bytes each) plus
+ * one source's image and postings, then the sort's or the encoder's. What does not fit is DS2I_ENOMEM with everything released.
+ * An index holds no wand data and none is merged. device_ms: extraction + placement + sort + encoder.
+ *
+ * ds2i_hip_merge_postings: the same placement and sort over sources in CSR form on the host; the merged collection comes back as
+ * ds2i_merge_postings returns it, element for element. Checks: the twin's, then the device. */
+typedef struct ds2i_merge_source {
+    int kind;
+    const void* image;
+    size_t bytes;
+    const uint32_t* doc_map;
+    uint64_t map_len;
+    const uint32_t* term_map;
+    uint64_t terms_len;
+} ds2i_merge_source;
+typedef struct ds2i_merge_postings_source ds2i_merge_postings_source; /* ds2i_build.h */
+int ds2i_hip_merge_indexes(int device, const ds2i_merge_source* src, uint32_t nsrc, uint64_t nlists, int to_kind, ds2i_blob** out_image,
+                           double* device_ms);
+int ds2i_hip_merge_postings(int device, const ds2i_merge_postings_source* src, uint32_t nsrc, uint64_t nlists, uint64_t* num_docs,
+                            uint64_t* out_nlists, ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs, double* device_ms);
+/* Diagnostic: the hipEvent milliseconds of this thread's last merge: ms[0] the extractions, ms[1] the placement kernels, ms[2] sort
+ * classes 1 to 3 summed, ms[3] the encoder (ms[0] and ms[3] are 0 for ds2i_hip_merge_postings); ms[4 .. 7] are 0. */
+void ds2i_hip_merge_ms(double ms[4 + 4]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
