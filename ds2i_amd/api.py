@@ -183,6 +183,19 @@ def lib():
         L.ds2i_hip_merge_indexes.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(vp), C.POINTER(C.c_double)]
         L.ds2i_hip_merge_ms.argtypes = [C.POINTER(C.c_double)]
         L.ds2i_hip_merge_ms.restype = None
+        L.ds2i_split_postings.argtypes = [C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint32, C.c_int, C.POINTER(vp)]
+        L.ds2i_split_free.argtypes = [vp, C.c_uint32]
+        L.ds2i_split_free.restype = None
+        L.ds2i_hip_split_postings.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, vp, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_split_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_uint64, C.c_uint32, C.c_int, C.POINTER(vp),
+                                           C.POINTER(C.c_double)]
+        L.ds2i_hip_image_shape.argtypes = [C.c_int, vp, C.c_size_t, u64p, u64p]
+        L.ds2i_hip_split_ms.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_split_ms.restype = None
+        L.ds2i_hip_split_window.argtypes = []
+        L.ds2i_hip_split_window.restype = C.c_uint32
+        L.ds2i_hip_split_grid_waves.argtypes = [C.c_uint32]
+        L.ds2i_hip_split_grid_waves.restype = C.c_uint32
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -585,6 +598,119 @@ def gpu_merge_indexes(sources, to_kind, num_terms=None, device=0):
     h, ms = C.c_void_p(), C.c_double()
     _check(lib().ds2i_hip_merge_indexes(device, arr, len(sources), num_terms or 0, _codec(to_kind), C.byref(h), C.byref(ms)))
     return _take_blob(h), _merge_info(ms)
+
+
+DROP = 0xFFFFFFFF  # DS2I_SPLIT_DROP (include/ds2i_build.h): the shard_of value that deletes a document
+
+
+class SplitShard(C.Structure):
+    """ds2i_split_shard (include/ds2i_build.h)"""
+    _fields_ = [("num_docs", C.c_uint64), ("nlists", C.c_uint64), ("doc_map", C.c_void_p), ("term_map", C.c_void_p),
+                ("list_offsets", C.c_void_p), ("docs", C.c_void_p), ("freqs", C.c_void_p), ("image", C.c_void_p)]
+
+
+def _shard_of(shard_of, nshards):
+    """(shard_of as uint32, nshards; None: the largest shard number plus one)"""
+    m = _u32(shard_of)
+    if nshards is None:
+        live = m[m != DROP]
+        nshards = int(live.max()) + 1 if len(live) else 1
+    return m, nshards
+
+
+def _copy_blob(handle, dtype=None):
+    """a blob's bytes (or array); the blob stays its owner's"""
+    L = lib()
+    n = L.ds2i_blob_size(handle)
+    raw = (C.c_char * n).from_address(L.ds2i_blob_data(handle)).raw if n else b""
+    return raw if dtype is None else np.frombuffer(raw, dtype=dtype)
+
+
+def _take_shards(handle, nshards, images):
+    """the shards of a ds2i_split_shard array as tuples, the array freed"""
+    try:
+        arr = C.cast(handle, C.POINTER(SplitShard))
+        out = []
+        for s in range(nshards):
+            sh = arr[s]
+            maps = (_copy_blob(sh.doc_map, np.uint32), _copy_blob(sh.term_map, np.uint32))
+            if images:
+                out.append((_copy_blob(sh.image),) + maps)
+                continue
+            offs, docs, freqs = (_copy_blob(h, t) for h, t in ((sh.list_offsets, np.uint64), (sh.docs, np.uint32), (sh.freqs, np.uint32)))
+            lists = [(docs[int(offs[t]):int(offs[t + 1])], freqs[int(offs[t]):int(offs[t + 1])]) for t in range(sh.nlists)]
+            out.append((int(sh.num_docs), lists) + maps)
+        return out
+    finally:
+        lib().ds2i_split_free(handle, nshards)
+
+
+def image_shape(kind, image):
+    """(num_docs, number of lists) of an index image from its host parse alone (ds2i_hip_image_shape): no device is needed"""
+    n, v = C.c_uint64(), C.c_uint64()
+    _check(lib().ds2i_hip_image_shape(_codec(kind), image, len(image), C.byref(n), C.byref(v)))
+    return n.value, v.value
+
+
+def split_window():
+    """the postings of one window of the device split as compiled (ds2i_hip_split_window): a wavefront takes a window at a time"""
+    return lib().ds2i_hip_split_window()
+
+
+def split_grid_waves(compute_units):
+    """the most wavefronts one launch of the device split has on a device of that many compute units (ds2i_hip_split_grid_waves); they
+    stride over the windows"""
+    return lib().ds2i_hip_split_grid_waves(compute_units)
+
+
+def split_postings(num_docs, lists, shard_of, nshards=None, threads=0):
+    """A collection cut into shards by documents ON THE HOST (ds2i_split_postings), the inverse of merge_postings and the host twin of
+    gpu_split_postings. shard_of[d] is the shard of document d, or DROP to delete it; nshards=None: the largest shard number plus one.
+    The documents of a shard keep their order (local id = rank among them), lists with no posting in a shard are dropped from it, and
+    nothing is sorted. Returns a list of (num_docs, lists, doc_map, term_map), one per shard: what merge_postings takes as sources.
+    doc_map gives the old id of every local document, term_map the old term of every list. Wand data is not split: build a shard's from
+    sizes[doc_map] (gpu_build_wand); scores over a shard use the shard's own statistics."""
+    m, nshards = _shard_of(shard_of, nshards)
+    if len(m) != num_docs:
+        raise ValueError("shard_of holds %d entries for %d documents" % (len(m), num_docs))
+    n, offs, docs, freqs = _csr(lists)
+    h = C.c_void_p()
+    _check(lib().ds2i_split_postings(num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), _ptr(m), nshards, threads, C.byref(h)))
+    return _take_shards(h, nshards, False)
+
+
+def _split_info(ms):
+    parts = (C.c_double * 8)()
+    lib().ds2i_hip_split_ms(parts)
+    return {"device_ms": ms.value, "extract_ms": parts[0], "count_ms": parts[1], "offsets_ms": parts[2], "scatter_ms": parts[3],
+            "encode_ms": parts[4]}
+
+
+def gpu_split_postings(num_docs, lists, shard_of, nshards=None, device=0):
+    """split_postings ON THE GPU (ds2i_hip_split_postings): the collection copied up once, then per shard a count kernel, the scan of
+    the window counts on the host, a scatter kernel and an offsets kernel; the same shards, element for element.
+    Returns ([(num_docs, lists, doc_map, term_map), ...], dict(device_ms, count_ms, offsets_ms, scatter_ms, ...))."""
+    m, nshards = _shard_of(shard_of, nshards)
+    if len(m) != num_docs:
+        raise ValueError("shard_of holds %d entries for %d documents" % (len(m), num_docs))
+    n, offs, docs, freqs = _csr(lists)
+    h, ms = C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_split_postings(device, num_docs, n, _ptr(offs), _ptr(docs), _ptr(freqs), _ptr(m), nshards, C.byref(h), C.byref(ms)))
+    return _take_shards(h, nshards, False), _split_info(ms)
+
+
+def gpu_split_index(kind, image, shard_of, nshards=None, to_kind=None, device=0):
+    """An index image of `kind` (any of the nine) cut into shards by documents ON THE GPU (ds2i_hip_split_index), each an image of
+    `to_kind` (a kind gpu_encode_index writes; None: `kind`): extracted once, every shard in turn compacted out of the postings and
+    encoded where it lies; every image byte-identical to build_index(to_kind, ...) over split_postings' lists. Every shard must be
+    assigned a document and receive a posting. Returns ([(image, doc_map, term_map), ...], dict(device_ms, extract_ms, count_ms,
+    offsets_ms, scatter_ms, encode_ms)): with the kind in front, what gpu_merge_indexes takes as sources. An index holds no wand data
+    and none is split: build a shard's from sizes[doc_map] (gpu_build_wand)."""
+    m, nshards = _shard_of(shard_of, nshards)
+    h, ms = C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_split_index(device, _codec(kind), image, len(image), _ptr(m), len(m), nshards,
+                                      _codec(kind if to_kind is None else to_kind), C.byref(h), C.byref(ms)))
+    return _take_shards(h, nshards, True), _split_info(ms)
 
 
 def synth_build_gpu(p, device=0, threads=0):
@@ -1015,6 +1141,11 @@ class Index:
         """The image this index was opened from with its documents renumbered, as an image of `to_kind` (None: the same kind), on
         this index's device (gpu_remap_index). Returns (image bytes, dict(device_ms, ...)); open it with remap_wand's wand data."""
         return gpu_remap_index(self.kind, self._image, doc_map, to_kind, device=self.device)
+
+    def split(self, shard_of, nshards=None, to_kind=None):
+        """The image this index was opened from cut into shards by documents, as images of `to_kind` (None: the same kind), on this
+        index's device (gpu_split_index). Returns ([(image, doc_map, term_map), ...], dict(device_ms, ...))."""
+        return gpu_split_index(self.kind, self._image, shard_of, nshards, to_kind, device=self.device)
 
     def calibration_read(self):
         n = C.c_uint64()

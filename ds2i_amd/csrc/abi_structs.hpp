@@ -483,4 +483,30 @@ struct MergePlaceArgs {
     uint32_t* flag;                       // set when a doc-id lies at or past map_len (that posting is not stored)
 };
 
+// ---- split_kernels.hip: ONE shard of a split cut out of the source postings. The shard's postings are the stable compaction of the
+// source postings by the flag shard_of[doc-id] == shard; the source is cut into windows of SPLIT_WINDOW consecutive postings, a
+// wavefront takes a window at a time, and the host scans the windows' counts between the count kernel and the other two.
+constexpr uint32_t SPLIT_WINDOW = 1024; // 16 postings a lane
+constexpr uint32_t SPLIT_THREADS = 256; // four wavefronts a workgroup
+// the workgroups of a launch over `items` wavefronts' worth of work (windows, or list starts): up to 8 a compute unit, which stride
+inline unsigned split_grid(uint64_t items, int cus) {
+    const uint64_t groups = (items + SPLIT_THREADS / 64 - 1) / (SPLIT_THREADS / 64), cap = 8ull * (uint64_t)(cus > 0 ? cus : 1);
+    return (unsigned)(groups < cap ? groups : cap);
+}
+struct SplitArgs {
+    const uint32_t *src_docs, *src_freqs; // the source as extracted: `postings` of them
+    uint64_t postings;
+    const uint32_t* shard_of;             // num_docs entries; gathered, never read at or past num_docs
+    const uint32_t* local;                // num_docs entries: the local id of every document in its shard (scatter)
+    uint64_t num_docs;
+    uint32_t shard;
+    uint64_t nstarts;                     // offsets: the source's nlists + 1 list starts
+    uint32_t* win_count;                  // count: the kept postings of every window
+    const uint64_t* win_base;             // offsets, scatter: windows + 1 values, the exclusive scan of win_count and its total
+    const uint64_t* src_first;            // offsets: nstarts posting offsets of the source, from 0 to `postings`
+    uint64_t* kept_before;                // offsets: nstarts values, the shard's postings before every source list start
+    uint32_t *dst_docs, *dst_freqs;       // scatter: the shard's postings, win_base[windows] of them
+    uint32_t* flag;                       // count: set when a doc-id lies at or past num_docs
+};
+
 } // namespace ds2i_dev

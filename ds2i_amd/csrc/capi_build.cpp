@@ -10,6 +10,7 @@
 #include "capi_error.hpp"
 #include "capi_hybrid.hpp"
 #include "capi_partition.hpp"
+#include "capi_split.hpp"
 #include "host_encode.hpp"
 #include "host_index.hpp"
 #include "host_pef.hpp"
@@ -247,6 +248,35 @@ int ds2i_merge_postings(const ds2i_merge_postings_source* src, uint32_t nsrc, ui
     *freqs = bf.release();
     return 0;
     DS2I_CATCH
+}
+
+int ds2i_split_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                        const uint32_t* shard_of, uint32_t nshards, int threads, ds2i_split_shard** shards) {
+    static const char* const who = "ds2i_split_postings";
+    if (!list_offsets || !docs || !freqs || (!shard_of && num_docs) || !shards) return ds2i_set_error(DS2I_EINVAL, "ds2i_split_postings: null argument");
+    DS2I_TRY
+    std::string fault = split_csr_fault(who, nlists, list_offsets);
+    if (fault.empty()) fault = split_assign_fault(who, num_docs, nlists, shard_of, nshards);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    threads = std::min(threads, 16);
+    std::vector<split_shard> out;
+    split_postings(num_docs, nlists, list_offsets, docs, freqs, shard_of, nshards, (unsigned)threads, out);
+    SplitShards arr = new_split_shards(nshards);
+    for (uint32_t s = 0; s < nshards; ++s) {
+        fill_split_shard(arr.get()[s], out[s], true);
+        out[s] = split_shard(); // (a shard's vectors go as soon as its blobs stand)
+    }
+    *shards = arr.release();
+    return 0;
+    DS2I_CATCH
+}
+
+void ds2i_split_free(ds2i_split_shard* shards, uint32_t nshards) {
+    if (!shards) return;
+    for (uint32_t s = 0; s < nshards; ++s)
+        for (ds2i_blob* b : {shards[s].doc_map, shards[s].term_map, shards[s].list_offsets, shards[s].docs, shards[s].freqs, shards[s].image}) delete b;
+    delete[] shards;
 }
 
 int ds2i_opt_list_directory(const void* opt_image, size_t bytes, uint32_t term, ds2i_blob** cmax, ds2i_blob** chunks,

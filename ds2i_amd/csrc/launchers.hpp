@@ -83,4 +83,10 @@ hipError_t ds2i_launch_remap_radix_pass(const ds2i_dev::RemapArgs& a, int from_s
 // ---- merge_kernels.hip: one source of a merge placed among the merged postings. grid: workgroups of 256 threads whose wavefronts
 // stride over the windows of MERGE_WINDOW source postings
 hipError_t ds2i_launch_merge_place(const ds2i_dev::MergePlaceArgs& a, unsigned grid, hipStream_t s);
+// ---- split_kernels.hip: one shard of a split. grid: workgroups of SPLIT_THREADS threads whose wavefronts stride over the windows of
+// SPLIT_WINDOW source postings (count, scatter) or over the source's list starts (offsets). count: a.win_count and a.flag; the host
+// scans the counts into a.win_base; offsets: a.kept_before; scatter: the shard's postings with their local doc-ids
+hipError_t ds2i_launch_split_count(const ds2i_dev::SplitArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_split_offsets(const ds2i_dev::SplitArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_split_scatter(const ds2i_dev::SplitArgs& a, unsigned grid, hipStream_t s);
 }

@@ -90,7 +90,7 @@ int ds2i_opt_partition(uint64_t num_docs, uint64_t nlists, const uint64_t* list_
                        ds2i_blob** docs_ends, ds2i_blob** docs_offs, ds2i_blob** freqs_ends, ds2i_blob** freqs_offs);
 
 /* Renumbering the documents of a collection: new doc-id = doc_map[old doc-id], doc_map a permutation of [0, num_docs). Deleting
- * documents (a map that drops ids) is not offered. The device forms, ds2i_hip_remap_postings and ds2i_hip_remap_index, are in ds2i_hip.h.
+ * documents (a map that drops ids) is ds2i_split_postings' work, below. The device forms, ds2i_hip_remap_postings and ds2i_hip_remap_index, are in ds2i_hip.h.
  * check_doc_map: DS2I_OK, or DS2I_EINVAL with ds2i_hip_last_error() naming the FIRST offending old doc-id: one whose value is
  * >= num_docs, or the second document sent to an id already taken. One bit per document; every entry point that takes a map runs it
  * before anything else is done with the map, and before any device is touched.
@@ -131,6 +131,36 @@ typedef struct ds2i_merge_postings_source {
 } ds2i_merge_postings_source;
 int ds2i_merge_postings(const ds2i_merge_postings_source* src, uint32_t nsrc, uint64_t nlists, int threads, uint64_t* num_docs,
                         uint64_t* out_nlists, ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs);
+
+/* Splitting a collection by documents, the inverse of a merge: shards and deletions. The collection holds num_docs documents and nlists
+ * lists in the CSR form of ds2i_opt_partition (empty lists are allowed). shard_of[d] (num_docs entries) is the shard of document d,
+ * < nshards, or DS2I_SPLIT_DROP to delete the document. Shard s holds the documents d with shard_of[d] == s in increasing old id: the
+ * local id of a document is its rank among them, and doc_map (u32[num_docs of the shard], strictly increasing) gives the old id of each.
+ * A list survives in a shard if at least one of its postings lies in a document of the shard; surviving lists keep their relative
+ * order, and term_map (u32[nlists of the shard], strictly increasing) gives the old term of each. The surviving postings of a list
+ * keep their order, carry their local doc-ids and keep their freqs. Local ids preserve the order of the old ones, so nothing is
+ * sorted; a caller who wants another order remaps the shard afterwards. doc_map and term_map are the maps ds2i_merge_postings and
+ * ds2i_hip_merge_indexes take: with no document dropped and every input list nonempty, merging the shards with them gives the input
+ * back. A shard may come back with no documents or with no lists.
+ * Not split: wand data (an index holds none, and a shard's max_term_weight depends on the shard's own average document length: build
+ * it from sizes[doc_map] with ds2i_hip_build_wand), and scores (BM25 over a shard uses the shard's own number of documents and document
+ * frequencies: shard scores are not the global ones).
+ * split_postings: the host twin of ds2i_hip_split_postings (ds2i_hip.h). Checks, all DS2I_EINVAL, in this order: null arguments and the
+ * offsets; nshards == 0; 2^32 documents or lists; the first document whose shard_of is neither < nshards nor the drop value (named). A
+ * doc-id >= num_docs among the postings is DS2I_EFORMAT. Out: *shards = an array of nshards ds2i_split_shard whose members are blobs
+ * (doc_map, term_map u32; list_offsets u64[nlists + 1]; docs / freqs u32[postings]; image is NULL here: it is ds2i_hip_split_index's);
+ * free the array and all its blobs with one ds2i_split_free. On an error nothing is written. Lists are spread over at most 16 host
+ * threads (threads <= 0: up to 16); every shard costs one pass over the postings. */
+#define DS2I_SPLIT_DROP 0xFFFFFFFFu
+typedef struct ds2i_split_shard {
+    uint64_t num_docs, nlists;
+    ds2i_blob *doc_map, *term_map;
+    ds2i_blob *list_offsets, *docs, *freqs; /* the postings forms; NULL from ds2i_hip_split_index */
+    ds2i_blob* image;                       /* ds2i_hip_split_index; NULL from the postings forms */
+} ds2i_split_shard;
+int ds2i_split_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
+                        const uint32_t* shard_of, uint32_t nshards, int threads, ds2i_split_shard** shards);
+void ds2i_split_free(ds2i_split_shard* shards, uint32_t nshards);
 
 /* The chunk directory ds2i_hip_index_open builds for one list of an opt image (inspection / test hook):
  * cmax = u32[nchunks] last doc-id per chunk, chunks = nchunks x 12 dwords (ds2i_amd/csrc/device_pef.hpp),

@@ -479,6 +479,55 @@ int ds2i_hip_merge_postings(int device, const ds2i_merge_postings_source* src, u
  * classes 1 to 3 summed, ms[3] the encoder (ms[0] and ms[3] are 0 for ds2i_hip_merge_postings); ms[4 .. 7] are 0. */
 void ds2i_hip_merge_ms(double ms[4 + 4]);
 
+/* Splitting an index on the GPU, the inverse of a merge: an image becomes nshards >= 1 images, one per shard of its documents, each with
+ * the doc map and the term map that ds2i_hip_merge_indexes takes. shard_of[d] is the shard of document d, < nshards, or
+ * DS2I_SPLIT_DROP (ds2i_build.h) to delete the document. ds2i_split_postings (ds2i_build.h, the host twin) states the semantics:
+ * order-preserving local doc-ids, lists without a posting in the shard dropped, nothing sorted. With no document dropped, merging the
+ * shards with their maps gives the input back, byte for byte when the kinds agree. Neither wand data nor scores are split: an index
+ * holds no wand data, and a shard's max_term_weight depends on the shard's own average document length; build it from
+ * sizes[doc_map] with ds2i_hip_build_wand. BM25 over a shard uses the shard's own number of documents and document frequencies.
+ *
+ * A shard's postings are the stable compaction of the source postings by the flag shard_of[doc-id] == shard. The source postings are
+ * cut into windows of ds2i_hip_split_window() postings. Per shard: a count kernel (kept postings per window, a ballot and a popcount
+ * per 64 postings), the exclusive scan of the window counts on the host (u64), a scatter kernel (a wavefront walks a window from its
+ * scanned position; doc-ids become local ids through a table computed once on the host) and an offsets kernel (the kept postings
+ * before every source list start; lists whose two consecutive values are equal vanish). A launch has at most
+ * ds2i_hip_split_grid_waves(compute units) wavefronts, which stride over the windows. Each shard costs one more read of the source
+ * postings; there is no single pass for all shards.
+ *
+ * ds2i_hip_split_index: an image of from_kind (any of the nine) in, *shards = nshards ds2i_split_shard out (num_docs, nlists, image,
+ * doc_map, term_map; free with ds2i_split_free): every image is byte-identical to the host builder's image of to_kind over the twin's
+ * lists for that shard. Checks, in this order, all before a device is looked for: null arguments and nshards == 0 (DS2I_EINVAL), the
+ * kinds (to_kind as ds2i_hip_convert_index takes it: DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL, same message, before the
+ * image is read), the host parse of the image (DS2I_EFORMAT), map_len == the image's number of documents, the values of shard_of (the
+ * first that is neither a shard nor the drop value is named), the first shard that is assigned no document (DS2I_EINVAL), then the
+ * device. Then: bare upload, extraction, the image closed, shard_of and the local ids uploaded once, and every shard in turn: count,
+ * scan, buffers of exactly the shard's size, scatter, offsets, the encoder over the postings where they lie (it frees them). A shard
+ * that has documents but receives no posting is found when it is counted: DS2I_EINVAL ("List must be nonempty", the shard named),
+ * everything released, no output written. The source postings are freed after the last shard. Peak device memory: the source postings
+ * (8 bytes each; the image beside them while extracting) plus 8 bytes per document, 16 per list and 12 per window, plus one shard's
+ * postings and the encoder's. What does not fit is DS2I_ENOMEM with everything released. device_ms: extraction + count + offsets +
+ * scatter + encoder.
+ *
+ * ds2i_hip_split_postings: the same kernels over a collection in CSR form on the host; the shards come back as ds2i_split_postings
+ * returns them, element for element (a shard may hold no document or no list). Checks: the twin's, then the device. A doc-id >=
+ * num_docs among the postings is found by the count kernel, which never reads past shard_of: DS2I_EFORMAT, no output written. */
+typedef struct ds2i_split_shard ds2i_split_shard; /* ds2i_build.h */
+/* The number of documents and of lists of an image, from the host parse alone (what ds2i_hip_split_index checks map_len against): no
+ * device is looked for. A caller that cuts doc-id ranges needs it to write shard_of. Null arguments and an unknown kind are DS2I_EINVAL,
+ * an image that does not parse DS2I_EFORMAT; on an error nothing is written. */
+int ds2i_hip_image_shape(int index_kind, const void* image, size_t bytes, uint64_t* num_docs, uint64_t* nlists);
+uint32_t ds2i_hip_split_window(void);
+uint32_t ds2i_hip_split_grid_waves(uint32_t compute_units);
+int ds2i_hip_split_index(int device, int from_kind, const void* image, size_t bytes, const uint32_t* shard_of, uint64_t map_len,
+                         uint32_t nshards, int to_kind, ds2i_split_shard** shards, double* device_ms);
+int ds2i_hip_split_postings(int device, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs,
+                            const uint32_t* freqs, const uint32_t* shard_of, uint32_t nshards, ds2i_split_shard** shards, double* device_ms);
+/* Diagnostic: the hipEvent milliseconds of this thread's last split, summed over its shards: ms[0] the extraction, ms[1] the count
+ * kernels, ms[2] the offsets kernels, ms[3] the scatter kernels, ms[4] the encoder (ms[0] and ms[4] are 0 for
+ * ds2i_hip_split_postings); ms[5 .. 7] are 0. */
+void ds2i_hip_split_ms(double ms[8]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
