@@ -196,6 +196,16 @@ def lib():
         L.ds2i_hip_split_window.restype = C.c_uint32
         L.ds2i_hip_split_grid_waves.argtypes = [C.c_uint32]
         L.ds2i_hip_split_grid_waves.restype = C.c_uint32
+        L.ds2i_invert_documents.argtypes = [C.c_uint64, vp, vp, C.c_uint64, C.c_int] + [C.POINTER(vp)] * 4
+        L.ds2i_transpose_postings.argtypes = [C.c_uint64, C.c_uint64, vp, vp, vp, C.c_int] + [C.POINTER(vp)] * 3
+        L.ds2i_hip_invert_postings.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_uint64] + [C.POINTER(vp)] * 4 + [C.POINTER(C.c_double)]
+        L.ds2i_hip_transpose_postings.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp] + [C.POINTER(vp)] * 3 + [C.POINTER(C.c_double)]
+        L.ds2i_hip_invert_documents.argtypes = [C.c_int, C.c_int, C.c_uint64, vp, vp, C.c_uint64] + [C.POINTER(vp)] * 4 + [C.POINTER(C.c_double)]
+        L.ds2i_hip_forward_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, u64p, u64p] + [C.POINTER(vp)] * 3 + [C.POINTER(C.c_double)]
+        L.ds2i_hip_invert_ms.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_invert_ms.restype = None
+        L.ds2i_hip_invert_window.argtypes = []
+        L.ds2i_hip_invert_window.restype = C.c_uint32
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -713,6 +723,123 @@ def gpu_split_index(kind, image, shard_of, nshards=None, to_kind=None, device=0)
     return _take_shards(h, nshards, True), _split_info(ms)
 
 
+def invert_window():
+    """the tokens of one window of the device inversion as compiled (ds2i_hip_invert_window): a wavefront takes a window at a time"""
+    return lib().ds2i_hip_invert_window()
+
+
+def _forward(docs):
+    """documents as a list of u32 arrays, or as (doc_offsets, tokens) -> (num_docs, doc_offsets uint64[num_docs + 1], tokens uint32)"""
+    if isinstance(docs, tuple) and len(docs) == 2:
+        offs, tokens = np.ascontiguousarray(docs[0], dtype=np.uint64), _u32(docs[1])
+    else:
+        docs = [_u32(d) for d in docs]
+        offs = np.zeros(len(docs) + 1, dtype=np.uint64)
+        if docs:
+            offs[1:] = np.cumsum([len(d) for d in docs], dtype=np.uint64)
+        tokens = np.concatenate(docs) if docs else np.zeros(0, np.uint32)
+    if len(offs) < 1:
+        raise ValueError("doc_offsets holds no value")
+    if len(tokens) < int(offs.max()):
+        raise ValueError("doc_offsets reach %d, past the %d tokens" % (int(offs.max()), len(tokens)))
+    if not len(tokens):
+        tokens = np.zeros(1, np.uint32)  # (a pointer the library may check against NULL)
+    return len(offs) - 1, offs, tokens
+
+
+def _take_csr(handles):
+    """(offsets uint64, ids uint32, values uint32[, more uint32 arrays]) of the blobs a CSR result comes back in"""
+    return tuple(np.frombuffer(_take_blob(h), dtype=np.uint64 if i == 0 else np.uint32) for i, h in enumerate(handles))
+
+
+def invert_documents(docs, nterms, threads=0):
+    """Documents inverted into posting lists ON THE HOST (ds2i_invert_documents), the host twin of gpu_invert_postings. docs: a list of
+    uint32 arrays of term ids < nterms (in any order, with repeats; empty documents are allowed), or (doc_offsets, tokens). Returns
+    (list_offsets uint64[nterms + 1], docs uint32, freqs uint32, doc_sizes uint32[num_docs]): list t holds the documents in which term
+    t occurs, strictly increasing, freq = its count in the document; terms that never occur have empty lists; doc_sizes are the token
+    counts."""
+    n, offs, tokens = _forward(docs)
+    h = [C.c_void_p() for _ in range(4)]
+    _check(lib().ds2i_invert_documents(n, _ptr(offs), _ptr(tokens), nterms, threads, *[C.byref(x) for x in h]))
+    return _take_csr(h)
+
+
+def transpose_postings(nrows, ncols, row_offsets, cols, vals, threads=0):
+    """A CSR matrix (column ids strictly increasing within every row and < ncols, one uint32 value per entry) transposed ON THE HOST
+    (ds2i_transpose_postings), the host twin of gpu_transpose_postings. Returns (col_offsets uint64[ncols + 1], rows uint32, vals uint32),
+    the row ids strictly increasing within every column. The transpose of posting lists is the forward index, and back."""
+    offs, c, v = np.ascontiguousarray(row_offsets, dtype=np.uint64), _u32(cols), _u32(vals)
+    if len(offs) != nrows + 1 or len(c) != len(v) or len(c) < int(offs.max()):
+        raise ValueError("row_offsets holds %d values for %d rows, over %d columns and %d values" % (len(offs), nrows, len(c), len(v)))
+    if not len(c):
+        c = v = np.zeros(1, np.uint32)
+    h = [C.c_void_p() for _ in range(3)]
+    _check(lib().ds2i_transpose_postings(nrows, ncols, _ptr(offs), _ptr(c), _ptr(v), threads, *[C.byref(x) for x in h]))
+    return _take_csr(h)
+
+
+INVERT_MS = ("check_ms", "doc_sort_ms", "count_ms", "scatter_ms", "transpose_ms", "column_sort_ms", "extract_ms", "encode_ms")
+
+
+def _invert_info(ms):
+    parts = (C.c_double * 8)()
+    lib().ds2i_hip_invert_ms(parts)
+    info = {"device_ms": ms.value}
+    info.update(zip(INVERT_MS, parts))
+    return info
+
+
+def gpu_invert_postings(docs, nterms, device=0):
+    """invert_documents ON THE GPU (ds2i_hip_invert_postings): the tokens checked, sorted within their documents, run-length compacted
+    into the canonical forward index and transposed; the same arrays, element for element. Returns ((list_offsets, docs, freqs,
+    doc_sizes), dict(device_ms, check_ms, doc_sort_ms, count_ms, scatter_ms, transpose_ms, column_sort_ms, ...))."""
+    n, offs, tokens = _forward(docs)
+    h, ms = [C.c_void_p() for _ in range(4)], C.c_double()
+    _check(lib().ds2i_hip_invert_postings(device, n, _ptr(offs), _ptr(tokens), nterms, *[C.byref(x) for x in h], C.byref(ms)))
+    return _take_csr(h), _invert_info(ms)
+
+
+def gpu_transpose_postings(nrows, ncols, row_offsets, cols, vals, device=0):
+    """transpose_postings ON THE GPU (ds2i_hip_transpose_postings): a histogram of the columns, a scatter through one cursor per
+    column, and the segmented sort of gpu_remap_postings over the columns; the same arrays, element for element.
+    Returns ((col_offsets, rows, vals), dict(device_ms, transpose_ms, column_sort_ms, ...))."""
+    offs, c, v = np.ascontiguousarray(row_offsets, dtype=np.uint64), _u32(cols), _u32(vals)
+    if len(offs) != nrows + 1 or len(c) != len(v) or len(c) < int(offs.max()):
+        raise ValueError("row_offsets holds %d values for %d rows, over %d columns and %d values" % (len(offs), nrows, len(c), len(v)))
+    if not len(c):
+        c = v = np.zeros(1, np.uint32)
+    h, ms = [C.c_void_p() for _ in range(3)], C.c_double()
+    _check(lib().ds2i_hip_transpose_postings(device, nrows, ncols, _ptr(offs), _ptr(c), _ptr(v), *[C.byref(x) for x in h], C.byref(ms)))
+    return _take_csr(h), _invert_info(ms)
+
+
+def gpu_invert_documents(kind, docs, nterms, wand=True, device=0):
+    """Documents indexed ON THE GPU (ds2i_hip_invert_documents): inverted as gpu_invert_postings does and encoded where the postings
+    lie, with the wand data from the same staging. kind: a kind gpu_encode_index writes. Terms that never occur get no list: term_map
+    (uint32, strictly increasing) gives the old term of every list of the image, the map gpu_merge_indexes takes; doc_sizes are the
+    token counts. The image is byte-identical to build_index(kind, ...) over invert_documents' nonempty lists, the wand image (None
+    with wand=False) to build_wand over them with doc_sizes.
+    Returns ((image, wand, term_map, doc_sizes), dict(device_ms, check_ms, doc_sort_ms, count_ms, scatter_ms, transpose_ms,
+    column_sort_ms, encode_ms, ...))."""
+    n, offs, tokens = _forward(docs)
+    hi, hw, ht, hs, ms = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_invert_documents(device, _codec(kind), n, _ptr(offs), _ptr(tokens), nterms, C.byref(hi), C.byref(hw) if wand else None,
+                                           C.byref(ht), C.byref(hs), C.byref(ms)))
+    return (_take_blob(hi), _take_blob(hw) if wand else None, np.frombuffer(_take_blob(ht), dtype=np.uint32),
+            np.frombuffer(_take_blob(hs), dtype=np.uint32)), _invert_info(ms)
+
+
+def gpu_forward_index(kind, image, device=0):
+    """The forward index of an index image of `kind` (any of the nine) ON THE GPU (ds2i_hip_forward_index): extracted in one launch
+    and transposed. Document d holds the terms (list numbers) terms[doc_offsets[d]:doc_offsets[d + 1]], strictly increasing, with
+    their freqs beside them. Returns ((num_docs, nterms, doc_offsets uint64[num_docs + 1], terms uint32, freqs uint32),
+    dict(device_ms, extract_ms, transpose_ms, column_sort_ms, ...))."""
+    n, v, ms = C.c_uint64(), C.c_uint64(), C.c_double()
+    h = [C.c_void_p() for _ in range(3)]
+    _check(lib().ds2i_hip_forward_index(device, _codec(kind), image, len(image), C.byref(n), C.byref(v), *[C.byref(x) for x in h], C.byref(ms)))
+    return (n.value, v.value) + _take_csr(h), _invert_info(ms)
+
+
 def synth_build_gpu(p, device=0, threads=0):
     """The synthetic collection as a block_optpfor index encoded on the GPU (ds2i_hip_synth_encode).
     -> (index image, wand image, postings, dict(generate_s, device_ms))"""
@@ -1146,6 +1273,11 @@ class Index:
         """The image this index was opened from cut into shards by documents, as images of `to_kind` (None: the same kind), on this
         index's device (gpu_split_index). Returns ([(image, doc_map, term_map), ...], dict(device_ms, ...))."""
         return gpu_split_index(self.kind, self._image, shard_of, nshards, to_kind, device=self.device)
+
+    def forward(self):
+        """The forward index of the image this index was opened from, on this index's device (gpu_forward_index).
+        Returns ((num_docs, nterms, doc_offsets, terms, freqs), dict(device_ms, ...))."""
+        return gpu_forward_index(self.kind, self._image, device=self.device)
 
     def calibration_read(self):
         n = C.c_uint64()

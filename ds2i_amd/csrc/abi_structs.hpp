@@ -509,4 +509,33 @@ struct SplitArgs {
     uint32_t* flag;                       // count: set when a doc-id lies at or past num_docs
 };
 
+// ---- invert_kernels.hip: documents (sequences of term ids) inverted into posting lists, and the primitive behind it, the transposition
+// of a sparse matrix in CSR form. Both work in windows of INVERT_WINDOW consecutive tokens or entries, a wavefront a window at a time, in
+// workgroups of SPLIT_THREADS threads on split_grid's grids.
+constexpr uint32_t INVERT_WINDOW = 1024; // 16 tokens a lane
+constexpr uint32_t INVERT_DOC_START = 2; // the payload of a document's first token once the mark kernel has run (every other token's is 1)
+struct InvertArgs {
+    uint32_t *keys, *vals;          // n tokens and their payloads: staged (1), sorted within the documents, marked (INVERT_DOC_START)
+    uint64_t n;
+    uint64_t nterms;                // stage: a token at or past it raises flag
+    const uint64_t* doc_first;      // mark, offsets: ndocs + 1 token offsets, from 0 to n
+    uint64_t ndocs;
+    uint32_t* win_count;            // count: the run heads of every window
+    const uint64_t* win_base;       // offsets, scatter: windows + 1 values, the exclusive scan of win_count and its total
+    uint64_t* heads_before;         // offsets: ndocs + 1 values, the entries before every document start
+    uint32_t *dst_terms, *dst_freqs; // scatter: win_base[windows] entries; dst_freqs arrives zero-filled
+    uint32_t* flag;
+};
+struct TransposeArgs {
+    const uint32_t *cols, *vals;    // n entries in row order
+    uint64_t n;
+    const uint64_t* row_first;      // nrows + 1 entry offsets, from 0 to n
+    uint32_t nrows;                 // >= 1 when there is an entry
+    uint64_t ncols;
+    uint32_t* count;                // ncols words, zero-filled before either kernel: the histogram (count), the cursors (scatter)
+    const uint64_t* col_first;      // scatter: ncols + 1 values, the exclusive scan of the histogram and its total
+    uint32_t *out_rows, *out_vals;  // scatter: n entries, column by column, in no order within a column
+    uint32_t* flag;                 // count: a column at or past ncols, or a row whose columns do not strictly increase
+};
+
 } // namespace ds2i_dev

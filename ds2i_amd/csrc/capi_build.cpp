@@ -13,6 +13,7 @@
 #include "capi_split.hpp"
 #include "host_encode.hpp"
 #include "host_index.hpp"
+#include "host_invert.hpp"
 #include "host_pef.hpp"
 #include "host_hybrid.hpp"
 #include "host_merge.hpp"
@@ -277,6 +278,47 @@ void ds2i_split_free(ds2i_split_shard* shards, uint32_t nshards) {
     for (uint32_t s = 0; s < nshards; ++s)
         for (ds2i_blob* b : {shards[s].doc_map, shards[s].term_map, shards[s].list_offsets, shards[s].docs, shards[s].freqs, shards[s].image}) delete b;
     delete[] shards;
+}
+
+int ds2i_invert_documents(uint64_t num_docs, const uint64_t* doc_offsets, const uint32_t* tokens, uint64_t nterms, int threads, ds2i_blob** list_offsets,
+                          ds2i_blob** docs, ds2i_blob** freqs, ds2i_blob** doc_sizes) {
+    static const char* const who = "ds2i_invert_documents";
+    if (!doc_offsets || !tokens || !list_offsets || !docs || !freqs || !doc_sizes) return ds2i_set_error(DS2I_EINVAL, "ds2i_invert_documents: null argument");
+    DS2I_TRY
+    const std::string fault = invert_shape_fault(who, num_docs, nterms, doc_offsets);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    threads = std::min(threads, 16);
+    csr_matrix lists;
+    std::vector<uint32_t> sizes;
+    invert_documents(who, num_docs, doc_offsets, tokens, nterms, (unsigned)threads, lists, sizes);
+    std::unique_ptr<ds2i_blob> bo(ds2i_blob_of(lists.offs)), bd(ds2i_blob_of(lists.ids)), bf(ds2i_blob_of(lists.vals)), bs(ds2i_blob_of(sizes));
+    *list_offsets = bo.release();
+    *docs = bd.release();
+    *freqs = bf.release();
+    *doc_sizes = bs.release();
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_transpose_postings(uint64_t nrows, uint64_t ncols, const uint64_t* row_offsets, const uint32_t* cols, const uint32_t* vals, int threads,
+                            ds2i_blob** col_offsets, ds2i_blob** rows, ds2i_blob** out_vals) {
+    static const char* const who = "ds2i_transpose_postings";
+    if (!row_offsets || !cols || !vals || !col_offsets || !rows || !out_vals) return ds2i_set_error(DS2I_EINVAL, "ds2i_transpose_postings: null argument");
+    DS2I_TRY
+    const std::string fault = transpose_shape_fault(who, nrows, ncols, row_offsets);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    threads = std::min(threads, 16);
+    check_columns(who, nrows, ncols, row_offsets, cols, (unsigned)threads);
+    csr_matrix t;
+    transpose_csr(nrows, ncols, row_offsets, cols, vals, (unsigned)threads, t);
+    std::unique_ptr<ds2i_blob> bo(ds2i_blob_of(t.offs)), br(ds2i_blob_of(t.ids)), bv(ds2i_blob_of(t.vals));
+    *col_offsets = bo.release();
+    *rows = br.release();
+    *out_vals = bv.release();
+    return 0;
+    DS2I_CATCH
 }
 
 int ds2i_opt_list_directory(const void* opt_image, size_t bytes, uint32_t term, ds2i_blob** cmax, ds2i_blob** chunks,

@@ -537,6 +537,12 @@ int ds2i_check_encoder_kind(const char* who, int index_kind) {
 
 int ds2i_encode_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                                 uint32_t* d_docs, uint32_t* d_freqs, ds2i_blob** image, double* device_ms) {
+    return ds2i_build_device_postings(who, device, index_kind, num_docs, nlists, list_offsets, d_docs, d_freqs, nullptr, image, nullptr, device_ms);
+}
+
+int ds2i_build_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                               uint32_t* d_docs, uint32_t* d_freqs, const uint32_t* doc_sizes, ds2i_blob** image, ds2i_blob** wand_image,
+                               double* device_ms) {
     DS2I_TRY
     freq_plan_ms = 0.0;
     EncStage st;
@@ -557,7 +563,16 @@ int ds2i_encode_device_postings(const char* who, int device, int index_kind, uin
     } else {
         STAGE_OK(encode_staged(st, codec, num_docs, &ib, ms));
     }
-    *image = ib;
+    std::unique_ptr<ds2i_blob> index_blob(ib), wand_blob;
+    if (wand_image) { // the wand data over the same staging, as build_images makes it
+        std::vector<float> norm_lens, max_w;
+        ds2i_host::compute_norm_lens(doc_sizes, num_docs, norm_lens);
+        STAGE_OK(wand_max_staged(st, norm_lens, max_w, ms));
+        wand_blob.reset(new ds2i_blob);
+        ds2i_host::wand_freeze(norm_lens, max_w, wand_blob->data);
+        *wand_image = wand_blob.release();
+    }
+    *image = index_blob.release();
     if (device_ms) *device_ms = ms;
     return DS2I_OK;
     DS2I_CATCH

@@ -19,22 +19,14 @@ inline SplitShards new_split_shards(uint32_t nshards) {
     return SplitShards(new ds2i_split_shard[nshards](), SplitShardsFree{nshards}); // (all members zero)
 }
 
-template <class T>
-ds2i_blob* split_blob(std::vector<T> const& v) {
-    std::unique_ptr<ds2i_blob> b(new ds2i_blob);
-    const uint8_t* p = (const uint8_t*)v.data();
-    b->data.assign(p, p + sizeof(T) * v.size());
-    return b.release();
-}
-
 // the shape and the two maps of a shard; postings: its lists too (the CSR forms)
 inline void fill_split_shard(ds2i_split_shard& out, ds2i_host::split_shard const& sh, bool postings) {
     out.num_docs = sh.num_docs;
     out.nlists = sh.nlists;
-    out.doc_map = split_blob(sh.doc_map);
-    out.term_map = split_blob(sh.term_map);
+    out.doc_map = ds2i_blob_of(sh.doc_map);
+    out.term_map = ds2i_blob_of(sh.term_map);
     if (!postings) return;
-    out.list_offsets = split_blob(sh.offs);
-    out.docs = split_blob(sh.docs);
-    out.freqs = split_blob(sh.freqs);
+    out.list_offsets = ds2i_blob_of(sh.offs);
+    out.docs = ds2i_blob_of(sh.docs);
+    out.freqs = ds2i_blob_of(sh.freqs);
 }

@@ -159,3 +159,9 @@ int ds2i_remap_device_postings(const char* who, int device, uint64_t num_docs, u
 int ds2i_check_encoder_kind(const char* who, int index_kind);
 int ds2i_encode_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
                                 uint32_t* d_docs, uint32_t* d_freqs, ds2i_blob** image, double* device_ms);
+// build_device_postings: the same, and from the same staging the wand_data image over doc_sizes (num_docs lengths, num_docs >= 1)
+// when wand_image is not null, as ds2i_hip_build_collection makes both from one upload: every doc-id must be < num_docs. Neither output
+// is written unless both succeed.
+int ds2i_build_device_postings(const char* who, int device, int index_kind, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets,
+                               uint32_t* d_docs, uint32_t* d_freqs, const uint32_t* doc_sizes, ds2i_blob** image, ds2i_blob** wand_image,
+                               double* device_ms);

@@ -89,4 +89,15 @@ hipError_t ds2i_launch_merge_place(const ds2i_dev::MergePlaceArgs& a, unsigned g
 hipError_t ds2i_launch_split_count(const ds2i_dev::SplitArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_split_offsets(const ds2i_dev::SplitArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_split_scatter(const ds2i_dev::SplitArgs& a, unsigned grid, hipStream_t s);
+// ---- invert_kernels.hip. grid: workgroups of SPLIT_THREADS threads. stage: every payload 1, a.flag for a token >= a.nterms (threads
+// stride over the tokens); mark: the payload of every document's first token INVERT_DOC_START (threads stride over the documents);
+// count / scatter: wavefronts stride over the windows of INVERT_WINDOW sorted tokens; offsets: over the ndocs + 1 document starts.
+// transpose_count / transpose_scatter: wavefronts stride over the windows of INVERT_WINDOW entries
+hipError_t ds2i_launch_invert_stage(const ds2i_dev::InvertArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_invert_mark(const ds2i_dev::InvertArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_invert_count(const ds2i_dev::InvertArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_invert_scatter(const ds2i_dev::InvertArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_invert_offsets(const ds2i_dev::InvertArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_transpose_count(const ds2i_dev::TransposeArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_transpose_scatter(const ds2i_dev::TransposeArgs& a, unsigned grid, hipStream_t s);
 }

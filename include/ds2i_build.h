@@ -162,6 +162,29 @@ int ds2i_split_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list
                         const uint32_t* shard_of, uint32_t nshards, int threads, ds2i_split_shard** shards);
 void ds2i_split_free(ds2i_split_shard* shards, uint32_t nshards);
 
+/* Indexing documents: a forward collection inverted into posting lists, and the primitive behind it, the transposition of a sparse
+ * matrix in CSR form. The host twins of ds2i_hip_invert_postings and ds2i_hip_transpose_postings (ds2i_hip.h), which return the same
+ * arrays element for element.
+ * A forward collection holds num_docs documents in CSR form: document d is tokens[doc_offsets[d] .. doc_offsets[d + 1]), each token a
+ * term id < nterms, in any order, with repeats (what a tokenizer emits). Empty documents are allowed. num_docs and nterms are < 2^32 and
+ * a document has < 2^32 tokens.
+ * invert_documents: for every term t < nterms the documents that hold t: doc-ids strictly increasing, freq = the number of times t
+ * occurs in the document; terms that never occur have empty lists. Out, as blobs: list_offsets u64[nterms + 1], docs / freqs
+ * u32[postings], doc_sizes u32[num_docs] = every document's token count (the ds2i .sizes value). It is the canonical form of the
+ * documents (every document's tokens sorted, equal neighbours turned into one (term, freq) entry) transposed.
+ * transpose_postings: a CSR matrix of nrows rows whose column ids are strictly increasing within each row and < ncols, with one u32
+ * value per entry, becomes the CSR of its transpose: col_offsets u64[ncols + 1], rows / out_vals u32[entries], the row ids strictly
+ * increasing within each column and the values travelling along. transpose(transpose(x)) == x; the forward index of a collection
+ * (every document's terms and freqs) is the transpose of its posting lists.
+ * Checks, all DS2I_EINVAL, in this order: null arguments and the offsets (not starting at 0, or decreasing); 2^32 documents or terms
+ * (rows or columns), or more; a document (row) of 2^32 tokens (entries) or more. Then a token >= nterms, or a column >= ncols or not
+ * above its left neighbour in the row, is DS2I_EFORMAT and the message names the first offender. On an error nothing is written. The
+ * work is spread over at most 16 host threads (threads <= 0: up to 16). */
+int ds2i_invert_documents(uint64_t num_docs, const uint64_t* doc_offsets, const uint32_t* tokens, uint64_t nterms, int threads,
+                          ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs, ds2i_blob** doc_sizes);
+int ds2i_transpose_postings(uint64_t nrows, uint64_t ncols, const uint64_t* row_offsets, const uint32_t* cols, const uint32_t* vals, int threads,
+                            ds2i_blob** col_offsets, ds2i_blob** rows, ds2i_blob** out_vals);
+
 /* The chunk directory ds2i_hip_index_open builds for one list of an opt image (inspection / test hook):
  * cmax = u32[nchunks] last doc-id per chunk, chunks = nchunks x 12 dwords (ds2i_amd/csrc/device_pef.hpp),
  * info = {n, docs_bit0, freqs_bit0, docs bit-vector byte offset in the image, freqs bit-vector byte offset} */

@@ -528,6 +528,64 @@ int ds2i_hip_split_postings(int device, uint64_t num_docs, uint64_t nlists, cons
  * ds2i_hip_split_postings); ms[5 .. 7] are 0. */
 void ds2i_hip_split_ms(double ms[8]);
 
+/* Indexing documents on the GPU: a forward collection (documents as sequences of term ids, what a tokenizer emits) inverted into posting
+ * lists or into an index image, and the same operation run the other way, the forward index of an image. Both are one primitive, the
+ * transposition of a sparse matrix in CSR form. ds2i_invert_documents and ds2i_transpose_postings (ds2i_build.h, the host twins) state
+ * the semantics; every answer is unique and the device returns the twins' arrays element for element.
+ *
+ * The plan. (1) The tokens are copied up and staged as keys with a payload of 1; the stage kernel flags a token >= nterms, which is
+ * DS2I_EFORMAT with nothing written. (2) Every document is sorted by the segmented sort of ds2i_hip_remap_postings (segments = the
+ * documents, key bound = nterms). (3) Run-length compaction in windows of ds2i_hip_invert_window() tokens: an entry starts wherever the
+ * term differs from the previous token's or a document starts; a count kernel (a ballot and a popcount per 64 tokens), the scan of the
+ * window counts on the host (u64), a scatter kernel that writes (term, freq = the run's length; a run may span any number of windows)
+ * and an offsets kernel (the entries before every document start) give the forward index in canonical form. (4) The transposition: a
+ * histogram of the columns, its scan on the host, a scatter that takes each entry's place from a per-column cursor with a returning
+ * atomic add, and the segmented sort again (segments = the columns, key bound = nrows) to put every column in row order. All adds to
+ * one column's cursor serialise: a term present in every document costs one returning add per document on one word. (5) The encoder and
+ * the wand kernel over the postings where they lie, from one staging, as ds2i_hip_build_collection; the Elias-Fano kinds come down once
+ * for the host planner, as in a conversion. No kernel waits for another workgroup; a launch has at most ds2i_hip_split_grid_waves(compute
+ * units) wavefronts, which stride over the windows.
+ *
+ * Device memory: 8 bytes per token while sorting the documents, 16 if any document is longer than the class-2 bound of
+ * ds2i_hip_remap_class_bounds; then the tokens beside the forward entries (8 bytes each) and 16 bytes per document and 12 per window of
+ * tables; then the forward entries beside the transposed entries (8 bytes each) and 8 bytes per row and 12 per column; then the
+ * transposed entries and the second sort's scratch (8 bytes per entry more if a list is longer than the class-2 bound); then the
+ * encoder's. What does not fit is DS2I_ENOMEM with everything released. There is no chunked form.
+ *
+ * Checks of every entry point, in the twins' order, all before anything is staged: null arguments and the offsets; 2^32 documents or
+ * terms (rows or columns), or more; a document (row) of 2^32 tokens (entries) or more (all DS2I_EINVAL); then the device (DS2I_EDEVICE).
+ * No output -- device_ms included -- is written on any error.
+ *
+ * ds2i_hip_invert_postings: ds2i_invert_documents' outputs (lists for all nterms terms, empty ones included, and doc_sizes).
+ * ds2i_hip_transpose_postings: ds2i_transpose_postings' outputs. A column >= ncols, or columns that do not strictly increase within a
+ * row, are found by the count kernel, which indexes nothing by them: DS2I_EFORMAT.
+ * ds2i_hip_invert_documents: the image of index_kind over the twin's NONEMPTY lists, byte-identical to the host builder's; terms that
+ * never occur vanish and term_map (u32, strictly increasing) gives the old term of every surviving list: the map ds2i_hip_merge_indexes
+ * takes, so that a batch of new documents is indexed here and merged there with the default doc map. wand_image (may be NULL: none is
+ * built) is byte-identical to ds2i_wand_* over the same lists with doc_sizes (u32[num_docs], every document's token count, the ds2i
+ * .sizes value). index_kind: a kind ds2i_hip_encode_index writes; DS2I_BLOCK_QMX and DS2I_BLOCK_MIXED are DS2I_EINVAL with
+ * ds2i_hip_convert_index's message, checked before anything else is read. Documents without a single token are DS2I_EINVAL ("List must
+ * be nonempty").
+ * ds2i_hip_forward_index: the forward index of an image of any of the nine kinds: document d holds terms[doc_offsets[d] ..
+ * doc_offsets[d + 1]) (list numbers, strictly increasing) with freqs beside them; what a document-reordering method needs to make a map
+ * for ds2i_hip_remap_index. Host parse (DS2I_EFORMAT), the device, bare upload, extraction, the image closed, transposition.
+ * device_ms: the sum of ds2i_hip_invert_ms. */
+uint32_t ds2i_hip_invert_window(void);
+int ds2i_hip_invert_postings(int device, uint64_t num_docs, const uint64_t* doc_offsets, const uint32_t* tokens, uint64_t nterms,
+                             ds2i_blob** list_offsets, ds2i_blob** docs, ds2i_blob** freqs, ds2i_blob** doc_sizes, double* device_ms);
+int ds2i_hip_transpose_postings(int device, uint64_t nrows, uint64_t ncols, const uint64_t* row_offsets, const uint32_t* cols,
+                                const uint32_t* vals, ds2i_blob** col_offsets, ds2i_blob** rows, ds2i_blob** out_vals, double* device_ms);
+int ds2i_hip_invert_documents(int device, int index_kind, uint64_t num_docs, const uint64_t* doc_offsets, const uint32_t* tokens,
+                              uint64_t nterms, ds2i_blob** index_image, ds2i_blob** wand_image, ds2i_blob** term_map, ds2i_blob** doc_sizes,
+                              double* device_ms);
+int ds2i_hip_forward_index(int device, int index_kind, const void* image, size_t bytes, uint64_t* num_docs, uint64_t* nterms,
+                           ds2i_blob** doc_offsets, ds2i_blob** terms, ds2i_blob** freqs, double* device_ms);
+/* Diagnostic: the hipEvent milliseconds of this thread's last call of the four: ms[0] the check (stage) kernel, ms[1] the document
+ * sort, ms[2] the mark and count kernels, ms[3] the scatter and offsets kernels, ms[4] the transposition's count and scatter kernels,
+ * ms[5] the column sort, ms[6] the extraction (ds2i_hip_forward_index), ms[7] the encoder and the wand kernel
+ * (ds2i_hip_invert_documents). Unused slots are 0. */
+void ds2i_hip_invert_ms(double ms[8]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
