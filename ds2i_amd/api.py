@@ -206,6 +206,15 @@ def lib():
         L.ds2i_hip_invert_ms.restype = None
         L.ds2i_hip_invert_window.argtypes = []
         L.ds2i_hip_invert_window.restype = C.c_uint32
+        L.ds2i_order_postings.argtypes = [C.c_uint64, C.c_uint64, vp, vp, vp, C.c_int, C.POINTER(vp), C.POINTER(vp)]
+        L.ds2i_order_log_table.argtypes = [C.c_uint64, vp]
+        L.ds2i_postings_cost.argtypes = [C.c_uint64, vp, vp, u64p]
+        L.ds2i_order_clamp_gain.argtypes = [C.c_int64]
+        L.ds2i_order_clamp_gain.restype = C.c_int32
+        L.ds2i_hip_order_postings.argtypes = [C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_order_index.argtypes = [C.c_int, C.c_int, vp, C.c_size_t, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_double)]
+        L.ds2i_hip_order_ms.argtypes = [C.POINTER(C.c_double)]
+        L.ds2i_hip_order_ms.restype = None
         # build side
         L.ds2i_blob_data.argtypes = [vp]
         L.ds2i_blob_data.restype = vp
@@ -840,6 +849,84 @@ def gpu_forward_index(kind, image, device=0):
     return (n.value, v.value) + _take_csr(h), _invert_info(ms)
 
 
+class OrderParams(C.Structure):
+    """ds2i_order_params: zero in a field means its default (iterations 20, min_half 16, max_levels 32)"""
+    _fields_ = [("iterations", C.c_uint32), ("min_half", C.c_uint32), ("max_levels", C.c_uint32)]
+
+
+ORDER_MS = ("extract_ms", "level_sort_ms", "runs_ms", "degrees_ms", "gains_ms", "gain_sort_ms", "swap_ms", "compose_ms")
+
+
+def _order_lists(lists):
+    """posting lists as an iterable of doc-id arrays or of (docs, freqs) -> (number of lists, offsets uint64, docs uint32)"""
+    lists = [_u32(x[0] if isinstance(x, tuple) else x) for x in lists]
+    offs = np.zeros(len(lists) + 1, dtype=np.uint64)
+    if lists:
+        offs[1:] = np.cumsum([len(d) for d in lists], dtype=np.uint64)
+    docs = np.concatenate(lists) if lists else np.zeros(0, np.uint32)
+    if not len(docs):
+        docs = np.zeros(1, np.uint32)  # (a pointer the library may check against NULL)
+    return len(lists), offs, docs
+
+
+def _order_info(ms):
+    parts = (C.c_double * 8)()
+    lib().ds2i_hip_order_ms(parts)
+    info = {"device_ms": ms.value}
+    info.update(zip(ORDER_MS, parts))
+    return info
+
+
+def _take_order(hm, ht):
+    return np.frombuffer(_take_blob(hm), dtype=np.uint32), np.frombuffer(_take_blob(ht), dtype=np.uint64)
+
+
+def order_log_table(n):
+    """LOGQ[0 .. n) (ds2i_order_log_table): rint(log2(x) * 256) as uint32, LOGQ[0] = 0 -- the fixed-point logarithms of the ordering"""
+    out = np.zeros(max(n, 1), dtype=np.uint32)
+    _check(lib().ds2i_order_log_table(n, _ptr(out)))
+    return out[:n]
+
+
+def postings_cost(lists):
+    """The sum of LOGQ[gap] over all postings of `lists` (doc-id arrays or (docs, freqs) pairs), a list's first gap being doc + 1
+    (ds2i_postings_cost): the size of the collection under an ideal gap coder in 1/256 bits, an exact Python int."""
+    n, offs, docs = _order_lists(lists)
+    cost = C.c_uint64()
+    _check(lib().ds2i_postings_cost(n, _ptr(offs), _ptr(docs), C.byref(cost)))
+    return cost.value
+
+
+def order_postings(num_docs, lists, iterations=0, min_half=0, max_levels=0, threads=0):
+    """A document order for `lists` (doc-id arrays or (docs, freqs) pairs; doc-ids strictly increasing and < num_docs) by recursive
+    graph bisection ON THE HOST (ds2i_order_postings), the host twin of gpu_order_postings. Zero in a parameter means its default
+    (iterations 20, min_half 16, max_levels 32). Returns (doc_map uint32[num_docs] with new id = doc_map[old id], what remap_postings
+    and Index.remap take; trace uint64, the exchanges of every (level, iteration) that ran)."""
+    n, offs, docs = _order_lists(lists)
+    prm, hm, ht = OrderParams(iterations, min_half, max_levels), C.c_void_p(), C.c_void_p()
+    _check(lib().ds2i_order_postings(num_docs, n, _ptr(offs), _ptr(docs), C.byref(prm), threads, C.byref(hm), C.byref(ht)))
+    return _take_order(hm, ht)
+
+
+def gpu_order_postings(num_docs, lists, iterations=0, min_half=0, max_levels=0, device=0):
+    """order_postings ON THE GPU (ds2i_hip_order_postings): degrees, gains and swaps as HIP kernels over the lists where they lie, the
+    halves sorted by the segmented sort of gpu_remap_postings; the same map and trace, element for element.
+    Returns ((doc_map, trace), dict(device_ms, level_sort_ms, runs_ms, degrees_ms, gains_ms, gain_sort_ms, swap_ms, compose_ms, ...))."""
+    n, offs, docs = _order_lists(lists)
+    prm, hm, ht, ms = OrderParams(iterations, min_half, max_levels), C.c_void_p(), C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_order_postings(device, num_docs, n, _ptr(offs), _ptr(docs), C.byref(prm), C.byref(hm), C.byref(ht), C.byref(ms)))
+    return _take_order(hm, ht), _order_info(ms)
+
+
+def gpu_order_index(kind, image, iterations=0, min_half=0, max_levels=0, device=0):
+    """A document order for an index image of `kind` (any of the nine) ON THE GPU (ds2i_hip_order_index): extracted in one launch and
+    ordered where the postings lie; order_postings' map and trace over the extracted lists.
+    Returns ((doc_map, trace), dict(device_ms, extract_ms, ...)); gpu_remap_index(kind, image, doc_map) applies the map."""
+    prm, hm, ht, ms = OrderParams(iterations, min_half, max_levels), C.c_void_p(), C.c_void_p(), C.c_double()
+    _check(lib().ds2i_hip_order_index(device, _codec(kind), image, len(image), C.byref(prm), C.byref(hm), C.byref(ht), C.byref(ms)))
+    return _take_order(hm, ht), _order_info(ms)
+
+
 def synth_build_gpu(p, device=0, threads=0):
     """The synthetic collection as a block_optpfor index encoded on the GPU (ds2i_hip_synth_encode).
     -> (index image, wand image, postings, dict(generate_s, device_ms))"""
@@ -1278,6 +1365,11 @@ class Index:
         """The forward index of the image this index was opened from, on this index's device (gpu_forward_index).
         Returns ((num_docs, nterms, doc_offsets, terms, freqs), dict(device_ms, ...))."""
         return gpu_forward_index(self.kind, self._image, device=self.device)
+
+    def order(self, **params):
+        """A document order for the image this index was opened from, on this index's device (gpu_order_index; params: iterations,
+        min_half, max_levels). Returns ((doc_map, trace), dict(device_ms, ...)); remap(doc_map) applies it."""
+        return gpu_order_index(self.kind, self._image, device=self.device, **params)
 
     def calibration_read(self):
         n = C.c_uint64()

@@ -538,4 +538,33 @@ struct TransposeArgs {
     uint32_t* flag;                 // count: a column at or past ncols, or a row whose columns do not strictly increase
 };
 
+// ---- order_kernels.hip: documents ordered by recursive graph bisection (order_cost.hpp states the arithmetic, host_order.hpp the
+// algorithm). The lists lie on the device in p0 order (p0 = a document's position at the level's start), so a term's documents of one
+// level segment are one RUN of its list; a run's degrees live at its first entry, its HEAD. Entries are walked in windows of
+// ORDER_WINDOW, a wavefront a window at a time; documents and slots a thread each. Workgroups of SPLIT_THREADS threads on
+// split_grid's grids.
+constexpr uint32_t ORDER_WINDOW = 1024; // 16 entries a lane
+struct OrderArgs {
+    uint64_t num_docs;              // n
+    uint32_t level;                 // l: the segments are level l's, the halves level l + 1's
+    const uint32_t* logq;           // n + 3 words: the fixed-point logarithms (host-built)
+    uint64_t postings;
+    uint32_t* docs;                 // the entries: p0 of every posting, every list in p0 order
+    const uint64_t* list_first;     // nlists + 1 entry offsets, from 0 to `postings`
+    uint32_t nlists;                // >= 1 when there is a posting
+    uint32_t* back;                 // runs: per entry, its distance to its run's head (head = i - back[i])
+    uint32_t* run_len;              // runs: at a head, the entries of its run
+    uint32_t* deg_right;            // degrees: at a head, the run's documents now in the right half (zero-filled before the launch)
+    uint32_t* half_of;              // per position: the level l + 1 segment it lies in (bit 0: the side, the rest: the level l segment)
+    uint32_t* side;                 // per p0: the side of the slot the document is in now
+    unsigned long long* gain;       // per p0: the sum of its terms' costs, a wrapping int64 (zero-filled before the gains launch)
+    uint32_t *keys, *members;       // per slot: the sort key of the member's clamped gain, and the member (a p0)
+    const uint32_t* order;          // per position at the level's start: the document there
+    uint32_t* next_order;           // compose: order'[s] = order[members[s]]
+    uint32_t* inv;                  // compose: inv[members[s]] = s, the map the lists go through at the next level's start
+    uint32_t* doc_map;              // finish: doc_map[order[s]] = s
+    unsigned long long* exchanges;  // swap: the iteration's exchanges (zeroed before the launch)
+    uint32_t* flag;                 // check: a doc-id at or past num_docs
+};
+
 } // namespace ds2i_dev

@@ -17,6 +17,7 @@
 #include "host_pef.hpp"
 #include "host_hybrid.hpp"
 #include "host_merge.hpp"
+#include "host_order.hpp"
 #include "host_parallel.hpp"
 #include "host_remap.hpp"
 #include "host_synth.hpp"
@@ -320,6 +321,52 @@ int ds2i_transpose_postings(uint64_t nrows, uint64_t ncols, const uint64_t* row_
     return 0;
     DS2I_CATCH
 }
+
+int ds2i_order_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const ds2i_order_params* params,
+                        int threads, ds2i_blob** doc_map, ds2i_blob** trace) {
+    static const char* const who = "ds2i_order_postings";
+    if (!list_offsets || !docs || !doc_map || !trace) return ds2i_set_error(DS2I_EINVAL, "ds2i_order_postings: null argument");
+    DS2I_TRY
+    std::string fault = order_offsets_fault(who, nlists, list_offsets);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    fault = order_docs_fault(who, num_docs, nlists, list_offsets, docs);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EFORMAT, fault.c_str());
+    order_params prm;
+    fault = order_num_docs_fault(who, num_docs);
+    if (fault.empty()) fault = order_params_fault(who, params ? params->iterations : 0, params ? params->min_half : 0, params ? params->max_levels : 0, prm);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    threads = std::min(threads, 16);
+    std::vector<uint32_t> map;
+    std::vector<uint64_t> tr;
+    order_postings(num_docs, nlists, list_offsets, docs, prm, (unsigned)threads, map, tr);
+    std::unique_ptr<ds2i_blob> bm(ds2i_blob_of(map)), bt(ds2i_blob_of(tr));
+    *doc_map = bm.release();
+    *trace = bt.release();
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_order_log_table(uint64_t n, uint32_t* out) {
+    if (!out) return ds2i_set_error(DS2I_EINVAL, "ds2i_order_log_table: null argument");
+    order_log_table(n, out);
+    return 0;
+}
+
+int ds2i_postings_cost(uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, uint64_t* cost) {
+    static const char* const who = "ds2i_postings_cost";
+    if (!list_offsets || !docs || !cost) return ds2i_set_error(DS2I_EINVAL, "ds2i_postings_cost: null argument");
+    DS2I_TRY
+    std::string fault = order_offsets_fault(who, nlists, list_offsets);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    fault = order_docs_fault(who, 1ull << 32, nlists, list_offsets, docs);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EFORMAT, fault.c_str());
+    *cost = postings_cost(nlists, list_offsets, docs);
+    return 0;
+    DS2I_CATCH
+}
+
+int32_t ds2i_order_clamp_gain(int64_t gain) { return order_clamp_gain(gain); }
 
 int ds2i_opt_list_directory(const void* opt_image, size_t bytes, uint32_t term, ds2i_blob** cmax, ds2i_blob** chunks,
                             uint64_t info[5]) {

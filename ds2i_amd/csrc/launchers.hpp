@@ -100,4 +100,20 @@ hipError_t ds2i_launch_invert_scatter(const ds2i_dev::InvertArgs& a, unsigned gr
 hipError_t ds2i_launch_invert_offsets(const ds2i_dev::InvertArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_transpose_count(const ds2i_dev::TransposeArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_transpose_scatter(const ds2i_dev::TransposeArgs& a, unsigned grid, hipStream_t s);
+// ---- order_kernels.hip. grid: workgroups of SPLIT_THREADS threads. check, renumber, runs, degrees, gains: wavefronts stride over
+// the windows of ORDER_WINDOW entries (check and renumber: threads over the entries); level, keys, presort_keys, swap, compose, finish:
+// threads stride over the n positions. check: a.flag for a doc-id >= n; renumber: every entry through a.inv; level: half_of, side and
+// members of a level's start; runs: back and run_len; degrees: deg_right; gains: gain; keys: (gain key, member) per slot;
+// presort_keys: (member, member) per slot; swap: the exchanges of one iteration; compose: next_order and inv; finish: doc_map
+hipError_t ds2i_launch_order_check(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_renumber(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_level(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_runs(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_degrees(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_gains(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_keys(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_presort_keys(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_swap(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_compose(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+hipError_t ds2i_launch_order_finish(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
 }

@@ -185,6 +185,41 @@ int ds2i_invert_documents(uint64_t num_docs, const uint64_t* doc_offsets, const 
 int ds2i_transpose_postings(uint64_t nrows, uint64_t ncols, const uint64_t* row_offsets, const uint32_t* cols, const uint32_t* vals, int threads,
                             ds2i_blob** col_offsets, ds2i_blob** rows, ds2i_blob** out_vals);
 
+/* Ordering documents: a doc-id map computed by recursive graph bisection (Dhulipala et al., KDD'16), the map ds2i_remap_postings and
+ * ds2i_hip_remap_index take. Every codec here codes gaps, and an order that puts similar documents side by side makes the gaps small.
+ * The input is the postings of a collection in the CSR form of ds2i_opt_partition without the freqs (empty lists are allowed; doc-ids
+ * strictly increasing and < num_docs); the output is doc_map, u32[num_docs], a permutation with new id = doc_map[old id], and trace,
+ * one u64 per (level, iteration) that ran: the exchanges of that iteration. Both are made of integers alone, and ds2i_hip_order_postings
+ * (ds2i_hip.h) returns the same two arrays element for element.
+ * Fixed point: LOGQ[x] = rint(log2((double)x) * 256) as u32, LOGQ[0] = 0. order_log_table writes LOGQ[0 .. n) to out.
+ * Segments: level l cuts the positions into 2^l segments, segment k = [(k * num_docs) >> l, ((k + 1) * num_docs) >> l); its halves are
+ * the level l + 1 segments 2k (left) and 2k + 1 (right). Level l runs iff l < max_levels and every level l + 1 segment holds at least
+ * min_half documents; the first level that fails ends the run, and num_docs < 2 * min_half gives the identity.
+ * State: order[s], the document at position s, starts as the identity. At a level's start every document is named by its position
+ * then, p0, and members[s] = s. One iteration, of at most `iterations`: (1) for every term and level l segment, dl and dr, the term's
+ * documents now in the left and the right half; (2) for every document the sum over its terms, as int64 clamped to int32, of
+ *   c = da*(LOGQ[na]-LOGQ[da+1]) + db*(LOGQ[nb]-LOGQ[db+1]) - (da-1)*(LOGQ[na]-LOGQ[da]) - (db+1)*(LOGQ[nb]-LOGQ[db+2])
+ * with na / nb the sizes of its own / the other half and da / db the term's degrees there: its gain; (3) each half's members sorted
+ * by gain descending, equal gains by smaller p0 first; (4) in each segment, with m the smaller half's size, the i-th left and the i-th
+ * right member exchanged for every i < m with gain_left[i] + gain_right[i] > 0; (5) zero exchanges end the level. At a level's end
+ * order'[s] = order[members[s]]; at the end of the run doc_map[order[s]] = s.
+ * params: zero in a field means its default (iterations 20, min_half 16, max_levels 32); NULL: all defaults.
+ * Checks of order_postings, in this order: null arguments; the offsets (not starting at 0, or decreasing: DS2I_EINVAL); a doc-id
+ * >= num_docs or a list that does not strictly increase (DS2I_EFORMAT, the first offender named); num_docs >= 2^32 - 2; iterations
+ * > 65536 or max_levels > 32 (DS2I_EINVAL). On an error nothing is written. Sorting is spread over at most 16 host threads (threads
+ * <= 0: up to 16).
+ * postings_cost: the sum of LOGQ[gap] over all postings, a list's first gap being doc + 1: the size of a collection under an ideal gap
+ * coder in 1/256 bits, an exact integer, so that "a better order" needs no float. Lists that do not strictly increase are DS2I_EFORMAT. */
+typedef struct ds2i_order_params {
+    uint32_t iterations, min_half, max_levels;
+} ds2i_order_params;
+int ds2i_order_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const ds2i_order_params* params,
+                        int threads, ds2i_blob** doc_map, ds2i_blob** trace);
+int ds2i_order_log_table(uint64_t n, uint32_t* out);
+int ds2i_postings_cost(uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, uint64_t* cost);
+/* test hook: the int32 a gain is clamped to before the sort and the swap see it */
+int32_t ds2i_order_clamp_gain(int64_t gain);
+
 /* The chunk directory ds2i_hip_index_open builds for one list of an opt image (inspection / test hook):
  * cmax = u32[nchunks] last doc-id per chunk, chunks = nchunks x 12 dwords (ds2i_amd/csrc/device_pef.hpp),
  * info = {n, docs_bit0, freqs_bit0, docs bit-vector byte offset in the image, freqs bit-vector byte offset} */

@@ -586,6 +586,42 @@ int ds2i_hip_forward_index(int device, int index_kind, const void* image, size_t
  * (ds2i_hip_invert_documents). Unused slots are 0. */
 void ds2i_hip_invert_ms(double ms[8]);
 
+/* Ordering documents on the GPU: the doc-id map of recursive graph bisection, the map ds2i_hip_remap_index takes. ds2i_order_postings
+ * (ds2i_build.h, the host twin) states the algorithm; the result is made of integers alone, and the device returns the twin's doc_map
+ * and trace element for element.
+ *
+ * The plan. The lists lie on the device as entries named by p0, a document's position at the level's start, every list in p0 order:
+ * at level 0 that is the input, at every later level the entries go through the previous level's inverse and the segmented sort of
+ * ds2i_hip_remap_postings orders every list again. A term's documents of one level segment are then one run of its list, and the
+ * run's two degrees live at its first entry: no forward index is built. Once a level a runs kernel finds every entry's run by two
+ * binary searches in its own list. Once an iteration: a degrees kernel (one atomic add per run and wavefront step), a gains kernel
+ * (the term cost per entry from the uploaded LOGQ table, a 64-bit integer atomic add per entry into its document's gain), a keys
+ * kernel ((order-reversing u32 image of the clamped gain, p0) per slot), the segmented sort over the 2^(l+1) halves with the full
+ * 32-bit key bound, and a swap kernel (a thread per pair; the exchanges counted into one word the host reads). Where a half is longer
+ * than the class-2 bound of ds2i_hip_remap_class_bounds the sort by gain is only stable, so the halves are sorted by p0 first (LSD:
+ * p0, then gain); shorter halves compare whole (key, p0) pairs. Only integers are added, so no result depends on the order of the
+ * atomics. No logarithm is evaluated on the device and no float is touched.
+ *
+ * Device memory: 16 bytes per posting (24 while a level's lists are sorted, if one is longer than the class-2 bound) and 40 bytes per
+ * document (48 and the sort's tables while the halves are sorted). What does not fit is DS2I_ENOMEM naming these figures, with
+ * everything released.
+ *
+ * Checks, all before any device is looked for. ds2i_hip_order_postings: ds2i_order_postings' checks in its order. ds2i_hip_order_index:
+ * null arguments; an unknown index kind (any of the nine is taken); the image (host parse, DS2I_EFORMAT); num_docs >= 2^32 - 2; the
+ * parameters. Then the device (DS2I_EDEVICE). A doc-id >= num_docs among an image's postings is DS2I_EFORMAT from the check kernel.
+ * No output -- device_ms included -- is written on any error.
+ * ds2i_hip_order_index is the extraction followed by the ordering; the postings stay on the device. */
+typedef struct ds2i_order_params ds2i_order_params; /* ds2i_build.h */
+int ds2i_hip_order_postings(int device, uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs,
+                            const ds2i_order_params* params, ds2i_blob** doc_map, ds2i_blob** trace, double* device_ms);
+int ds2i_hip_order_index(int device, int index_kind, const void* image, size_t bytes, const ds2i_order_params* params, ds2i_blob** doc_map,
+                         ds2i_blob** trace, double* device_ms);
+/* Diagnostic: the hipEvent milliseconds of this thread's last call of the two: ms[0] the extraction (ds2i_hip_order_index), ms[1] the
+ * renumbering and sort of the lists at every level's start but the first, ms[2] the check, level-start and runs kernels, ms[3] the
+ * degrees kernels, ms[4] the gains kernels, ms[5] the keys kernels and the sorts of the halves, ms[6] the swap kernels, ms[7] the
+ * compose kernels and the final map. device_ms is their sum. */
+void ds2i_hip_order_ms(double ms[8]);
+
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
  * analogue of wand_data's max_term_weight, wand_data.hpp:40-52); out gets *nblocks floats (capacity in floats).
