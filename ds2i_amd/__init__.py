@@ -12,6 +12,7 @@ from .api import (  # noqa: F401
     invert_documents, transpose_postings, gpu_invert_postings, gpu_transpose_postings, gpu_invert_documents, gpu_forward_index, invert_window,
     order_postings, gpu_order_postings, gpu_order_index, postings_cost, order_log_table, OrderParams,
     DROP, split_postings, gpu_split_postings, gpu_split_index, split_window, split_grid_waves, image_shape,
+    MAX_SHARDS, ShardSet, split_wand, wand_arrays, merge_topk, gpu_merge_topk, merge_topk_grid,
     SynthParams, HybridBuilder, HybridModel, HULL_POINT, opt_list_directory, synth_list, synth_doc_sizes, set_option, synth_queries, synth_queries_topical, synth_build, synth_build_hybrid,
     and_query, or_query, ranked_and_query, wand_query, maxscore_query, ranked_or_query,
 )

@@ -196,6 +196,17 @@ def lib():
         L.ds2i_hip_split_window.restype = C.c_uint32
         L.ds2i_hip_split_grid_waves.argtypes = [C.c_uint32]
         L.ds2i_hip_split_grid_waves.restype = C.c_uint32
+        L.ds2i_hip_index_set_collection_stats.argtypes = [vp, C.c_uint64, vp, C.c_uint64]
+        L.ds2i_split_wand.argtypes = [vp, C.c_size_t, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]
+        L.ds2i_wand_arrays.argtypes = [vp, C.c_size_t, C.POINTER(vp), C.POINTER(vp)]
+        L.ds2i_merge_topk.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.c_int]
+        L.ds2i_hip_merge_topk.argtypes = [C.c_int, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, C.POINTER(C.c_double)]
+        L.ds2i_hip_merge_topk_grid.argtypes = [C.c_uint32, C.c_uint32]
+        L.ds2i_hip_merge_topk_grid.restype = C.c_uint32
+        L.ds2i_hip_shard_set_open.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, vp, C.POINTER(vp)]
+        L.ds2i_hip_shard_set_query.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp, vp, vp]
+        L.ds2i_hip_shard_set_close.argtypes = [vp]
+        L.ds2i_hip_shard_set_close.restype = None
         L.ds2i_invert_documents.argtypes = [C.c_uint64, vp, vp, C.c_uint64, C.c_int] + [C.POINTER(vp)] * 4
         L.ds2i_transpose_postings.argtypes = [C.c_uint64, C.c_uint64, vp, vp, vp, C.c_int] + [C.POINTER(vp)] * 3
         L.ds2i_hip_invert_postings.argtypes = [C.c_int, C.c_uint64, vp, vp, C.c_uint64] + [C.POINTER(vp)] * 4 + [C.POINTER(C.c_double)]
@@ -730,6 +741,83 @@ def gpu_split_index(kind, image, shard_of, nshards=None, to_kind=None, device=0)
     _check(lib().ds2i_hip_split_index(device, _codec(kind), image, len(image), _ptr(m), len(m), nshards,
                                       _codec(kind if to_kind is None else to_kind), C.byref(h), C.byref(ms)))
     return _take_shards(h, nshards, True), _split_info(ms)
+
+
+MAX_SHARDS = 64  # DS2I_HIP_MAX_SHARDS (include/ds2i_hip.h)
+
+
+def split_wand(wand_image, doc_map, term_map):
+    """A shard's wand_data image under the COLLECTION's normalisation (ds2i_split_wand): norm_lens gathered through doc_map,
+    max_term_weight through term_map (the maps of split_postings / gpu_split_index), no pass over the postings. It is not the image
+    build_wand gives over the shard: that one divides by the shard's own average document length."""
+    dm, tm = _u32(doc_map), _u32(term_map)
+    h = C.c_void_p()
+    _check(lib().ds2i_split_wand(wand_image, len(wand_image), _ptr(dm), len(dm), _ptr(tm), len(tm), C.byref(h)))
+    return _take_blob(h)
+
+
+def wand_arrays(wand_image):
+    """(norm_lens float32[num_docs], max_term_weight float32[terms]) of a wand_data image (ds2i_wand_arrays)"""
+    a, b = C.c_void_p(), C.c_void_p()
+    _check(lib().ds2i_wand_arrays(wand_image, len(wand_image), C.byref(a), C.byref(b)))
+    return np.frombuffer(_take_blob(a), dtype=np.float32), np.frombuffer(_take_blob(b), dtype=np.float32)
+
+
+class TopkRows(C.Structure):
+    """ds2i_topk_rows (include/ds2i_build.h)"""
+    _fields_ = [("scores", C.c_void_p), ("docs", C.c_void_p), ("lens", C.c_void_p), ("doc_map", C.c_void_p), ("map_len", C.c_uint64)]
+
+
+def _topk_rows(rows, k):
+    """rows: iterable of (scores float32[nq, k], docs uint32[nq, k], lens uint32[nq][, doc_map]) -> (array of TopkRows, nq, k, what it
+    points into)"""
+    rows = list(rows)
+    arr, keep, nq = (TopkRows * max(1, len(rows)))(), [], None
+    for dst, (scores, docs, lens, *rest) in zip(arr, rows):
+        s = np.ascontiguousarray(scores, dtype=np.float32)
+        dd, ll = _u32(docs), _u32(lens)
+        if k is None:
+            k = s.shape[1] if s.ndim == 2 else 0
+        nq = len(ll) if nq is None else nq
+        if len(ll) != nq or s.size != nq * k or dd.size != nq * k:
+            raise ValueError("every row set holds nq lengths and nq * k scores and docs")
+        m = _u32(rest[0]) if rest and rest[0] is not None else None
+        keep.extend((s, dd, ll, m))
+        dst.scores, dst.docs, dst.lens = s.ctypes.data, dd.ctypes.data, ll.ctypes.data
+        dst.doc_map, dst.map_len = (None, 0) if m is None else (m.ctypes.data, len(m))
+    return arr, len(rows), nq or 0, k or 0, keep
+
+
+def _merge_out(nq, k):
+    return (np.full((nq, max(k, 1)), -np.inf, dtype=np.float32), np.full((nq, max(k, 1)), 0xFFFFFFFF, dtype=np.uint32),
+            np.zeros(max(nq, 1), dtype=np.uint32))
+
+
+def merge_topk(rows, k=None, threads=0):
+    """The top-k rows several shards answered for the same queries merged ON THE HOST into the rows of the whole collection
+    (ds2i_merge_topk), the host twin of gpu_merge_topk. rows: iterable of (scores[nq, k], docs[nq, k], lens[nq][, doc_map]); doc_map
+    gives the collection doc-id of every local id (None: the ids are the collection's). Score descending, equal scores by collection
+    doc-id ascending, the smaller ids on a tie at the k-th place. Returns (scores float32[nq, k], docs uint32[nq, k], lens uint32[nq])."""
+    arr, n, nq, k, keep = _topk_rows(rows, k)
+    s, dd, ll = _merge_out(nq, k)
+    _check(lib().ds2i_merge_topk(arr, n, nq, k, _ptr(s), _ptr(dd), _ptr(ll), threads))
+    return s[:, :k], dd[:, :k], ll[:nq]
+
+
+def gpu_merge_topk(rows, k=None, device=0):
+    """merge_topk ON THE GPU (ds2i_hip_merge_topk): one wavefront per query folds the row sets into a best-k buffer in LDS; the same
+    rows, element for element. Returns (scores, docs, lens, dict(device_ms))."""
+    arr, n, nq, k, keep = _topk_rows(rows, k)
+    s, dd, ll = _merge_out(nq, k)
+    ms = C.c_double()
+    _check(lib().ds2i_hip_merge_topk(device, arr, n, nq, k, _ptr(s), _ptr(dd), _ptr(ll), C.byref(ms)))
+    return s[:, :k], dd[:, :k], ll[:nq], {"device_ms": ms.value}
+
+
+def merge_topk_grid(compute_units, k):
+    """the most workgroups (one wavefront each, a query at a time) a launch of the device merge at that k has on a device of that many
+    compute units (ds2i_hip_merge_topk_grid): what the units' LDS and wavefront slots hold; they stride over the queries"""
+    return lib().ds2i_hip_merge_topk_grid(compute_units, k)
 
 
 def invert_window():
@@ -1310,6 +1398,17 @@ class Index:
     def device_bytes(self):
         return lib().ds2i_hip_index_device_bytes(self._h)
 
+    def set_collection_stats(self, num_docs=0, df=None):
+        """Collection-wide BM25 statistics for an index that holds a shard (ds2i_hip_index_set_collection_stats): every batch planned
+        afterwards weighs a term by query_term_weight(qtf, df[term], num_docs). df: one document frequency per list of this index.
+        No arguments: cleared, the index scores by its own statistics again. Not to be called while another thread plans a batch on
+        this index."""
+        if df is None:
+            _check(lib().ds2i_hip_index_set_collection_stats(self._h, num_docs, None, 0))
+            return
+        a = _u32(df)
+        _check(lib().ds2i_hip_index_set_collection_stats(self._h, num_docs, _ptr(a), len(a)))
+
     def info(self):
         """what the upload put into HBM beside the index image (ds2i_hip_index_get_info), as a dict"""
         i = IndexInfo()
@@ -1428,6 +1527,90 @@ class Index:
 
 
 # ---------------------------------------------------------------- query-operator concept
+class ShardSource(C.Structure):
+    """ds2i_shard_source (include/ds2i_hip.h)"""
+    _fields_ = [("device", C.c_int), ("kind", C.c_int), ("image", C.c_void_p), ("bytes", C.c_size_t), ("wand_image", C.c_void_p),
+                ("wand_bytes", C.c_size_t), ("doc_map", C.c_void_p), ("map_len", C.c_uint64), ("term_map", C.c_void_p), ("terms_len", C.c_uint64)]
+
+
+class ShardStats(C.Structure):
+    """ds2i_hip_shard_stats (include/ds2i_hip.h)"""
+    _fields_ = [("kernel_ms", C.c_double * MAX_SHARDS), ("merge_ms", C.c_double), ("translate_ms", C.c_double), ("shards_open", C.c_uint32)]
+
+
+class ShardSet:
+    """Document shards queried as one index (ds2i_hip_shard_set_*): every shard an index on its own device with the collection's BM25
+    statistics, a batch sent to all of them and their top-k rows merged on the device, in the collection's doc-ids.
+    sources: iterable of (kind, image, wand_image or None, doc_map, term_map[, device]) -- wand_image is split_wand's.
+    num_docs / df: the collection's statistics (None: the sums over the shards, which for a split with nothing dropped are the unsplit
+    index's own)."""
+
+    def __init__(self, sources, collection_docs, collection_terms, num_docs=None, df=None):
+        self._h = C.c_void_p()
+        sources = list(sources)
+        arr, keep = (ShardSource * max(1, len(sources)))(), []
+        for src, (kind, image, wand, doc_map, term_map, *rest) in zip(arr, sources):
+            dm, tm = _u32(doc_map), _u32(term_map)
+            keep.extend((image, wand, dm, tm))
+            src.device, src.kind = (rest[0] if rest else 0), _codec(kind)
+            src.image, src.bytes = C.cast(C.c_char_p(image), C.c_void_p), len(image)
+            src.wand_image, src.wand_bytes = (None, 0) if wand is None else (C.cast(C.c_char_p(wand), C.c_void_p), len(wand))
+            src.doc_map, src.map_len, src.term_map, src.terms_len = dm.ctypes.data, len(dm), tm.ctypes.data, len(tm)
+        self.nsources = len(sources)
+        a = None if df is None else _u32(df)
+        if a is not None and len(a) != collection_terms:
+            raise ValueError("df holds %d entries for %d collection terms" % (len(a), collection_terms))
+        _check(lib().ds2i_hip_shard_set_open(arr, len(sources), collection_docs, collection_terms, num_docs or 0, None if a is None else _ptr(a),
+                                             C.byref(self._h)))
+
+    @classmethod
+    def from_split(cls, kind, image, wand_image, shard_of, nshards=None, to_kind=None, devices=None, num_docs=None, df=None):
+        """The image cut into shards on the GPU (gpu_split_index, on devices[0]), every shard given its wand data (split_wand) and
+        opened on devices[s % len(devices)] (None: device 0). The collection's doc-ids are the image's."""
+        devices = list(devices) if devices else [0]
+        n, v = image_shape(kind, image)
+        shards, _ = gpu_split_index(kind, image, shard_of, nshards, to_kind, device=devices[0])
+        kind2 = kind if to_kind is None else to_kind
+        sources = [(kind2, img, None if wand_image is None else split_wand(wand_image, dm, tm), dm, tm, devices[s % len(devices)])
+                   for s, (img, dm, tm) in enumerate(shards)]
+        return cls(sources, n, v, num_docs=num_docs, df=df)
+
+    def _query(self, op, queries, k, ranked):
+        terms, offs = queries if isinstance(queries, tuple) else _flatten(queries)
+        nq = len(offs) - 1
+        count = np.zeros(max(nq, 1), dtype=np.uint64)
+        st = ShardStats()
+        if not ranked:
+            _check(lib().ds2i_hip_shard_set_query(self._h, _op(op), 0, _ptr(terms), _ptr(offs), nq, _ptr(count), None, None, None, C.byref(st)))
+            return count[:nq], st
+        topk = np.full((max(nq, 1), max(k, 1)), -np.inf, dtype=np.float32)
+        docs = np.full((max(nq, 1), max(k, 1)), 0xFFFFFFFF, dtype=np.uint32)
+        tlen = np.zeros(max(nq, 1), dtype=np.uint32)
+        _check(lib().ds2i_hip_shard_set_query(self._h, _op(op), k, _ptr(terms), _ptr(offs), nq, _ptr(count), _ptr(topk), _ptr(docs), _ptr(tlen),
+                                              C.byref(st)))
+        return count[:nq], topk[:nq], docs[:nq], tlen[:nq], st
+
+    def query_batch_docs(self, op, queries, k=10):
+        """a ranked operator over the set -> (count, topk float32[nq, k], collection doc-ids uint32[nq, k], tlen, ShardStats): what
+        Index.query_batch_docs of the whole collection returns"""
+        return self._query(op, queries, k, True)
+
+    def query_counts(self, op, queries):
+        """`and` / `or` over the set -> (count uint64[nq] = the sum of the shards' counts, ShardStats)"""
+        return self._query(op, queries, 0, False)
+
+    def close(self):
+        if self._h:
+            lib().ds2i_hip_shard_set_close(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _query_op:
     op = None
     ranked = False

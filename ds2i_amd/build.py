@@ -18,7 +18,8 @@ ARCH = "gfx950"
 # encoder, wand_kernels.hip the wand_data builder, freq_encode_kernels.hip the encoder of the Elias-Fano layouts, partition_kernels.hip the
 # partition DP of the opt layout, remap_kernels.hip the doc-id map and the segmented sort of a renumbered collection, merge_kernels.hip the placement of a merge's sources,
 # split_kernels.hip the compaction of a split's shards, invert_kernels.hip the run-length step and the transposition that index documents,
-# order_kernels.hip the degrees, gains and swaps of recursive graph bisection, which orders documents.
+# order_kernels.hip the degrees, gains and swaps of recursive graph bisection, which orders documents,
+# shard_kernels.hip the merge of the top-k rows of document shards.
 RANKED_UNITS = [("kernels.hip", "kernels_t%d.hip" % t, ["-DDS2I_TU_TMAX=%d" % t]) for t in (2, 4, 8, 16, 0)] + [
     ("ranked_stream.hip", "ranked_stream.hip", []),
     ("ranked_stream.hip", "ranked_stream_bigk.hip", ["-DDS2I_RS_BIGK_TU"]),
@@ -36,9 +37,10 @@ DEVICE_UNITS = RANKED_UNITS + [("kernels.hip", "kernels.hip", []), ("freq_stream
                                ("merge_kernels.hip", "merge_kernels.hip", []),
                                ("split_kernels.hip", "split_kernels.hip", []),
                                ("invert_kernels.hip", "invert_kernels.hip", []),
-                               ("order_kernels.hip", "order_kernels.hip", [])] + DOCS_UNITS
+                               ("order_kernels.hip", "order_kernels.hip", []),
+                               ("shard_kernels.hip", "shard_kernels.hip", [])] + DOCS_UNITS
 HOST_SRCS = ["capi.cpp", "capi_batch.cpp", "batch_plan.cpp", "capi_build.cpp", "capi_encode.cpp", "capi_verify.cpp", "capi_extract.cpp",
-             "capi_remap.cpp", "capi_merge.cpp", "capi_split.cpp", "capi_invert.cpp", "capi_order.cpp"]
+             "capi_remap.cpp", "capi_merge.cpp", "capi_split.cpp", "capi_invert.cpp", "capi_order.cpp", "capi_shards.cpp"]
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           "-Wno-unused-variable", "-Wno-unused-but-set-variable"]
 

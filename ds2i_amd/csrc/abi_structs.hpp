@@ -567,4 +567,38 @@ struct OrderArgs {
     uint32_t* flag;                 // check: a doc-id at or past num_docs
 };
 
+// ---- shard_kernels.hip: the top-k rows several shards answered for the same queries merged into the rows of the whole collection
+// (include/ds2i_build.h, ds2i_merge_topk, states the key order). One wavefront a workgroup and a query at a time; workgroups stride.
+constexpr uint32_t MERGE_TOPK_MAX_ROWS = 64;   // DS2I_HIP_MAX_SHARDS
+constexpr uint32_t MERGE_TOPK_MAX_K = 1024;    // DS2I_HIP_MAX_K_LONG: the bitonic network sorts at most that many keys
+// k rounded up to a power of two, at least 2: the keys of one LDS buffer
+inline uint32_t merge_topk_pow2(uint32_t k) {
+    uint32_t p = 2;
+    while (p < k) p <<= 1;
+    return p;
+}
+// the workgroups of a launch over nq queries: per compute unit as many as 128 KiB of its LDS hold at 24 * pow2(k) bytes each, at most
+// its 32 wavefront slots (5 at k = 1024, 32 from k = 128 down). Sized from the resources alone: no rate was measured at any k.
+inline unsigned merge_topk_grid(uint64_t nq, int cus, uint32_t k) {
+    const uint64_t fit = (128ull << 10) / (24ull * merge_topk_pow2(k)), per_cu = fit > 32 ? 32 : fit < 1 ? 1 : fit;
+    const uint64_t cap = per_cu * (uint64_t)(cus > 0 ? cus : 1);
+    return (unsigned)(nq < cap ? nq : cap);
+}
+struct TopkRowSet {
+    const float* scores;            // nq * k
+    const uint32_t* docs;           // nq * k, local doc-ids
+    const uint32_t* lens;           // nq
+    const uint32_t* doc_map;        // map_len collection doc-ids, or null: the ids are the collection's
+    uint64_t map_len;
+};
+struct MergeTopkArgs {
+    const TopkRowSet* rows;         // nrows of them, on the device
+    uint32_t nrows, nq, k;
+    uint32_t pow2;                  // k rounded up to a power of two: the keys of one LDS buffer
+    unsigned long long unsorted;    // bit r: row set r's map is not increasing, its rows are sorted by key first
+    float* out_scores;              // nq * k
+    uint32_t* out_docs;             // nq * k
+    uint32_t* out_lens;             // nq
+};
+
 } // namespace ds2i_dev

@@ -234,7 +234,8 @@ static void plan_range(BatchPlan& b, const PlanIndex& ix, const uint32_t* terms,
             const uint32_t nb = qt.nblocks;
             qt.q_weight = qt.max_weight = 0.f;
             if (ranked) {
-                qt.q_weight = ds2i_host::bm25::query_term_weight(p.second, qt.n, ix.num_docs);
+                qt.q_weight = ix.stats_df ? ds2i_host::bm25::query_term_weight(p.second, ix.stats_df[p.first], ix.stats_num_docs)
+                                          : ds2i_host::bm25::query_term_weight(p.second, qt.n, ix.num_docs);
                 qt.max_weight = qt.q_weight * mtw;
                 qt.max_bmw = ix.bmw ? qt.q_weight * lbmw : std::numeric_limits<float>::infinity();
                 qt.rmw_scale = qt.q_weight * (lbmw * (1.0f / 255.0f)); // range-table byte -> bound of the term score

@@ -103,6 +103,10 @@ struct PlanIndex {
     const ds2i_dev::QTerm* term_proto = nullptr; // one per list (ds2i_hip_index::term_proto)
     const uint32_t* list_n = nullptr;            // postings per list
     const float* list_topbmw = nullptr;          // per list: its DS2I_HIP_MAX_K largest block weights, descending, padded with 0
+    // collection-wide BM25 statistics of an index that holds a shard (ds2i_hip_index_set_collection_stats); unset: the query weight of
+    // a term comes from its list's own length and num_docs. They enter the query weight and nothing else.
+    uint64_t stats_num_docs = 0;
+    const uint32_t* stats_df = nullptr;          // one per list
 };
 
 // What a caller asks for

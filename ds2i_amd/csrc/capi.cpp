@@ -779,6 +779,30 @@ uint64_t ds2i_hip_index_num_docs(const ds2i_hip_index* idx) { return idx ? idx->
 uint64_t ds2i_hip_index_device_bytes(const ds2i_hip_index* idx) {
     return idx ? idx->arena_bytes + idx->extra_bytes + (idx->has_wand ? 4 * idx->num_docs : 0) : 0;
 }
+int ds2i_hip_index_set_collection_stats(ds2i_hip_index* idx, uint64_t num_docs, const uint32_t* df, uint64_t ndf) {
+    static const std::string who = "ds2i_hip_index_set_collection_stats: ";
+    if (!idx) return ds2i_set_error(DS2I_EINVAL, (who + "null index").c_str());
+    if (num_docs == 0 && !df) { // cleared
+        idx->stats_num_docs = 0;
+        std::vector<uint32_t>().swap(idx->stats_df);
+        return DS2I_OK;
+    }
+    if (!df || ndf != idx->size)
+        return ds2i_set_error(DS2I_EINVAL, (who + "df holds " + std::to_string(df ? ndf : 0) + " terms, the index " + std::to_string(idx->size)).c_str());
+    if (num_docs < idx->num_docs)
+        return ds2i_set_error(DS2I_EINVAL, (who + "a collection of " + std::to_string(num_docs) + " documents is smaller than the index's " +
+                                            std::to_string(idx->num_docs)).c_str());
+    for (uint64_t t = 0; t < ndf; ++t)
+        if (df[t] < idx->list_n[t] || df[t] > num_docs)
+            return ds2i_set_error(DS2I_EINVAL, (who + "term " + std::to_string(t) + ": df " + std::to_string(df[t]) + " lies outside its list's length " +
+                                                std::to_string(idx->list_n[t]) + " .. the collection's " + std::to_string(num_docs) + " documents").c_str());
+    DS2I_TRY
+    std::vector<uint32_t> copy(df, df + ndf);
+    idx->stats_df.swap(copy);
+    idx->stats_num_docs = num_docs;
+    return DS2I_OK;
+    DS2I_CATCH
+}
 int ds2i_hip_index_get_info(const ds2i_hip_index* idx, ds2i_hip_index_info* out) {
     if (!idx || !out) return ds2i_set_error(DS2I_EINVAL, "ds2i_hip_index_get_info: null argument");
     std::memset(out, 0, sizeof *out);

@@ -20,6 +20,7 @@
 #include "host_order.hpp"
 #include "host_parallel.hpp"
 #include "host_remap.hpp"
+#include "host_shard.hpp"
 #include "host_synth.hpp"
 
 using namespace ds2i_host;
@@ -216,6 +217,48 @@ int ds2i_remap_wand(const void* wand_image, size_t bytes, const uint32_t* doc_ma
     std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
     remap_wand(w, doc_map, blob->data);
     *out = blob.release();
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_split_wand(const void* wand_image, size_t bytes, const uint32_t* doc_map, uint64_t ndocs, const uint32_t* term_map, uint64_t nterms,
+                    ds2i_blob** out) {
+    if (!wand_image || !out || (!doc_map && ndocs) || (!term_map && nterms)) return ds2i_set_error(DS2I_EINVAL, "ds2i_split_wand: null argument");
+    DS2I_TRY
+    wand_view w;
+    w.parse(wand_image, bytes);
+    const std::string fault = split_wand_fault("ds2i_split_wand", w, doc_map, ndocs, term_map, nterms);
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    std::unique_ptr<ds2i_blob> blob(new ds2i_blob);
+    split_wand(w, doc_map, ndocs, term_map, nterms, blob->data);
+    *out = blob.release();
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_wand_arrays(const void* wand_image, size_t bytes, ds2i_blob** norm_lens, ds2i_blob** max_term_weight) {
+    if (!wand_image || (!norm_lens && !max_term_weight)) return ds2i_set_error(DS2I_EINVAL, "ds2i_wand_arrays: null argument");
+    DS2I_TRY
+    wand_view w;
+    w.parse(wand_image, bytes);
+    std::unique_ptr<ds2i_blob> a(new ds2i_blob), b(new ds2i_blob);
+    a->data.assign(w.norm_lens, w.norm_lens + 4 * w.num_docs);
+    b->data.assign(w.max_term_weight, w.max_term_weight + 4 * w.num_terms);
+    if (norm_lens) *norm_lens = a.release();
+    if (max_term_weight) *max_term_weight = b.release();
+    return 0;
+    DS2I_CATCH
+}
+
+int ds2i_merge_topk(const ds2i_topk_rows* rows, uint32_t nrows, uint32_t nq, uint32_t k, float* out_scores, uint32_t* out_docs, uint32_t* out_lens,
+                    int threads) {
+    DS2I_TRY
+    const std::string fault = merge_topk_fault("ds2i_merge_topk", rows, nrows, nq, k, nq && (!out_scores || !out_docs || !out_lens));
+    if (!fault.empty()) return ds2i_set_error(DS2I_EINVAL, fault.c_str());
+    if (!nq) return 0;
+    if (threads <= 0) threads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    threads = std::min(threads, 16);
+    merge_topk(rows, nrows, nq, k, out_scores, out_docs, out_lens, (unsigned)threads);
     return 0;
     DS2I_CATCH
 }

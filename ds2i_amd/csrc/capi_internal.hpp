@@ -143,6 +143,10 @@ struct ds2i_hip_index {
     // it, with the query-independent factors parked in the fields planning overwrites -- q_weight = max_term_weight,
     // max_weight = list max block weight.
     std::vector<ds2i_dev::QTerm> term_proto;
+    // ds2i_hip_index_set_collection_stats: the collection's number of documents and document frequencies (one per list) of an index
+    // that holds a shard; stats_df empty = unset
+    uint64_t stats_num_docs = 0;
+    std::vector<uint32_t> stats_df;
 };
 
 void ds2i_batch_destroy(ds2i_hip_batch* b); // capi_batch.cpp
@@ -222,6 +226,8 @@ static inline PlanIndex ds2i_plan_index(const ds2i_hip_index* idx) {
     ix.term_proto = idx->term_proto.data();
     ix.list_n = idx->list_n.data();
     ix.list_topbmw = idx->list_topbmw.data();
+    ix.stats_num_docs = idx->stats_num_docs;
+    ix.stats_df = idx->stats_df.empty() ? nullptr : idx->stats_df.data();
     return ix;
 }
 

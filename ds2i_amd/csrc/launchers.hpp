@@ -116,4 +116,6 @@ hipError_t ds2i_launch_order_presort_keys(const ds2i_dev::OrderArgs& a, unsigned
 hipError_t ds2i_launch_order_swap(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_order_compose(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
 hipError_t ds2i_launch_order_finish(const ds2i_dev::OrderArgs& a, unsigned grid, hipStream_t s);
+// ---- shard_kernels.hip: grid workgroups of one wavefront stride over the a.nq queries; dynamic LDS = 24 * a.pow2 bytes
+hipError_t ds2i_launch_merge_topk(const ds2i_dev::MergeTopkArgs& a, unsigned grid, hipStream_t s);
 }

@@ -425,4 +425,51 @@ typedef gpu_query_op<DS2I_OP_RANKED_OR> ranked_or_query;
 // the same operators over a replica set (one index per device)
 template <int OP> using set_query = gpu_set_query_op<OP>;
 
+// Document shards queried as one index (ds2i_hip_shard_set_*): every shard an image of its own kind on its own device, with the maps of
+// a split and its wand data under the collection's normalisation (ds2i_split_wand). A batch goes to every shard; the top-k rows are
+// merged on the device, in the collection's doc-ids. (gpu_index_set above replicates one index and cuts the batch; this cuts the index.)
+class gpu_shard_set {
+public:
+    struct result {
+        std::vector<uint64_t> count;      // per query: the merged row's length (ranked), the sum of the shards' counts (and / or)
+        std::vector<float> topk;          // nq * k, ranked operators only
+        std::vector<uint32_t> docs, len;  // nq * k collection doc-ids, nq lengths
+        ds2i_hip_shard_stats stats;
+    };
+    gpu_shard_set(std::vector<ds2i_shard_source> const& sources, uint64_t collection_docs, uint64_t collection_terms, uint64_t stats_num_docs = 0,
+                  const uint32_t* stats_df = nullptr) {
+        check(ds2i_hip_shard_set_open(sources.data(), (uint32_t)sources.size(), collection_docs, collection_terms, stats_num_docs, stats_df, &m_h),
+              "ds2i_hip_shard_set_open");
+    }
+    gpu_shard_set(gpu_shard_set const&) = delete;
+    gpu_shard_set& operator=(gpu_shard_set const&) = delete;
+    ~gpu_shard_set() { ds2i_hip_shard_set_close(m_h); }
+    // op: DS2I_OP_AND / DS2I_OP_OR (k ignored) or a ranked operator
+    result operator()(int op, std::vector<term_id_vec> const& queries, uint32_t k = 10) const {
+        std::vector<uint32_t> terms, offs(1, 0);
+        for (auto const& q : queries) {
+            terms.insert(terms.end(), q.begin(), q.end());
+            offs.push_back((uint32_t)terms.size());
+        }
+        if (terms.empty()) terms.push_back(0);
+        const uint32_t nq = (uint32_t)queries.size();
+        const bool ranked = (op & 0xFF) >= DS2I_OP_RANKED_AND;
+        result r;
+        r.count.assign(nq, 0);
+        if (ranked) {
+            r.topk.assign((size_t)nq * k, -std::numeric_limits<float>::infinity());
+            r.docs.assign((size_t)nq * k, 0xFFFFFFFFu);
+            r.len.assign(nq, 0);
+        }
+        check(ds2i_hip_shard_set_query(m_h, op, k, terms.data(), offs.data(), nq, r.count.data(), ranked ? r.topk.data() : nullptr,
+                                       ranked ? r.docs.data() : nullptr, ranked ? r.len.data() : nullptr, &r.stats),
+              "ds2i_hip_shard_set_query");
+        return r;
+    }
+    ds2i_hip_shard_set* handle() const { return m_h; }
+
+private:
+    ds2i_hip_shard_set* m_h = nullptr;
+};
+
 } // namespace ds2i_hip

@@ -1,6 +1,6 @@
 // split_index -- an index file cut into shards by documents, or with documents deleted, on the GPU: the inverse of merge_indexes.
 //
-//   split_index <from_type> <in_index> <to_type> <out> (--assign <file> | --ranges c1,c2,...) [--check] [--device <n>]
+//   split_index <from_type> <in_index> <to_type> <out> (--assign <file> | --ranges c1,c2,...) [--wand <in.wand>] [--check] [--device <n>]
 //
 // Writes, for every shard s, <out>.<s> (the image ds2i_hip_split_index returns: byte-identical to what create_freq_index <to_type>
 // writes for the shard's collection), <out>.<s>.docs (the old doc-id of every document of the shard) and <out>.<s>.terms (the old term
@@ -17,19 +17,24 @@
 //   --check          the input is extracted (ds2i_hip_extract_collection), split on the host (ds2i_split_postings) and every written
 //                    shard verified against that (ds2i_hip_verify_collection): one line per shard on stdout,
 //                    "OK lists=<V> postings=<n>" or "MISMATCH <what> ..." as create_freq_index --check prints it.
+//   --wand <in.wand> the wand data of the input: <out>.<s>.wand is written beside every shard, the shard's wand data under the
+//                    COLLECTION's normalisation (ds2i_split_wand: both arrays gathered through the shard's maps), which is what
+//                    shard_queries opens the shard with. A file that is missing or is no wand data of the input is found before any
+//                    device is touched.
 //   --device <n>     the HIP device (default 0)
 // When no document is deleted, the first line on stdout is the merge_indexes command line that puts the shards back together, into
-// <out>.merged. Wand data is not split: a shard's normalised lengths divide by the shard's own average length; build it from the
-// shard's document sizes, sizes[<out>.<s>.docs]. Flags may stand anywhere.
+// <out>.merged. Without --wand no wand data is written: the wand data of a shard as a collection of its own (normalised lengths divided by
+// the shard's own average length) is built from the shard's document sizes, sizes[<out>.<s>.docs]. Flags may stand anywhere.
 // Exit code: 0 success, 1 a written shard does not match the input, 2 an error.
 #include "tool_verify.hpp"
 
 #include <cstdlib>
 
 static const char* const USAGE =
-    " <from_type> <in_index> <to_type> <out> (--assign <file> | --ranges c1,c2,...) [--check] [--device <n>]\n"
+    " <from_type> <in_index> <to_type> <out> (--assign <file> | --ranges c1,c2,...) [--wand <in.wand>] [--check] [--device <n>]\n"
     "  --assign: <file> is one binary sequence [num_docs][num_docs x u32], the shard of every document (4294967295 deletes it)\n"
     "  --ranges: contiguous doc-id ranges [0, c1), [c1, c2), ..., [cn, num_docs)\n"
+    "  --wand: <in.wand> is the input's wand data; <out>.<s>.wand is written under the collection's normalisation\n"
     "  writes <out>.<s>, <out>.<s>.docs and <out>.<s>.terms for every shard s\n";
 
 // one binary sequence whose length word counts exactly the words behind it
@@ -102,7 +107,7 @@ static void write_map(std::string const& path, ds2i_blob* b) {
 int main(int argc, const char** argv) {
     std::vector<const char*> pos;
     bool check = false, bad_flag = false;
-    const char *assign_path = nullptr, *ranges_text = nullptr;
+    const char *assign_path = nullptr, *ranges_text = nullptr, *wand_path = nullptr;
     int device = 0;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -113,6 +118,9 @@ int main(int argc, const char** argv) {
         } else if (a == "--ranges" && i + 1 < argc) {
             bad_flag = bad_flag || ranges_text;
             ranges_text = argv[++i];
+        } else if (a == "--wand" && i + 1 < argc) {
+            bad_flag = bad_flag || wand_path;
+            wand_path = argv[++i];
         } else if (a == "--device" && i + 1 < argc) {
             char* end = nullptr;
             const long v = std::strtol(argv[++i], &end, 10);
@@ -142,6 +150,25 @@ int main(int argc, const char** argv) {
             }
         }
         tool::mapped_file in(pos[1]);
+        std::unique_ptr<tool::mapped_file> wand;
+        if (wand_path) { // held against the input's shape on the host: no device yet
+            try {
+                wand.reset(new tool::mapped_file(wand_path));
+            } catch (std::exception const& e) {
+                std::cerr << "ERROR: " << e.what() << "\nusage: " << argv[0] << USAGE;
+                return 2;
+            }
+            uint64_t num_docs = 0, lists = 0;
+            tool::hip_ok(ds2i_hip_image_shape(from, in.data, in.size, &num_docs, &lists), "ds2i_hip_image_shape");
+            ds2i_blob *nl = nullptr, *mw = nullptr;
+            tool::hip_ok(ds2i_wand_arrays(wand->data, wand->size, &nl, &mw), "ds2i_wand_arrays");
+            const uint64_t wdocs = ds2i_blob_size(nl) / 4, wterms = ds2i_blob_size(mw) / 4;
+            ds2i_blob_free(nl);
+            ds2i_blob_free(mw);
+            if (wdocs != num_docs || wterms < lists)
+                throw std::runtime_error("--wand: the wand data holds " + std::to_string(wdocs) + " documents and " + std::to_string(wterms) +
+                                         " terms, the index " + std::to_string(num_docs) + " and " + std::to_string(lists));
+        }
         std::unique_ptr<extracted> c;
         std::vector<uint32_t> ranged;
         const uint32_t* shard_of = nullptr;
@@ -179,6 +206,14 @@ int main(int argc, const char** argv) {
             tool::write_blob(base.c_str(), got.s[s].image);
             write_map(base + ".docs", got.s[s].doc_map);
             write_map(base + ".terms", got.s[s].term_map);
+            if (wand) {
+                ds2i_blob* w = nullptr;
+                tool::hip_ok(ds2i_split_wand(wand->data, wand->size, (const uint32_t*)ds2i_blob_data(got.s[s].doc_map), ds2i_blob_size(got.s[s].doc_map) / 4,
+                                             (const uint32_t*)ds2i_blob_data(got.s[s].term_map), ds2i_blob_size(got.s[s].term_map) / 4, &w),
+                             "ds2i_split_wand");
+                tool::write_blob((base + ".wand").c_str(), w);
+                ds2i_blob_free(w);
+            }
             bytes += ds2i_blob_size(got.s[s].image);
             merge << " " << pos[2] << " " << base << " --docs " << base << ".docs --terms " << base << ".terms";
         }

@@ -142,9 +142,10 @@ int ds2i_merge_postings(const ds2i_merge_postings_source* src, uint32_t nsrc, ui
  * sorted; a caller who wants another order remaps the shard afterwards. doc_map and term_map are the maps ds2i_merge_postings and
  * ds2i_hip_merge_indexes take: with no document dropped and every input list nonempty, merging the shards with them gives the input
  * back. A shard may come back with no documents or with no lists.
- * Not split: wand data (an index holds none, and a shard's max_term_weight depends on the shard's own average document length: build
- * it from sizes[doc_map] with ds2i_hip_build_wand), and scores (BM25 over a shard uses the shard's own number of documents and document
- * frequencies: shard scores are not the global ones).
+ * Wand data and scores: an index holds no wand data; ds2i_split_wand (below) gives a shard the collection's own normalisation, and
+ * ds2i_hip_index_set_collection_stats (ds2i_hip.h) the collection's number of documents and document frequencies, so that a shard
+ * scores as the collection does; ds2i_hip_shard_set_* (ds2i_hip.h) queries the shards of a split as one index. A shard opened without
+ * them scores by its own statistics, which are not the collection's.
  * split_postings: the host twin of ds2i_hip_split_postings (ds2i_hip.h). Checks, all DS2I_EINVAL, in this order: null arguments and the
  * offsets; nshards == 0; 2^32 documents or lists; the first document whose shard_of is neither < nshards nor the drop value (named). A
  * doc-id >= num_docs among the postings is DS2I_EFORMAT. Out: *shards = an array of nshards ds2i_split_shard whose members are blobs
@@ -161,6 +162,45 @@ typedef struct ds2i_split_shard {
 int ds2i_split_postings(uint64_t num_docs, uint64_t nlists, const uint64_t* list_offsets, const uint32_t* docs, const uint32_t* freqs,
                         const uint32_t* shard_of, uint32_t nshards, int threads, ds2i_split_shard** shards);
 void ds2i_split_free(ds2i_split_shard* shards, uint32_t nshards);
+
+/* A shard's wand data under the COLLECTION's normalisation, with no pass over the postings: norm_lens[i] = the collection's
+ * norm_lens[doc_map[i]] (ndocs entries), max_term_weight[j] = the collection's max_term_weight[term_map[j]] (nterms entries); the maps
+ * are a split's, and need not be increasing. This is on purpose NOT the image ds2i_wand_create gives over the shard: that one divides by
+ * the shard's own average document length, and scores under it are not the collection's. The gathered maximum is an upper bound of the
+ * maximum over the shard's own postings, which is all the pruning needs (the exact maximum is not computed). Checks, all DS2I_EINVAL:
+ * null arguments (a map may be NULL when its length is 0); the first doc_map entry, then the first term_map entry, at or past the
+ * image's arrays, named. An image that does not parse is DS2I_EFORMAT. On an error nothing is written.
+ * wand_arrays: an image read back into its two float arrays (blobs of float32; either output may be NULL). */
+int ds2i_split_wand(const void* wand_image, size_t bytes, const uint32_t* doc_map, uint64_t ndocs, const uint32_t* term_map, uint64_t nterms,
+                    ds2i_blob** out);
+int ds2i_wand_arrays(const void* wand_image, size_t bytes, ds2i_blob** norm_lens, ds2i_blob** max_term_weight);
+
+/* Merging top-k rows: what several shards answered for the same nq queries with DS2I_OP_TOPK_DOCS becomes what the whole collection
+ * answers. The semantics, in integers:
+ *   - A candidate is entry i < lens[q] of row set r for query q.
+ *   - Its key is the u64 ((0xFFFFFFFF - bits(score)) << 32) | g, with g = doc_map ? doc_map[doc] : doc and bits() the float's bit pattern.
+ *   - The output row of q holds the min(k, sum over r of lens[q]) candidates of smallest key, in ascending key order: score descending,
+ *     equal scores by collection doc-id ascending, and the smaller ids on a tie at the k-th place -- the rule DS2I_OP_TOPK_DOCS has for
+ *     one index. out_lens[q] is that number.
+ *   - Rows are padded as a single index pads them: -inf for scores, 0xFFFFFFFF for docs.
+ *   - An input row is what DS2I_OP_TOPK_DOCS returns: sorted by score descending, equal scores by local doc-id ascending. The device
+ *     form relies on it (this twin sorts every candidate and does not).
+ * The bit pattern of a non-negative finite float orders as the float, and BM25 scores here are positive; the order is total and
+ * integer, so ds2i_hip_merge_topk (ds2i_hip.h, the device form) and this twin agree element for element.
+ * Checks, all DS2I_EINVAL, in this order (the device form makes them before a device is looked for): null arguments; nrows == 0 or
+ * nrows > 64 (DS2I_HIP_MAX_SHARDS); k == 0 or k > 1024 (DS2I_HIP_MAX_K_LONG); the first lens[q] > k; the first candidate whose score has
+ * its sign bit set or is not finite; the first candidate whose local id is >= map_len. Each names row set, query and position.
+ * nq == 0 succeeds and writes nothing. Two candidates of one query with the same collection id are the caller's error: the result may
+ * hold both, and nothing is read or written out of bounds because of it. At most 16 host threads (threads <= 0: up to 16). */
+typedef struct ds2i_topk_rows {      /* what one shard answered for nq queries with DS2I_OP_TOPK_DOCS */
+    const float* scores;             /* nq * k */
+    const uint32_t* docs;            /* nq * k, local doc-ids */
+    const uint32_t* lens;            /* nq, each <= k */
+    const uint32_t* doc_map;         /* local -> collection doc-id; NULL: the ids are the collection's already */
+    uint64_t map_len;
+} ds2i_topk_rows;
+int ds2i_merge_topk(const ds2i_topk_rows* rows, uint32_t nrows, uint32_t nq, uint32_t k, float* out_scores, uint32_t* out_docs,
+                    uint32_t* out_lens, int threads);
 
 /* Indexing documents: a forward collection inverted into posting lists, and the primitive behind it, the transposition of a sparse
  * matrix in CSR form. The host twins of ds2i_hip_invert_postings and ds2i_hip_transpose_postings (ds2i_hip.h), which return the same

@@ -124,6 +124,18 @@ void ds2i_hip_index_close(ds2i_hip_index* idx);
 uint64_t ds2i_hip_index_size(const ds2i_hip_index* idx);
 uint64_t ds2i_hip_index_num_docs(const ds2i_hip_index* idx);
 uint64_t ds2i_hip_index_device_bytes(const ds2i_hip_index* idx);
+/* Collection-wide BM25 statistics on an open index, for an index that holds a shard of a collection: every batch planned afterwards
+ * (one-shot, prepared and pipelined alike) weighs a query term by bm25::query_term_weight(qtf, df[term], num_docs) instead of the
+ * list's own length and the index's own number of documents. Nothing else changes: list order, work units, routes and kernel choice
+ * keep using the shard's own list lengths, and the bounds that are products of the query weight follow from it as before (wand /
+ * maxscore / ranked_or as streams drive a query by its lists in the order of those bounds and give no units to the lists whose bounds
+ * lie below the query's static floor, as they always did: there the units follow from the query weight too). df has
+ * ndf == ds2i_hip_index_size(idx) entries and is copied. num_docs == 0 && df == NULL clears the statistics. Checks, in this order, all
+ * DS2I_EINVAL, nothing changed on an error: null index; ndf != ds2i_hip_index_size(idx) (or df == NULL with num_docs != 0); num_docs <
+ * ds2i_hip_index_num_docs(idx); the first term whose df[t] is below its list length or above num_docs, named. Batches already prepared
+ * keep their weights. The call must NOT run concurrently with planning on the same index (prepare, submit or a one-shot query on
+ * another thread): the handle is not re-entrant. */
+int ds2i_hip_index_set_collection_stats(ds2i_hip_index* idx, uint64_t num_docs, const uint32_t* df, uint64_t ndf);
 /* What the upload put into HBM beside the index image. The pruning tables are accelerators: an upload that cannot
  * afford them (or was told not to build them) still succeeds and the query kernels take their slower table-free paths,
  * so a caller that cares checks has_range_tables here (the library also says so once on stderr). With
@@ -483,9 +495,9 @@ void ds2i_hip_merge_ms(double ms[4 + 4]);
  * the doc map and the term map that ds2i_hip_merge_indexes takes. shard_of[d] is the shard of document d, < nshards, or
  * DS2I_SPLIT_DROP (ds2i_build.h) to delete the document. ds2i_split_postings (ds2i_build.h, the host twin) states the semantics:
  * order-preserving local doc-ids, lists without a posting in the shard dropped, nothing sorted. With no document dropped, merging the
- * shards with their maps gives the input back, byte for byte when the kinds agree. Neither wand data nor scores are split: an index
- * holds no wand data, and a shard's max_term_weight depends on the shard's own average document length; build it from
- * sizes[doc_map] with ds2i_hip_build_wand. BM25 over a shard uses the shard's own number of documents and document frequencies.
+ * shards with their maps gives the input back, byte for byte when the kinds agree. An index holds no wand data: ds2i_split_wand
+ * (ds2i_build.h) makes a shard's under the collection's normalisation, ds2i_hip_index_set_collection_stats gives an open shard the
+ * collection's BM25 statistics, and ds2i_hip_shard_set_* below queries the shards as one index, in the collection's doc-ids.
  *
  * A shard's postings are the stable compaction of the source postings by the flag shard_of[doc-id] == shard. The source postings are
  * cut into windows of ds2i_hip_split_window() postings. Per shard: a count kernel (kept postings per window, a ballot and a popcount
@@ -621,6 +633,70 @@ int ds2i_hip_order_index(int device, int index_kind, const void* image, size_t b
  * degrees kernels, ms[4] the gains kernels, ms[5] the keys kernels and the sorts of the halves, ms[6] the swap kernels, ms[7] the
  * compose kernels and the final map. device_ms is their sum. */
 void ds2i_hip_order_ms(double ms[8]);
+
+/* Querying document shards as one index. A collection cut by ds2i_hip_split_index answers a query batch as the whole collection would,
+ * in the collection's doc-ids, from three parts: the collection's BM25 statistics on every shard (ds2i_hip_index_set_collection_stats),
+ * every shard's wand data under the collection's normalisation (ds2i_split_wand, ds2i_build.h), and a merge of the shards' top-k rows.
+ *
+ * ds2i_hip_merge_topk: the device form of ds2i_merge_topk (ds2i_build.h, the host twin, which states the key order and the checks; all
+ * of them are made before a device is looked for). All pointers are host pointers: the rows and the maps go up, one kernel merges, the
+ * result comes down. The kernel takes one wavefront per query, and wavefronts stride over the queries (at most
+ * ds2i_hip_merge_topk_grid(compute units, k) of them: as many workgroups of one wavefront as a compute unit's LDS and its 32 wavefront
+ * slots hold at that k, 5 at k = 1024 and 32 from k = 128 down). A row arrives sorted by score with its equal-score runs in LOCAL id order, which
+ * under an increasing doc_map is key order; the host marks the row sets whose map is not increasing, and such a row is first sorted by
+ * key in LDS (a bitonic network over at most 1024 keys). Rows are then folded one at a time into a best-k buffer in LDS: both sides
+ * are sorted, an element's rank in the union is its own position plus a binary search in the other side (lower bound one way, upper
+ * bound the other: ranks stay distinct on duplicate keys), and elements of rank < k are stored at their rank. No atomics; three
+ * buffers of 8 * (k rounded up to a power of two) bytes of dynamic LDS. device_ms (may be NULL): the hipEvent time of the kernel. */
+#define DS2I_HIP_MAX_SHARDS 64
+struct ds2i_topk_rows; /* ds2i_build.h */
+int ds2i_hip_merge_topk(int device, const struct ds2i_topk_rows* rows, uint32_t nrows, uint32_t nq, uint32_t k, float* out_scores,
+                        uint32_t* out_docs, uint32_t* out_lens, double* device_ms);
+uint32_t ds2i_hip_merge_topk_grid(uint32_t compute_units, uint32_t k);
+
+/* The shard set: nshards sources, each an index image of its own kind on its own device with the maps of a split.
+ * open. Checks, in this order, all before a device is looked for: null arguments (DS2I_EINVAL); nshards == 0 or above
+ * DS2I_HIP_MAX_SHARDS; the kinds; every image through the host parse (DS2I_EFORMAT, as ds2i_hip_image_shape gives); map_len and
+ * terms_len against the parsed shape; every term map strictly increasing and < collection_terms; every doc map < collection_docs with
+ * no id taken twice across the whole set (one bit per document, the first offender named). Statistics: stats_num_docs == 0 means the
+ * sum of the shards' documents; stats_df == NULL means, per collection term, the sum of the lengths of the shard lists mapped to it, so
+ * that a set made from a split with nothing dropped scores exactly as the unsplit index; a given stats_df (collection_terms entries)
+ * must be at least that sum and at most stats_num_docs, per term (DS2I_EINVAL, the term named). Then every shard that has lists and
+ * documents is opened with ds2i_hip_index_open on its device and given its statistics; a shard with no lists or no documents is
+ * accepted and skipped. wand_image NULL: the shard answers `and` / `or` only (a ranked operator is DS2I_ENOWAND). The merge runs on the
+ * device of the first opened shard, where the doc maps are kept. The images and maps are not referenced after the call.
+ * query: op is one of the four ranked operators (DS2I_OP_TOPK_DOCS is implied and accepted) or DS2I_OP_AND / DS2I_OP_OR.
+ * DS2I_OP_AND_FREQ, DS2I_OP_OR_FREQ, DS2I_OP_REFERENCE_ORDER and, for a ranked operator, k == 0 or k > DS2I_HIP_MAX_K_LONG are
+ * DS2I_EINVAL; a term >= collection_terms is DS2I_ETERM. Per shard the queries are translated on the host by a binary search in the
+ * term map: repeats are kept (they are the query term frequencies); for `and` and `ranked_and` a query with a distinct term absent from
+ * the shard is sent as the empty query; for the union operators absent terms are dropped. The shards' batches are submitted together,
+ * each through a pipeline of its own, and collected; the rows come back through the public fetch and go up to the merge device, where
+ * ds2i_hip_merge_topk's kernel merges them. Ranked: out_topk / out_topk_docs (nq * k each, collection doc-ids) and out_topk_len (nq) are
+ * the merged rows, out_count[q] the merged row's length (out_count and out_topk_len may be NULL). and / or: out_count[q] is the sum of the
+ * shards' counts and no other output is touched.
+ * Ties: if every doc map is increasing, the set breaks ties as the whole index does. Otherwise a tie at a shard's own k-th place is
+ * broken by that shard's local ids; the merge still orders by collection id.
+ * stats (may be NULL): per source its batch's kernel_ms (0 for a skipped shard), the merge kernel's ms, and the host milliseconds of the
+ * translation. A set is not re-entrant. */
+typedef struct ds2i_shard_source {
+    int device, kind;
+    const void* image;      size_t bytes;
+    const void* wand_image; size_t wand_bytes;   /* ds2i_split_wand's; NULL: the and / or counts only */
+    const uint32_t* doc_map;  uint64_t map_len;  /* local -> collection doc-id, injective */
+    const uint32_t* term_map; uint64_t terms_len;/* local -> collection term, strictly increasing */
+} ds2i_shard_source;
+typedef struct ds2i_hip_shard_stats {
+    double kernel_ms[DS2I_HIP_MAX_SHARDS];
+    double merge_ms, translate_ms;
+    uint32_t shards_open;
+} ds2i_hip_shard_stats;
+typedef struct ds2i_hip_shard_set ds2i_hip_shard_set;
+int ds2i_hip_shard_set_open(const ds2i_shard_source* src, uint32_t nshards, uint64_t collection_docs, uint64_t collection_terms,
+                            uint64_t stats_num_docs, const uint32_t* stats_df, ds2i_hip_shard_set** out);
+int ds2i_hip_shard_set_query(ds2i_hip_shard_set* s, int op, uint32_t k, const uint32_t* terms, const uint32_t* query_offsets,
+                             uint32_t nq, uint64_t* out_count, float* out_topk, uint32_t* out_topk_docs, uint32_t* out_topk_len,
+                             ds2i_hip_shard_stats* stats);
+void ds2i_hip_shard_set_close(ds2i_hip_shard_set* s);
 
 /* Inspection of the upload-time pruning tables of one list (test hooks; both tables exist only with wand data).
  * block weights: bmw[b] = max over block b's postings of bm25::doc_term_weight(freq, norm_len[doc]) (the block-level
