@@ -22,8 +22,9 @@ struct ScoreHist {
     // lower bound of the k-th score of the union, or -inf (relaxed agent-scope loads: the counters are updated by
     // other CUs' atomics and must not come from a stale L1 line)
     struct Snapshot { uint32_t x, y, z, w; }; // lane l: buckets 252-4l .. 255-4l (highest scores in lane 0)
-    DS2I_DEV Snapshot load() const {
-        const unsigned int* hp = h + 252u - 4u * lane_id();
+    DS2I_DEV Snapshot load() const { return load(lane_id()); }
+    DS2I_DEV Snapshot load(uint32_t lane) const { // lane = the caller's lane_id()
+        const unsigned int* hp = h + 252u - 4u * lane;
         Snapshot s;
         s.x = __hip_atomic_load(hp + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         s.y = __hip_atomic_load(hp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

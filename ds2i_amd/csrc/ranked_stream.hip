@@ -54,8 +54,9 @@ namespace {
 #ifndef DS2I_RS_OCC4
 #define DS2I_RS_OCC4 6 // (round 5, on the leaner kernel: 5 -> 6 waves per SIMD for 3 / 4 lists +3.5 % end to end; 6 -> 7 / 8 for 2 lists: nothing)
 #endif
-// 5..8 lists: what fits -- one more decoded block (1 KB of LDS) and nine more parked scalars per list:
-// 7 936 .. 11 008 bytes of LDS per wave
+// 5..16 lists: one more decoded block (1 KB of LDS) and nine more parked scalars per list -- 8 960 / 11 008 / 19 968 bytes of LDS per
+// wave and 104 / 110 / 134 registers at capacity 6 / 8 / 16. The figures below are what the source ASKS for; at capacity 8
+// that is three waves per SIMD although its 110 registers would allow four (the compiler's own figure).
 #define RS_WAVES(NT) ((NT) <= 2 ? DS2I_RS_OCC2 : (NT) <= 4 ? DS2I_RS_OCC4 : (NT) <= 6 ? 4 : (NT) <= 8 ? 3 : 2)
 
 template <int NT>
@@ -69,6 +70,30 @@ struct LdsRS {
     uint32_t fj[NT - 1][128];    // and its freqs
     uint32_t fw[64];             // the query's shared floor word, as fetched an iteration ago (LDS-DMA: one copy per lane)
 };
+// Three and four lists (6 waves per SIMD, DS2I_RS_OCC4): the same members, with stage C's staging of list j's block laid over list
+// 1's gathered bytes -- 6400 bytes instead of 6912, so that a CU's 160 KB hold the 24 waves the launch bound asks for (6912: 23) whether
+// LDS is handed out in units of 128, 512 or 1280 bytes (6400 = 5 x 1280; rounded up to 6656 it is 24.6 waves). Lifetimes that make
+// it safe, all within one wave:
+//   gb   written by the LDS-DMA gathers issued at the rotate (the last step of an iteration), complete at stage B's counted wait of
+//        the next iteration, read ONCE, right after that wait (x0 / x1), into registers -- before stage C of that iteration can start;
+//   stb  written and read only inside stage C's decode of a block of list j (rs_stage_block's plain stores, rs_decode_full's reads, all
+//        consumed before the decode returns), which lies between that read and the next rotate.
+// A wave's LDS instructions execute in order and the gathers' asm statements are memory barriers for the compiler, so neither side
+// can move past the other. (The other capacities are bound by registers, not by LDS: they keep the layout above.)
+template <>
+struct LdsRS<4> {
+    uint32_t stage[3][STAGE_DW];
+    uint32_t xs[3][XSLOT_DW];
+    union {
+        uint32_t gb[2][64];
+        uint32_t stb[STAGE_DW];
+    };
+    uint32_t xsb[XSLOT_DW];
+    uint32_t dj[3][128];
+    uint32_t fj[3][128];
+    uint32_t fw[64];
+};
+static_assert(sizeof(LdsRS<4>) == 6400 && sizeof(LdsRS<2>) == 4864, "LDS per wave: 24 waves of <4> per CU");
 
 // stage C as ONE loop body over the lists (run-time list index) from this capacity on; below it the body is unrolled per list
 #ifndef RS_ONE_BODY
@@ -152,8 +177,12 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
             }
         };
         rs_for<1, NT>(bind_one);
+        // Capacity 4 runs six waves per SIMD, 80 registers a lane, and is the longest kernel of the headline step: what only rare paths read
+        // of the unit's scalars waits in lanes of `cold` (X_RT .. below) instead of in scalar registers the compiler would have to spill,
+        // and rsc[] for the list loop has its lanes there too instead of a register of its own
+        constexpr bool LEAN = NT == 4;
         float rscv = 0.f; // lane j = rsc[j] (read by stage C's one-body list loop)
-        if constexpr (NT >= RS_ONE_BODY) {
+        if constexpr (NT >= RS_ONE_BODY && !LEAN) {
             auto spread = [&](auto jc) __attribute__((always_inline)) { constexpr int j = decltype(jc)::value; rscv = lane == (uint32_t)j ? rsc[j] : rscv; };
             rs_for<1, NT>(spread);
         }
@@ -170,6 +199,11 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         // if the dense lists carry bitmaps, else 0 (X_ND); the shared floor word (X_FW) and histogram (X_SH, X_BOUND: its counters, the score bound that scales them); AND:
         // the unit's segment of the match buffer (X_OUT)
         enum { X_HD = (NT - 1) * C_PER, X_ND = X_HD + 2, X_FW = X_ND + 1, X_SH = X_FW + 2, X_BOUND = X_SH + 2, X_OUT = X_BOUND + 1, X_END = X_OUT + 2 };
+        // LEAN: lists 2..: range table (X_RT, two lanes each) and shift (X_RSH); rsc[j] in lane X_RSC + j; the unit's query, whether it is
+        // the whole query, its first block; list 0's first table row and its tail entry
+        enum { X_RT = X_END, X_RSH = X_RT + 2 * (NT - 2), X_RSC = X_RSH + (NT - 2), X_Q = X_RSC + NT, X_WHOLE = X_Q + 1, X_BLKB = X_WHOLE + 1, X_BB0 = X_BLKB + 1,
+               X_TL0 = X_BB0 + 1, X_LEAN_END = X_TL0 + 2 };
+        static_assert(!LEAN || X_LEAN_END <= 64, "the lean capacity keeps one register of cold lanes");
         constexpr int NCOLD = (X_END + 63) / 64;
         uint32_t cold[NCOLD];
 #pragma unroll
@@ -204,11 +238,37 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         // RS_BM in rsh[1] = list 1's byte is a bitmap byte; shift_of() is the list's shift proper.
         constexpr bool HF = AND || RS_HINT_FIRST(NT); // (AND: the hint is the answer, the weight says nothing it needs)
         constexpr uint32_t RS_BM = 256u;
+        if constexpr (LEAN) {
+            auto park_rt = [&](auto jc) __attribute__((always_inline)) {
+                constexpr int j = decltype(jc)::value;
+                cset64(X_RT + 2 * (j - 2), (unsigned long long)(uintptr_t)rt[j]);
+                cset(X_RSH + (j - 2), rsh[j]);
+            };
+            rs_for<2, NT>(park_rt);
+            auto park_rsc = [&](auto jc) __attribute__((always_inline)) { constexpr int j = decltype(jc)::value; cset(X_RSC + j, __float_as_uint(rsc[j])); };
+            rs_for<1, NT>(park_rsc);
+            cset(X_Q, q);
+            cset(X_WHOLE, whole ? 1u : 0u);
+            cset(X_BLKB, blk_begin);
+            cset(X_BB0, bb0);
+            cset64(X_TL0, qt[0].aux1);
+        }
         auto shift_of = [&](auto jc) __attribute__((always_inline)) -> uint32_t {
             constexpr int j = decltype(jc)::value;
             if constexpr (HF && j == 1) return rsh[1] & 31u;
+            else if constexpr (LEAN && j >= 2) return cget(X_RSH + (j - 2));
             else return rsh[j];
         };
+        auto rt_of = [&](auto jc) __attribute__((always_inline)) -> const uint8_t* { // list j's range table
+            constexpr int j = decltype(jc)::value;
+            if constexpr (LEAN && j >= 2) return (const uint8_t*)(uintptr_t)cget64(X_RT + 2 * (j - 2));
+            else return rt[j];
+        };
+        auto q_of = [&]() __attribute__((always_inline)) -> uint32_t { if constexpr (LEAN) return cget(X_Q); else return q; };
+        auto whole_of = [&]() __attribute__((always_inline)) -> bool { if constexpr (LEAN) return cget(X_WHOLE) != 0u; else return whole; };
+        auto blk_begin_of = [&]() __attribute__((always_inline)) -> uint32_t { if constexpr (LEAN) return cget(X_BLKB); else return blk_begin; };
+        auto tl0_of = [&]() __attribute__((always_inline)) -> unsigned long long { if constexpr (LEAN) return cget64(X_TL0); else return rs_uniform64(qt[0].aux1); }; // list 0's tail entry
+        auto bb0_of = [&]() __attribute__((always_inline)) -> uint32_t { if constexpr (LEAN) return cget(X_BB0); else return bb0; };
         bool hint_first = false;
         const uint8_t* gt1 = rt[1];
         {
@@ -299,8 +359,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
             s_e = make_uint2(0xFFFFFFFFu, 0u);
             float s_w = 0.f;
             {   // (once per 63 blocks: the table pointers are re-derived here rather than carried through the loop)
-                const uint2* const tab0 = (const uint2*)rs_args()->skip + bb0;
-                const float* const w0tab = rs_args()->bmw + bb0;
+                const uint2* const tab0 = (const uint2*)rs_args()->skip + bb0_of();
+                const float* const w0tab = rs_args()->bmw + bb0_of();
                 if (idx < blk_end) { s_e = tab0[idx]; s_w = w0tab[idx]; }
                 LC(PH_PROLOG, lines_of(tab0 + idx, idx < blk_end, 8u) + lines_of(w0tab + idx, idx < blk_end, 4u));
             }
@@ -319,8 +379,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 const uint32_t lo = b2 >> lsh, hi = t2 >> lsh;
                 const bool fits = hi - lo < 16u;
                 const uint64_t loff = lvl == 0 ? 0ull : lvl == 1 ? g.off[1] : g.off[2]; // (selects: a run-time index would put the array into scratch)
-                const uint32_t m = max_of_bytes16(rt[j] + loff + (fits ? lo : 0u), fits ? hi - lo + 1u : 1u);
-                LC(PH_PROLOG, lines_of(rt[j] + loff + (fits ? lo : 0u), true, 16u));
+                const uint32_t m = max_of_bytes16(rt_of(jc) + loff + (fits ? lo : 0u), fits ? hi - lo + 1u : 1u);
+                LC(PH_PROLOG, lines_of(rt_of(jc) + loff + (fits ? lo : 0u), true, 16u));
                 const uint32_t best = (row && fits) ? m : 255u; // (255 = the list maximum)
                 dead = dead || best == 0u;
                 acc = acc + rsc[j] * (float)best;
@@ -347,7 +407,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                     return 1u;
                 }
                 if (s_valid && s_first + 64u >= blk_end) return 0u;
-                s_fill(s_valid ? s_first + 63u : (blk_begin ? blk_begin - 1u : 0u)); // (once per 63 blocks)
+                s_fill(s_valid ? s_first + 63u : (blk_begin_of() ? blk_begin_of() - 1u : 0u)); // (once per 63 blocks)
                 s_valid = 1u;
                 s_bm_examined += 1;
                 s_bytes += 4;
@@ -403,7 +463,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 const uint32_t szA = ((A.blk + 1u) * 128u <= n0) ? 128u : (n0 & 127u);
                 uint32_t v0, v1, fv0, fv1, consA, consF;
                 if (__builtin_expect(szA == 128u, 1)) rs_decode_full(L.stage[bufA], L.xs[bufA], data0 + A.ep, rs_args()->xovf, v0, v1, fv0, fv1, consA, consF);
-                else rs_tail(rs_args()->tails, rs_uniform64(qt[0].aux1), szA, v0, v1, fv0, fv1, consA, consF);
+                else rs_tail(rs_args()->tails, tl0_of(), szA, v0, v1, fv0, fv1, consA, consF);
                 const uint32_t g0 = (lane < szA) ? v0 + 1u : 0u, g1 = (lane + 64 < szA) ? v1 + 1u : 0u;
                 const uint32_t i0 = wave_incl_scan(g0);
                 const uint32_t i1 = wave_incl_scan(g1) + bcast(i0, 63);
@@ -457,10 +517,10 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                             uint32_t bmm = 0; // bit j: list j answers from its bitmap (derived here, for the survivors' round trip only)
                             auto hload = [&](auto jc) __attribute__((always_inline)) {
                                 constexpr int j = decltype(jc)::value;
-                                const uint8_t* ht = rt[j] + hdelta;
+                                const uint8_t* ht = rt_of(jc) + hdelta;
                                 uint32_t sj = shift_of(jc);
                                 if ((uint32_t)j < nt && nd_bm != 0u && RmwLevels::has_bitmap(cget((j - 1) * C_PER + C_N), nd_bm)) {
-                                    ht = rt[j] + RmwLevels(nd_bm, sj).bytes();
+                                    ht = rt_of(jc) + RmwLevels(nd_bm, sj).bytes();
                                     sj = 3u;
                                     bmm |= 1u << j;
                                 }
@@ -493,9 +553,9 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                     if (!AND && !no_thr && (ballot(ok0) | ballot(ok1))) {
                         auto wload = [&](auto jc) __attribute__((always_inline)) {
                             constexpr int j = decltype(jc)::value;
-                            gP0 |= (GP)((ok0 & ((uint32_t)j < nt)) ? (uint32_t)rt[j][dB0 >> shift_of(jc)] : 0u) << (8 * (j - 1));
-                            gP1 |= (GP)((ok1 & ((uint32_t)j < nt)) ? (uint32_t)rt[j][dB1 >> shift_of(jc)] : 0u) << (8 * (j - 1));
-                            LC(PH_FREQS, lines_of(rt[j] + (dB0 >> shift_of(jc)), ok0, 1u) + lines_of(rt[j] + (dB1 >> shift_of(jc)), ok1, 1u));
+                            gP0 |= (GP)((ok0 & ((uint32_t)j < nt)) ? (uint32_t)rt_of(jc)[dB0 >> shift_of(jc)] : 0u) << (8 * (j - 1));
+                            gP1 |= (GP)((ok1 & ((uint32_t)j < nt)) ? (uint32_t)rt_of(jc)[dB1 >> shift_of(jc)] : 0u) << (8 * (j - 1));
+                            LC(PH_FREQS, lines_of(rt_of(jc) + (dB0 >> shift_of(jc)), ok0, 1u) + lines_of(rt_of(jc) + (dB1 >> shift_of(jc)), ok1, 1u));
                         };
                         rs_for<1, NT>(wload);
                         rs_settle_vm();
@@ -511,8 +571,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                         auto load_one = [&](auto jc) __attribute__((always_inline)) {
                             constexpr int j = decltype(jc)::value;
                             if ((uint32_t)j >= nt) return;
-                            gP0 |= (GP)(uint32_t)rt[j][(ok0 ? dB0 : 0u) >> shift_of(jc)] << (8 * (j - 1));
-                            gP1 |= (GP)(uint32_t)rt[j][(ok1 ? dB1 : 0u) >> shift_of(jc)] << (8 * (j - 1));
+                            gP0 |= (GP)(uint32_t)rt_of(jc)[(ok0 ? dB0 : 0u) >> shift_of(jc)] << (8 * (j - 1));
+                            gP1 |= (GP)(uint32_t)rt_of(jc)[(ok1 ? dB1 : 0u) >> shift_of(jc)] << (8 * (j - 1));
                         };
                         rs_for<2, NT>(load_one);
                         auto test_one = [&](auto jc) __attribute__((always_inline)) {
@@ -557,7 +617,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                     // not in the list -- settled here, by one more byte, instead of by a block search and a block decode in stage C.
                     auto hint_one = [&](auto jc) __attribute__((always_inline)) {
                         constexpr int j = decltype(jc)::value;
-                        const uint8_t* const ht = rt[j] + hdelta;
+                        const uint8_t* const ht = rt_of(jc) + hdelta;
                         const bool hashint = shift_of(jc) != 0u && (uint32_t)j < nt; // (one doc-id per entry: the weight byte was the answer)
                         const uint32_t h0 = (ok0 & hashint) ? (uint32_t)ht[dB0 >> shift_of(jc)] : 255u, h1 = (ok1 & hashint) ? (uint32_t)ht[dB1 >> shift_of(jc)] : 255u;
                         LC(PH_MEMBER, lines_of(ht + (dB0 >> shift_of(jc)), ok0 & hashint, 1u) + lines_of(ht + (dB1 >> shift_of(jc)), ok1 & hashint, 1u));
@@ -572,6 +632,15 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                 if (__builtin_expect((ballot(ok0) | ballot(ok1)) != 0, 0)) {
                     LC(PH_C_LIVEROUNDS, 1);
                     // ---------------- stage C: somebody of block B may enter the heap: norm_len, exact list-0 score
+                    // (LEAN: block A's state is not stage C's business, and stage C's decode of a block of list j is where the kernel needs
+                    // the most registers. A's doc-ids wait in the side-slot buffers of blocks A and B -- both decoded by now, the next
+                    // prefetch into either is issued after this stage -- and its freq-only bounds are computed again afterwards from its
+                    // parked freqs: same inputs, same operations, same bits. The lane that writes is the lane that reads: no fence.)
+                    if constexpr (LEAN && !AND) {
+                        L.xs[bufA][lane] = dA0;
+                        L.xs[bufB][lane] = dA1;
+                        asm volatile("" ::: "memory"); // (the values go to LDS here and come back below, whatever the optimiser can see through)
+                    }
                     const float* const norm_lens = rs_args()->norm_lens;
                     const uint8_t* const arena = rs_args()->arena;
                     // (list 1's rows after its current block go out together with the norm_lens: the search they serve comes first
@@ -586,6 +655,14 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                         nl0 = ok0 ? norm_lens[dB0] : 1.f;
                         nl1 = ok1 ? norm_lens[dB1] : 1.f;
                         LC(PH_SCORE, lines_of(norm_lens + dB0, ok0, 4u) + lines_of(norm_lens + dB1, ok1, 4u));
+                        // (LEAN: the rows wait in stage C's own staging area, which nothing uses before the first decode of this stage -- and a
+                        // decode is what ends their use (rows_fresh); as registers they were live across every list's decode)
+                        if constexpr (LEAN) {
+                            L.stb[lane] = rows1.e.x;
+                            L.stb[lane + 64] = rows1.e.y;
+                            L.xsb[lane] = __float_as_uint(rows1.w);
+                            asm volatile("" ::: "memory");
+                        }
                         const uint32_t fB0 = L.stage[bufB][lane], fB1 = L.stage[bufB][lane + 64];
                         pa0 = qw0 * doc_term_weight(fB0, nl0);
                         pa1 = qw0 * doc_term_weight(fB1, nl1);
@@ -608,7 +685,8 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                         if (j >= nt) return;
                         const uint32_t CB = (j - 1u) * C_PER; // this list's lanes of `cold`
                         float rsc_j = 0.f; // rsc[j]: from lane j of rscv where j is a run-time index (an array indexed at run time goes to scratch)
-                        if constexpr (RT) rsc_j = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(rscv), (int)j));
+                        if constexpr (RT && LEAN) rsc_j = __uint_as_float(cget(X_RSC + j));
+                        else if constexpr (RT) rsc_j = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(rscv), (int)j));
                         else rsc_j = rsc[decltype(jc)::value];
                         // (AND: only the candidates list j's hint left open are searched; the others are members already)
                         uint64_t todo0 = AND ? ballot(ok0 & (((need0 >> j) & 1u) != 0u)) : ballot(ok0), todo1 = AND ? ballot(ok1 & (((need1 >> j) & 1u) != 0u)) : ballot(ok1);
@@ -630,7 +708,11 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                             const uint32_t amin = todo0 ? bcast(dB0, (uint32_t)__builtin_ctzll(todo0)) : bcast(dB1, (uint32_t)__builtin_ctzll(todo1));
                             if (curj == 0xFFFFFFFFu || amin > bmj) {
                                 Found fb;
-                                const bool found = find_block_rows(tabj, wtabj, nbj, curj + 1u, amin, fb, rows_fresh ? rows1 : rows_load(tabj, wtabj, nbj, curj + 1u));
+                                Rows fr;
+                                if (!rows_fresh) fr = rows_load(tabj, wtabj, nbj, curj + 1u);
+                                else if constexpr (LEAN && !AND) fr = Rows{make_uint2(L.stb[lane], L.stb[lane + 64]), __uint_as_float(L.xsb[lane])};
+                                else fr = rows1;
+                                const bool found = find_block_rows(tabj, wtabj, nbj, curj + 1u, amin, fb, fr);
                                 LC(PH_FIND, 1);
                                 if (!found) { // list j has nothing >= amin: no later document of list 0 can be a result either
                                     s_bm_examined += 1;
@@ -653,6 +735,7 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                                 }
                                 rows_fresh = false;
                                 const uint8_t* pb = dataj + fb.ep;
+                                if constexpr (LEAN) pb = rs_uniform_ptr(pb); // (a scalar pair, not a register pair per lane across the decode)
                                 LC(PH_C_BDOCS, 1);
                                 LC(PH_DOCS, lines_of(pb + 8u * lane, true, 8u));
                                 const uint32_t szb = ((fb.blk + 1) * 128u <= nj) ? 128u : (nj & 127u);
@@ -773,11 +856,24 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
                         }
                     }
                     if (shared_floor && inserted) { // the histogram moved: what floor does it imply now
-                        const float f = hist().floor(tk.k);
+                        float f;
+                        if constexpr (LEAN) { // (the lane's offset into the histogram is worked out here, not kept in two registers for the kernel's lifetime)
+                            uint32_t l = lane;
+                            asm volatile("" : "+v"(l));
+                            const ScoreHist sh = hist();
+                            f = sh.floor(sh.load(l), tk.k);
+                        } else f = hist().floor(tk.k);
                         if (f > 0.f) {
                             if (lane == 0) __hip_atomic_fetch_max(fwp(), __float_as_uint(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                             if (f > tk.floor) { tk.floor = f; refresh(); }
                         }
+                    }
+                    if constexpr (LEAN && !AND) {
+                        asm volatile("" ::: "memory");
+                        dA0 = L.xs[bufA][lane];
+                        dA1 = L.xs[bufB][lane];
+                        boA0 = qw0 * rs_dtw_bound(L.stage[bufA][lane], min_nl);
+                        boA1 = qw0 * rs_dtw_bound(L.stage[bufA][lane + 64], min_nl);
                     }
                     rs_settle_vm(); // (stage C is over: its loads are settled for the compiler too)
                 }
@@ -818,11 +914,15 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         }
         PT(PH_TOTAL);
         rs_wait_vm<0>(); // (a unit left early -- list exhausted -- may still have a prefetch or gathers in flight)
+        const uint32_t q_end = q_of();
+        const bool whole_end = whole_of();
 #undef cget
 #undef cset
 #undef cget64
 #undef cset64
         KArgs r = rs_args();
+        unsigned long long no_fsum = 0; // (ranked: the freq checksum a unit reports)
+        if constexpr (LEAN) asm volatile("" : "+v"(no_fsum)); // (materialised here: as a constant it was kept in a register pair for the kernel's lifetime)
         if constexpr (STATS) {
             unsigned long long* const clk = r->unit_clock;
             if (clk && lane == 0) clk[2ull * uid + 1] = wall_clock64();
@@ -830,14 +930,14 @@ __global__ void __launch_bounds__(64, waves_for_k(RS_WAVES(NT), NK)) DS2I_KN(k_r
         if constexpr (AND) { // and_query returns the size of the intersection (queries.hpp:85); the parts of a split query are summed by k_merge
             if constexpr (FREQS) for (int o = 32; o; o >>= 1) and_fsum += __shfl_xor(and_fsum, o);
             if (lane == 0) {
-                if (whole) { r->out_count[q] = and_count; if (r->out_freq_sum) r->out_freq_sum[q] = and_fsum; }
+                if (whole_end) { r->out_count[q_end] = and_count; if (r->out_freq_sum) r->out_freq_sum[q_end] = and_fsum; }
                 else { r->unit_count[uid] = and_count; r->unit_freq_sum[uid] = and_fsum; }
             }
-        } else if (whole) {
-            if (lane == 0) { r->out_count[q] = tk.n; if (r->out_freq_sum) r->out_freq_sum[q] = 0; }
-            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q, tk DS2I_DOCS_ARG(r->out_topk_docs));
+        } else if (whole_end) {
+            if (lane == 0) { r->out_count[q_end] = tk.n; if (r->out_freq_sum) r->out_freq_sum[q_end] = no_fsum; }
+            store_topk_rs(r->out_topk, r->out_topk_len, tk.k, q_end, tk DS2I_DOCS_ARG(r->out_topk_docs));
         } else {
-            if (lane == 0) { r->unit_count[uid] = tk.n; r->unit_freq_sum[uid] = 0; }
+            if (lane == 0) { r->unit_count[uid] = tk.n; r->unit_freq_sum[uid] = no_fsum; }
             store_topk_rs(r->unit_topk, r->unit_topk_len, tk.k, uid, tk DS2I_DOCS_ARG(r->unit_topk_docs));
         }
     }
